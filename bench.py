@@ -2,8 +2,15 @@
 """Benchmark of the gradient-bucket allreduce engine (BASELINE.json metric:
 "device-resident allreduce GiB/s vs bucket size at 1/2/4/8 MI355X").
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints the result line. --dump-outputs DIR
+also writes what the last timed step computed (N = 1: the accumulator, reduce_acc.npy; N > 1:
+every rank's result, allreduce_recv_rank<r>.npy; float32, a fixed seeded sample of the bucket;
+the inputs are seeded, so two builds run with the same arguments can be compared file for file).
+--full adds every other leg to the line: the sweeps, kernel variants and folds, the host and
+fusion paths, RCCL's comparator, the parity check and the CPU baselines named below.
 
 A step is one pass of the hot path over one bucket resident in HBM:
   * N = 1 (BASELINE configs[1], "1xMI355X: local reduce kernel only, fp32 bucket sweep"): the
@@ -44,6 +51,13 @@ def parse():
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--bucket-mib', type=int, default=256)
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline steps also run every other leg (kernel variants, size sweeps, folds, '
+                         'host and fusion paths, comparators, parity check, CPU baselines); the --no-* options '
+                         'below drop single legs of it')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last timed step computed as DIR/<name>.npy '
+                         '(float32; a fixed seeded sample of the bucket, see dump_outputs)')
     ap.add_argument('--no-cta-sweep', action='store_true', help='N>1: skip the RCCL channel-bound sweep')
     ap.add_argument('--no-sweep', action='store_true')
     ap.add_argument('--no-variants', action='store_true')
@@ -75,6 +89,27 @@ def parse():
                     help='reduce kernel variant bits (-1 default; 1 nt-load a, 2 nt-load b, 4 nt-store, 8 lds b, '
                          '16 write-through store)')
     return ap.parse_args()
+
+
+DUMP_BUDGET_BYTES = 32 << 20  # all files of one run together
+
+
+def dump_outputs(dirname, name, t, budget_bytes):
+    """--dump-outputs: the device tensor `t` (what the last timed step left with its caller) as
+    dirname/name.npy in float32. A tensor over `budget_bytes` is sampled at fixed positions: the
+    first and the last eighth of the budget (the ragged ends of the launch) and seeded random
+    positions in between, in ascending order — the same positions in every run of the same shape."""
+    import numpy as np
+    import torch
+    n, k = t.numel(), budget_bytes // 4
+    flat = t.detach().reshape(-1)
+    if n > k:
+        edge = k // 8
+        mid = np.sort(np.random.default_rng(20240607).integers(edge, n - edge, size=k - 2 * edge))
+        idx = np.concatenate([np.arange(edge), mid, np.arange(n - edge, n)])
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, name + '.npy'), flat.float().cpu().numpy())
 
 
 def dispatch_us(workload_key):
@@ -294,16 +329,19 @@ def single_gpu(args):
     ms_per_step = wall * 1e3 / args.steps
     value = S / GiB / (ms_per_step / 1e3)
     achieved = 3.0 * S / (kernel_ms / 1e3) / 1e9
+    if args.dump_outputs and counter[0]:  # the accumulator the last timed step wrote
+        dump_outputs(args.dump_outputs, 'reduce_acc', sets[(counter[0] - 1) % NSETS][0], DUMP_BUDGET_BYTES)
 
     extra = {}
-    if not args.no_variants:  # interleaved rounds in one process (guide §5.4 rule 24)
+    full = args.full  # every leg below is a measurement beside the headline: --full only
+    if full and not args.no_variants:  # interleaved rounds in one process, so no variant gets a cooler card
         best = {k: float('inf') for k in VARIANTS}
         for _ in range(3):
             for k, v in VARIANTS.items():
                 best[k] = min(best[k], timed_kernel_ms(12, variant=v))
         extra['variants_achieved_GBs'] = {k: round(3.0 * S / (t / 1e3) / 1e9, 1) for k, t in best.items()}
 
-    if not args.no_sweep:
+    if full and not args.no_sweep:
         sweep = []
         size = 4 << 10
         while size <= (1 << 30):
@@ -325,7 +363,7 @@ def single_gpu(args):
 
     # the direct schedule's fold at P = 8 (chunk = S/8, 7 received inputs) and the per-hop
     # reduce in the C4 dtypes, on the same rotating-buffer discipline
-    if not args.no_variants:
+    if full and not args.no_variants:
         extra['fold_kernel'] = fold_roofline(lib, dev, sh, S)
         # the fold the reference-order direct schedule runs at P = 8 (MPICH's pre-fold + tree)
         extra['fold_kernel_reference_order'] = fold_roofline(lib, dev, sh, S, order=1)
@@ -392,6 +430,9 @@ def single_gpu(args):
                      'frac_of_measured_copy_peak': round(achieved / HBM_MEASURED_GBS, 4)},
     }
     out.update(extra)
+    if not full:  # the plain run ends with its headline line
+        emit(out)
+        return
     from ddl.torch.communicator import Communicator
     if not args.no_host:
         out['host_resident'] = host_resident_rate(lib, Communicator.world(), S, reps=8)
@@ -1093,15 +1134,9 @@ def multi_gpu(args):
         return timed_fn(lambda: step(variant), steps, warmup)
 
     sec = timed(0, args.steps, args.warmup)
-    # reduce-kernel roofline: time every reduce launch on the engine's compute stream
-    check(lib.ddl_kernel_timing(comm.id, 1), 'ddl_kernel_timing')
-    for _ in range(min(args.steps, 10)):
-        step(0)
-    torch.cuda.synchronize()
-    check(lib.ddl_kernel_timing(comm.id, 0), 'ddl_kernel_timing')
-    launches, kbytes, kms = ctypes.c_longlong(), ctypes.c_double(), ctypes.c_double()
-    check(lib.ddl_kernel_stats(comm.id, ctypes.byref(launches), ctypes.byref(kbytes), ctypes.byref(kms)),
-          'ddl_kernel_stats')
+    if args.dump_outputs:  # every rank's result of the last timed allreduce
+        dump_outputs(args.dump_outputs, f'allreduce_recv_rank{rank}', recv, DUMP_BUDGET_BYTES // world)
+    full = args.full  # everything but the headline steps is a leg of its own: --full only
     # the autotuner's record for this bucket (tuned during the first warmup call)
     tune = None
     chosen, count = ctypes.c_int(-1), ctypes.c_int(0)
@@ -1111,22 +1146,11 @@ def multi_gpu(args):
           'ddl_tune_result')
     if chosen.value >= 0:
         tune = tuner_table(chosen, count, cfgs, tms)
-    # correctness spot check: every rank's sum must match (checksum of checksums)
-    step(0)
-    torch.cuda.synchronize()
-    cs = torch.tensor([recv.double().sum().item()], dtype=torch.float64)
-    ref = torch.tensor([send.double().sum().item()], dtype=torch.float64)
-    dist.all_reduce(ref)
-    cs_max, cs_min = cs.clone(), cs.clone()
-    dist.all_reduce(cs_max, op=dist.ReduceOp.MAX)
-    dist.all_reduce(cs_min, op=dist.ReduceOp.MIN)
 
     ms = sec * 1e3
     algbw = S / GiB / sec
     busbw_gbs = 2 * (world - 1) / world * S / sec / 1e9
     ceiling = link_ceiling(world)
-    avg_kernel_ms = kms.value / max(1, launches.value)
-    achieved = kbytes.value / max(1e-9, kms.value / 1e3) / 1e9
     out = {
         'metric': 'device-resident allreduce GiB/s vs bucket size at 1/2/4/8 MI355X',
         'value': round(algbw, 2),
@@ -1158,24 +1182,61 @@ def multi_gpu(args):
                           dict(ceiling, frac=round(busbw_gbs / ceiling['busbw_ceiling_GBs'], 4),
                                algbw_frac=round(algbw * GiB / 1e9 / ceiling['algbw_ceiling_GBs'], 4))),
         'autotune': tune,
-        'roofline': {'bound': 'hbm', 'achieved': round(achieved, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                     'frac': round(achieved / HBM_PEAK_GBS, 4), 'traffic': None,
-                     'traffic_note': 'no PMC pass on the node; the same kernels measured 1.0001-1.0002x '
-                                     'algorithmic bytes on one GPU (profiles/pmc_traffic.json)',
-                     'kernel': (f'k_sumN_run / k_sumN_tile<float,{world - 1}> ({tune["chosen"]["algo"]} fold; run form '
-                                f'from 4 MiB slices at P >= 7)'
-                                if tune and tune['chosen']['algo'] != 'ring' else
-                                'k_sum2_tile<float> (reduce-scatter step, all rings in one launch)'),
-                     'avg_kernel_ms': round(avg_kernel_ms, 4), 'launches_timed': launches.value},
-        'check': {'sum_of_recv_min': cs_min.item(), 'sum_of_recv_max': cs_max.item(),
-                  'sum_of_inputs': ref.item()},
     }
+    if full:
+        # reduce-kernel roofline: time every reduce launch on the engine's compute stream
+        check(lib.ddl_kernel_timing(comm.id, 1), 'ddl_kernel_timing')
+        for _ in range(min(args.steps, 10)):
+            step(0)
+        torch.cuda.synchronize()
+        check(lib.ddl_kernel_timing(comm.id, 0), 'ddl_kernel_timing')
+        launches, kbytes, kms = ctypes.c_longlong(), ctypes.c_double(), ctypes.c_double()
+        check(lib.ddl_kernel_stats(comm.id, ctypes.byref(launches), ctypes.byref(kbytes), ctypes.byref(kms)),
+              'ddl_kernel_stats')
+        avg_kernel_ms = kms.value / max(1, launches.value)
+        achieved = kbytes.value / max(1e-9, kms.value / 1e3) / 1e9
+        out['roofline'] = {
+            'bound': 'hbm', 'achieved': round(achieved, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+            'frac': round(achieved / HBM_PEAK_GBS, 4), 'traffic': None,
+            'traffic_note': 'no PMC pass on the node; the same kernels measured 1.0001-1.0002x '
+                            'algorithmic bytes on one GPU (profiles/pmc_traffic.json)',
+            'kernel': (f'k_sumN_run / k_sumN_tile<float,{world - 1}> ({tune["chosen"]["algo"]} fold; run form '
+                       f'from 4 MiB slices at P >= 7)'
+                       if tune and tune['chosen']['algo'] != 'ring' else
+                       'k_sum2_tile<float> (reduce-scatter step, all rings in one launch)'),
+            'avg_kernel_ms': round(avg_kernel_ms, 4), 'launches_timed': launches.value}
+        # correctness spot check: every rank's sum must match (checksum of checksums)
+        step(0)
+        torch.cuda.synchronize()
+        cs = torch.tensor([recv.double().sum().item()], dtype=torch.float64)
+        ref = torch.tensor([send.double().sum().item()], dtype=torch.float64)
+        dist.all_reduce(ref)
+        cs_max, cs_min = cs.clone(), cs.clone()
+        dist.all_reduce(cs_max, op=dist.ReduceOp.MAX)
+        dist.all_reduce(cs_min, op=dist.ReduceOp.MIN)
+        out['check'] = {'sum_of_recv_min': cs_min.item(), 'sum_of_recv_max': cs_max.item(),
+                        'sum_of_inputs': ref.item()}
     if args.rehearse:
         out['rehearsal'] = 'point-to-point over gloo host copies on one GPU: exercises the N>1 legs, NOT a measurement'
     elif args.rehearse_rccl:
         out['rehearsal'] = ('real multi-rank RCCL communicators on one GPU (NCCL_HOSTID per rank: RCCL\'s socket '
                             'transport over loopback): the node\'s code path end to end, NOT an xGMI measurement')
     state['out'] = out  # from here on a hung optional leg still reports the headline result
+
+    def finish():
+        state['leg'] = 'finalize'
+        if rank == 0:
+            emit(out)
+        state['printed'] = True  # a hang in teardown must not print a second line
+        dist.barrier()
+        from ddl.torch.communicator import finalize
+        finalize()
+        dist.destroy_process_group()
+        dog.cancel()
+
+    if not full:  # the plain run ends with its headline line
+        finish()
+        return
     # parity on this node first, so no optional leg can hide it: every rank's result equals
     # MPI_Allreduce's (MPICH 3.3.2 order) bit for bit, on both sides of MPICH's 2048-byte switch
     state['leg'] = 'parity'
@@ -1474,15 +1535,7 @@ def multi_gpu(args):
         graph = replay = None
         gc.collect()
         torch.cuda.synchronize()
-    state['leg'] = 'finalize'
-    if rank == 0:
-        emit(out)
-    state['printed'] = True  # a hang in teardown must not print a second line
-    dist.barrier()
-    from ddl.torch.communicator import finalize
-    finalize()
-    dist.destroy_process_group()
-    dog.cancel()
+    finish()
 
 
 def tuner_table(chosen, count, cfgs, tms):

@@ -14,7 +14,7 @@ if [ -z "$SKIP_TESTS" ]; then
   rc=$?; echo "smoke rc=$rc"; tail -1 $O/smoke.log
   if crashed $rc; then exit $rc; fi
 fi
-timeout -k 10 400 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err
+timeout -k 10 400 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
 rc=$?; echo "bench rc=$rc"; tail -c 300 $O/bench_n1.json; echo
 if crashed $rc; then exit $rc; fi
 if [ -z "$SKIP_PROF" ]; then TAG=$TAG bash scripts/gpu_profile.sh; fi
