@@ -79,7 +79,6 @@ void negotiate_keys(ControlChannel &ch, const char *keys, char *out, size_t len)
     Agreed a;
     if (ch.rank() == 0) {
         a = negotiate_root(ch, cached, idx, mine);
-        negotiate_root_finish(ch);
     } else {
         Token t;
         ch.recv(t, -1);

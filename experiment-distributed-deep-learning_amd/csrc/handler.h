@@ -22,7 +22,6 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
-#include <functional>
 #include <map>
 #include <memory_resource>
 #include <memory>
@@ -32,9 +31,10 @@
 #include <unordered_map>
 #include <vector>
 
-#include "control.h"
 #include "engine.h"
 #include "fusion.h"
+#include "host_stage.h"
+#include "negotiate.h"
 
 namespace ddl {
 
@@ -46,12 +46,6 @@ struct ReadyEvent {
     ReadyEvent(const ReadyEvent &) = delete;
     ReadyEvent &operator=(const ReadyEvent &) = delete;
 };
-
-// Request types, numbered as the reference's Token::RequestType (rtc/Token.h:23-29); the type
-// name prefixes the key on the wire and in the pending map ("Allreduce::grad_0", as
-// RingTokenCommunicateHandler.cc:140-146 builds its ready keys).
-enum RequestType : int { kReqAllreduce = 1, kReqBroadcast = 2, kReqAllgather = 3 };
-const char *request_type_name(int type);
 
 struct Request {
     int type = kReqAllreduce;
@@ -72,78 +66,7 @@ struct Request {
     void *user = nullptr;
 };
 
-// Parallel host memcpy for the host-staging pipeline (pageable <-> pinned): one memcpy thread
-// moves ~10 GB/s, less than the PCIe link, so large chunks are split over a few workers.
-class CopyPool {
-public:
-    struct Piece {
-        void *dst;
-        const void *src;
-        size_t bytes;
-    };
-    // cpus non-empty: every worker binds itself to that CPU set (the GPU's NUMA node)
-    explicit CopyPool(int threads, std::vector<int> cpus = {});
-    ~CopyPool();
-    CopyPool(const CopyPool &) = delete;
-    CopyPool &operator=(const CopyPool &) = delete;
-    // Copies every piece; returns when all are done (the caller's thread takes a share).
-    void run(const std::vector<Piece> &pieces);
-    // fn(lo, hi) over [0, n) cut into one range per thread (the caller's thread takes the first);
-    // returns when every range is done
-    void parallel(size_t n, const std::function<void(size_t, size_t)> &fn);
-    int threads() const { return (int)threads_.size(); }
-
-private:
-    void worker_();
-    void submit_and_wait_(std::vector<std::function<void()>> &tasks);  // tasks[0] on the caller
-    std::vector<int> cpus_;
-    std::vector<std::thread> threads_;
-    std::mutex mu_;
-    std::condition_variable cv_, done_cv_;
-    std::vector<std::function<void()>> queue_;
-    size_t outstanding_ = 0;
-    bool stop_ = false;
-};
-
-// One worker thread running jobs in submission order: the host unpack of staged chunks, so the
-// engine thread packs chunk i (CopyPool) while chunk i - kHostSlots is unpacked (its own CopyPool)
-// — the two host memcpys overlap instead of alternating on the engine thread. wait(seq) blocks
-// until job `seq` (1-based, from submit) has run; a job's Error is rethrown by the next wait.
-class AsyncLane {
-public:
-    explicit AsyncLane(std::vector<int> cpus = {});
-    ~AsyncLane();
-    AsyncLane(const AsyncLane &) = delete;
-    AsyncLane &operator=(const AsyncLane &) = delete;
-    uint64_t submit(std::function<void()> job);
-    void wait(uint64_t seq);
-    void drain() noexcept;  // every job submitted so far has run (errors dropped)
-
-private:
-    void worker_();
-    std::vector<int> cpus_;
-    std::mutex mu_;
-    std::condition_variable cv_, done_cv_;
-    std::deque<std::function<void()>> q_;
-    uint64_t submitted_ = 0, done_ = 0;
-    bool stop_ = false;
-    bool failed_ = false;
-    Error err_{0, ""};
-    std::thread thread_;
-};
-
-// Request identity: (type, key), ordered as the reference's (typeName, key) pairs —
-// "Allgather" < "Allreduce" < "Broadcast", then the key bytewise. On the wire it is the string
-// "<TypeName>::<key>".
-struct ReqId {
-    int order;  // type_order(type)
-    std::string key;
-    bool operator<(const ReqId &o) const { return order != o.order ? order < o.order : key < o.key; }
-};
-int type_order(int type);
 ReqId req_id(const Request &r);
-std::string wire_id(const ReqId &id);
-ReqId parse_wire_id(const std::string &s);  // throws on an unknown type name
 
 struct Plan {  // makeCollectiveCommunicatePlan's (requestBegin, elementBegin, requestEnd, elementEnd)
     size_t req_begin, elem_begin, req_end, elem_end;
@@ -157,43 +80,6 @@ struct Plan {  // makeCollectiveCommunicatePlan's (requestBegin, elementBegin, r
 std::vector<Plan> make_plans(const std::vector<size_t> &elements, const std::vector<size_t> &esize,
                              size_t limit);
 
-// The process's listening / standalone control channel: ddl_control_listen opens it,
-// ddl_control_connect hands it to the world communicator (replacing it with a fresh one),
-// ddl_control_connect_ranked keeps it for ddl_control_negotiate (tools, CPU tests).
-std::shared_ptr<ControlChannel> &standalone_control();
-
-// One negotiation round over the star (control.h).
-//   root:   SYNC(proposal) to every member; every member's SYNC(intersection) back; the
-//           proposal's ids every member kept go out as COMMUNICATE(agreed). (negotiate_root_finish
-//           is a no-op kept for the ring's call sites.)
-//   member: receives SYNC, intersects with what it holds (may block until the first proposed
-//           id is registered), answers rank 0, then receives COMMUNICATE.
-// A proposal made only of ids agreed in earlier rounds travels as indices into the channel's
-// IdCache (TOKEN_*_CACHED) and is intersected by index; otherwise as "Type::key" strings.
-// Every token also carries the sender's Config::shared_hash(): rank 0 compares the members'
-// with its own and the COMMUNICATE says whether they all agree (cfg_ok); a round whose ranks
-// disagree takes its agreed requests out on every rank and fails them with
-// DDL_STATUS_CONFIG_MISMATCH instead of running them. `snapshot` (optional) freezes the rank's
-// user collectives and returns how many it has issued (Communicator::round_freeze): members
-// call it right before answering, rank 0 once every answer is in; the COMMUNICATE carries the
-// maximum (release: the round goes after that many user collectives on every rank, -1 without
-// snapshots).
-struct Agreed {
-    bool cached = false;
-    std::vector<uint32_t> idx;      // cached round: indices into ch.cache
-    std::vector<std::string> wire;  // string round: ids, sorted (their (type, key) order)
-    bool cfg_ok = true;
-    long long release = -1;
-};
-Agreed negotiate_root(ControlChannel &ch, bool cached, const std::vector<uint32_t> &idx,
-                      const std::vector<std::string> &strs, int request_type = kReqAllreduce,
-                      const std::function<long long()> &snapshot = nullptr);
-void negotiate_root_finish(ControlChannel &ch);
-Agreed negotiate_member(ControlChannel &ch, const Token &sync,
-                        const std::function<std::vector<std::string>(const std::vector<std::string> &)> &by_string,
-                        const std::function<std::vector<uint32_t>(const std::vector<uint32_t> &)> &by_index,
-                        const std::function<long long()> &snapshot = nullptr);
-
 class RequestHandler {
 public:
     explicit RequestHandler(Communicator *owner);
@@ -201,14 +87,9 @@ public:
     hipStream_t stream() const { return stream_; }  // the engine thread's (pack / unpack)
 
     void submit(Request r);
-    // Unregisters every range of the host registration cache (ddl_set_config
-    // "host_register_cache_bytes" 0): waits for the handler's streams first.
-    void release_registrations();
-    // The host range [ptr, ptr + bytes) is about to be freed (ddl_host_unregister): every cached
-    // registration overlapping it goes — now if no host plan is being posted, otherwise before the
-    // next lookup of the cache (the engine thread drains the queue first), so a later tensor at the
-    // same address is never taken for the old, still-registered pages.
-    void unregister_range(const void *ptr, size_t bytes);
+    // the host registration cache (host_stage.h HostRegistrations), from the user's threads
+    void release_registrations() { host_->registrations().release_all(); }
+    void unregister_range(const void *ptr, size_t bytes) { host_->registrations().unregister_range(ptr, bytes); }
     // All-or-nothing registration of several requests under one lock (one wake-up).
     void submit_batch(std::vector<Request> &rs);
     void wait_all();
@@ -254,40 +135,14 @@ private:
     void completer_();                    // the completion thread
     void wait_inputs_(const Request &r, std::vector<hipEvent_t> &waited);
     void *ensure_(void *&buf, size_t &cap, size_t need);
+    // A host group (`host`) holds the registration lock while its plans are posted; with the
+    // cache on, its tensors (reqs[i] for i in `group`) are registered first. Not held otherwise.
+    std::unique_lock<std::mutex> lock_host_group_(const std::vector<Request> &reqs, const std::vector<size_t> &group,
+                                                  size_t es, bool host);
+    // Records plan p's event; done() is due for every request of `group` whose last element it carries.
+    void finish_plan_(const Plan &p, const std::vector<Request> &reqs, const std::vector<size_t> &group,
+                      std::vector<Done> &dones, size_t &nplans);
     void allreduce_reqs_(std::vector<Request> &reqs, std::vector<Done> &dones, size_t &nplans);
-    // Host-resident requests (the reference's deployment case, MPIRingTokenCommunication.cc:
-    // 548-733 copies CPU tensors into its MPI buffer): the plan's segments are staged through
-    // pinned slots in chunks — host pack (CopyPool) -> H2D -> `coll` on the device slot
-    // (stream_) -> D2H -> host unpack — with kHostSlots chunks in flight so the copies overlap
-    // the collective. `upload` false: nothing is packed (a broadcast's non-root ranks).
-    // `padded`: segment i starts at the 256-byte-rounded running offset (the fusion kernels'
-    // layout), so plans with and without `device_unpack` cut the same chunks — and issue the
-    // same collectives — on ranks that differ in which outputs are pinned; otherwise back to
-    // back (broadcast, as the reference packs).
-    // `device_unpack` (every destination pinned and mapped on the device, mapped_host_dsts_): the
-    // unpack kernel writes each chunk's result straight into the outputs over PCIe (d2h_), in
-    // place of the D2H copy and the host unpack; the host never waits for a chunk to come back
-    // (measured 43 GB/s each way with the uploads running, vs 32 when the pack kernel also
-    // reads the tensors over PCIe: profiles/r02/host/zero_copy_probe.jsonl).
-    struct HostSeg {
-        const char *src;
-        char *dst;
-        size_t bytes;
-        char *ddst = nullptr;  // the device's address of dst (device unpack; mapped_host_dsts_)
-    };
-    void host_staged_(const std::vector<HostSeg> &segs, size_t es, bool upload,
-                      const std::function<void(void *dev, size_t elems)> &coll, bool padded = false,
-                      bool device_unpack = false);
-    void host_pieces_(const std::vector<HostSeg> &segs, const std::vector<size_t> &starts, size_t off, size_t len,
-                      char *pinned, bool pack, std::vector<CopyPool::Piece> &out);
-    // true when every segment's destination range is 16-byte-aligned pinned host memory that the
-    // device reaches at the same address, inside one allocation
-    // fills every segment's ddst; false unless all of them are mapped
-    // (the queries of a plan's 4096 tensors run on the copy threads: ~3 HIP calls each)
-    bool mapped_host_dsts_(std::vector<HostSeg> &segs);
-    size_t host_slots_(size_t total);  // chunk size for `total` bytes; (re)allocates the slots
-    CopyPool &pool_for_config_();     // the copy threads, rebuilt when host_copy_threads changed
-    std::vector<int> local_cpus_;     // the GPU's NUMA node's CPUs (config host_numa_bind; empty: no binding)
     void broadcast_reqs_(std::vector<Request> &reqs, std::vector<Done> &dones, size_t &nplans);
     void allgather_reqs_(std::vector<Request> &reqs, std::vector<Done> &dones, size_t &nplans);
     void fail_all_(int status);
@@ -302,43 +157,13 @@ private:
     // multi-request plans: pack -> allreduce -> unpack, pipelined in sub-plans above
     // fusion_pipeline_bytes (fusion.h); its buffer 0 also packs broadcast / allgather plans
     FusionPipe fp_;
+    // host-resident requests: made once stream_ exists, destroyed (both threads joined) before it
+    std::unique_ptr<HostStager> host_;
     void *gather_ = nullptr;  // allgather receive side
     size_t gather_bytes_ = 0;
     void *dims_ = nullptr;    // allgather first-dim exchange
     size_t dims_bytes_ = 0;
     std::vector<hipEvent_t> round_events_;  // plan events of the round being enqueued (engine thread)
-    static constexpr int kHostSlots = 4;
-    void *pin_[kHostSlots] = {};    // pinned host staging slots (uploads)
-    void *pout_[kHostSlots] = {};   // pinned download slots: a chunk's D2H lands here, apart from the
-                                    // upload slot, so its host unpack overlaps the next packs
-    void *dslot_[kHostSlots] = {};  // device slots
-    size_t host_slot_bytes_ = 0;
-    hipStream_t h2d_ = nullptr, d2h_ = nullptr;
-    hipEvent_t hev_[3 * kHostSlots] = {};  // per slot: input landed, collective done, output landed
-    bool slot_used_[kHostSlots] = {};        // hev_[3k + 2] marks the slot's last device use
-    std::unique_ptr<CopyPool> pool_;
-    // the host unpack of staged chunks (its own copy threads, host_copy_threads of them); the lane
-    // is destroyed first (its jobs use out_pool_)
-    std::unique_ptr<CopyPool> out_pool_;
-    std::unique_ptr<AsyncLane> lane_;
-    // opt-in registration cache (config "host_register_cache_bytes"): pageable host tensors of
-    // keyed requests are hipHostRegister'ed once and kept (least recently used out past the cap),
-    // so a training loop's CPU gradients take the pinned paths (direct DMA in, device unpack out)
-    // registers the page ranges of (pointer, bytes) that are not pinned yet: ranges sharing a page
-    // are merged (a page cannot be registered twice), overlapping entries join the union
-    void register_hosts_(const std::vector<std::pair<const void *, size_t>> &ranges);
-    void unregister_all_();  // the cache was switched off (host_register_cache_bytes 0)
-    // drops the entries overlapping [lo, hi) (reg_mu_ held); syncs the handler's streams first
-    void drop_overlapping_(uintptr_t lo, uintptr_t hi);
-    void drain_unregisters_();  // reg_mu_ held: the queued unregister_range calls
-    std::mutex unreg_mu_;
-    std::vector<std::pair<uintptr_t, uintptr_t>> unreg_q_;
-    std::mutex reg_mu_;  // reg_: the engine thread registers, ddl_set_config may release
-    std::map<uintptr_t, std::pair<size_t, uint64_t>> reg_;  // page-aligned start -> (bytes, last use)
-    size_t reg_bytes_ = 0;
-    uint64_t reg_tick_ = 0;
-    void *pin_gather_ = nullptr;  // host allgather staging
-    size_t pin_gather_bytes_ = 0;
 
     std::mutex mu_;
     std::condition_variable cv_;       // new registrations / stop
@@ -346,8 +171,8 @@ private:
     // the pending map's nodes come from a pool, allocated and freed under mu_ only: a 4096-request
     // batch's sorted inserts and its take walk ran 2-3x faster than with the process heap
     // (CPU micro-benchmark; r05 s22 on the box)
-    std::pmr::unsynchronized_pool_resource pending_pool_;
-    std::pmr::map<ReqId, Request> pending_{&pending_pool_};  // (type name, key) order
+    std::pmr::unsynchronized_pool_resource pending_mem_;
+    std::pmr::map<ReqId, Request> pending_{&pending_mem_};  // (type name, key) order
     // id table mirror (indices of the ring's cache): parsed ids, key -> index per type,
     // and which indices are pending here — a cached round is intersected by index
     std::vector<ReqId> cache_req_;
@@ -362,7 +187,7 @@ private:
     std::mutex done_mu_;
     std::condition_variable done_cv_;
     std::deque<Round> rounds_;
-    std::vector<hipEvent_t> event_pool_;
+    std::vector<hipEvent_t> free_events_;
     unsigned long long rounds_queued_ = 0, rounds_done_ = 0;
     bool done_stop_ = false;
     std::thread done_thread_;
@@ -371,9 +196,5 @@ private:
 // Test hook (ddl_testing_control_fault): the next keyed round a member joins closes that member's
 // control link right after its snapshot froze the user collectives (a link lost mid-round).
 void set_testing_control_fault(int on);
-// Test hook (ddl_testing_host_coll_fault): the next host plan's staging loop fails at chunk
-// `chunk` (-1: off) — its device collective is not posted — to check that no unpack job of the
-// chunks before outlives the plan.
-void set_testing_host_coll_fault(long long chunk);
 
 }  // namespace ddl
