@@ -34,6 +34,8 @@ def parse():
     p.add_argument('--warmup_epochs', default=5, type=int)
     p.add_argument('--lr', default=0.001, type=float)
     p.add_argument('--samples', default=60000, type=int, help='synthetic training samples (all ranks)')
+    p.add_argument('--fused-mean', action='store_true',
+                   help='let the engine average the gradients (DDL_ALLREDUCE_OP_AVG) instead of a div_ per gradient')
     return p.parse_args()
 
 
@@ -75,7 +77,7 @@ def main():
     # scale the lr by the number of replicas; the warm-up ramps to it from slightly above base_lr
     scaled_lr = world.size * args.lr
     optimizer = data_parallelism_distributed_optimizer_wrapper(torch.optim.Adam(model.parameters(), lr=scaled_lr),
-                                                               world)
+                                                               world, fused_mean=args.fused_mean)
     if world.size > 1:
         InitialParametersBroadcast(model, 0, optimizer, communicator=world).broadcast()
     steps = max(1, len(x_train) // args.batch_size)

@@ -381,14 +381,32 @@ int ddl_unpack(void *const *dsts, const void *src, const size_t *bytes, int coun
     });
 }
 
+int ddl_unpack_ops(void *const *dsts, const void *src, const size_t *bytes, const int *ops, int count, int dtype,
+                   int divisor, void *hip_stream) {
+    return guarded([&] {
+        DDL_REQUIRE(count >= 0 && (count == 0 || (dsts && bytes && ops)) && divisor >= 1, DDL_STATUS_INVALID_ARGUMENT,
+                    "bad unpack_ops args");
+        std::lock_guard<std::mutex> g(abi_copier_mu());
+        abi_copier().run(src ? 1 : SegmentCopier::kDivInPlace, const_cast<void *>(src), dsts, bytes, count,
+                         as_stream(hip_stream), dtype, divisor, ops);
+    });
+}
+
 int ddl_local_ring_allreduce(int nranks, const void *const *sends, void *const *recvs, size_t elements,
                              int dtype, int op, void *hip_stream) {
     return guarded([&] {
         DDL_REQUIRE(nranks >= 1 && nranks <= 64, DDL_STATUS_INVALID_ARGUMENT, "nranks " << nranks);
-        DDL_REQUIRE(op == DDL_ALLREDUCE_OP_SUM, DDL_STATUS_INVALID_ARGUMENT, "only SUM");
+        check_allreduce_op(op, dtype);
         DDL_REQUIRE(sends && recvs, DDL_STATUS_INVALID_ARGUMENT, "null buffer arrays");
         (void)current_device();
         local_world(nranks).allreduce(sends, recvs, elements, dtype, as_stream(hip_stream), config().ring());
+        if (op == DDL_ALLREDUCE_OP_AVG && nranks > 1 && elements) {  // every rank's result, one launch
+            const std::vector<size_t> bytes(nranks, elements * dtype_size(dtype));
+            const std::vector<int> ops(nranks, op);
+            std::lock_guard<std::mutex> g(abi_copier_mu());
+            abi_copier().run(SegmentCopier::kDivInPlace, nullptr, recvs, bytes.data(), nranks, as_stream(hip_stream), dtype,
+                             nranks, ops.data());
+        }
     });
 }
 
@@ -423,22 +441,35 @@ int ddl_local_allgatherv(int nranks, const void *const *sends, void *const *recv
 }
 
 // ---- thread world: the production RingExecutor per rank, asynchronous transport --------------------
-int ddl_testing_thread_allreduce(int nranks, const void *const *sends, void *const *recvs, size_t elements, int dtype,
-                                 void *hip_stream) {
+int ddl_testing_thread_allreduce_op(int nranks, const void *const *sends, void *const *recvs, size_t elements,
+                                    int dtype, int op, void *hip_stream) {
     return guarded([&] {
         DDL_REQUIRE(nranks >= 1 && nranks <= 64 && sends && recvs, DDL_STATUS_INVALID_ARGUMENT, "bad thread allreduce");
-        thread_world(nranks).allreduce(sends, recvs, elements, dtype, as_stream(hip_stream), config().ring());
+        check_allreduce_op(op, dtype);
+        thread_world(nranks).allreduce(sends, recvs, elements, dtype, as_stream(hip_stream), config().ring(), op);
+    });
+}
+
+int ddl_testing_thread_allreduce(int nranks, const void *const *sends, void *const *recvs, size_t elements, int dtype,
+                                 void *hip_stream) {
+    return ddl_testing_thread_allreduce_op(nranks, sends, recvs, elements, dtype, DDL_ALLREDUCE_OP_SUM, hip_stream);
+}
+
+int ddl_testing_thread_allreduce_batch_op(int nranks, int count, const void *const *sends, void *const *recvs,
+                                          const size_t *elements, int dtype, int op, void *hip_stream) {
+    return guarded([&] {
+        DDL_REQUIRE(nranks >= 1 && nranks <= 64 && count >= 0 && (count == 0 || (sends && recvs && elements)),
+                    DDL_STATUS_INVALID_ARGUMENT, "bad thread allreduce batch");
+        check_allreduce_op(op, dtype);
+        thread_world(nranks).allreduce_batch(sends, recvs, elements, count, dtype, as_stream(hip_stream),
+                                             config().ring(), op);
     });
 }
 
 int ddl_testing_thread_allreduce_batch(int nranks, int count, const void *const *sends, void *const *recvs,
                                        const size_t *elements, int dtype, void *hip_stream) {
-    return guarded([&] {
-        DDL_REQUIRE(nranks >= 1 && nranks <= 64 && count >= 0 && (count == 0 || (sends && recvs && elements)),
-                    DDL_STATUS_INVALID_ARGUMENT, "bad thread allreduce batch");
-        thread_world(nranks).allreduce_batch(sends, recvs, elements, count, dtype, as_stream(hip_stream),
-                                             config().ring());
-    });
+    return ddl_testing_thread_allreduce_batch_op(nranks, count, sends, recvs, elements, dtype, DDL_ALLREDUCE_OP_SUM,
+                                                 hip_stream);
 }
 
 int ddl_testing_thread_broadcast(int nranks, int root, void *const *bufs, size_t elements, int dtype,
@@ -461,6 +492,12 @@ int ddl_testing_thread_allgatherv(int nranks, const void *const *sends, void *co
 
 int ddl_testing_thread_fused_allreduce(int nranks, int count, const void *const *srcs, void *const *dsts,
                                        const size_t *bytes, int dtype, void *hip_stream, size_t *subplans) {
+    return ddl_testing_thread_fused_allreduce_ops(nranks, count, srcs, dsts, bytes, nullptr, dtype, hip_stream, subplans);
+}
+
+int ddl_testing_thread_fused_allreduce_ops(int nranks, int count, const void *const *srcs, void *const *dsts,
+                                           const size_t *bytes, const int *ops, int dtype, void *hip_stream,
+                                           size_t *subplans) {
     return guarded([&] {
         DDL_REQUIRE(nranks >= 1 && nranks <= 64 && count >= 1 && srcs && dsts && bytes, DDL_STATUS_INVALID_ARGUMENT,
                     "bad thread fused allreduce");
@@ -468,9 +505,10 @@ int ddl_testing_thread_fused_allreduce(int nranks, int count, const void *const 
         DDL_REQUIRE(es != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported dtype " << dtype);
         for (int i = 0; i < count; ++i)
             DDL_REQUIRE(bytes[i] % es == 0, DDL_STATUS_INVALID_ARGUMENT, "segment " << i << " is not whole elements");
+        for (int i = 0; ops && i < count; ++i) check_allreduce_op(ops[i], dtype);
         const size_t j = thread_world(nranks).fused_allreduce(srcs, dsts, bytes, count, dtype, as_stream(hip_stream),
                                                               config().ring(),
-                                                              (size_t)config().fusion_pipeline_bytes.load());
+                                                              (size_t)config().fusion_pipeline_bytes.load(), ops);
         if (subplans) *subplans = j;
     });
 }

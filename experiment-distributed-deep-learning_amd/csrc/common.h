@@ -40,6 +40,10 @@ inline const char *dtype_name(int dt) {
     }
 }
 
+inline bool dtype_is_float(int dt) {
+    return dt == DDL_FLOAT || dt == DDL_DOUBLE || dt == DDL_HALF || dt == DDL_BFLOAT16;
+}
+
 // Thread-local description of the last failure (ddl_last_error).
 void set_error(const std::string &msg);
 const char *last_error();
@@ -72,6 +76,15 @@ struct Error {
             ::ddl::fail((status), _os.str());             \
         }                                                 \
     } while (0)
+
+// The op of every allreduce entry point: SUM or AVG, AVG on float types only. Refused before
+// anything is posted; the dtype is the same on every rank, so all ranks refuse together.
+inline void check_allreduce_op(int op, int dtype) {
+    DDL_REQUIRE(op == DDL_ALLREDUCE_OP_SUM || op == DDL_ALLREDUCE_OP_AVG, DDL_STATUS_INVALID_ARGUMENT,
+                "unknown allreduce op " << op << " (SUM = 0, AVG = 1)");
+    DDL_REQUIRE(op != DDL_ALLREDUCE_OP_AVG || dtype_size(dtype) == 0 || dtype_is_float(dtype),
+                DDL_STATUS_UNSUPPORTED_DTYPE, "AVG is not defined for " << dtype_name(dtype));
+}
 
 // Logging (the reference logs per rank to log-<rank>.txt, GlobalLog.cc:17-49; here
 // stderr, gated by the "log_level" config: 0 errors, 1 info, 2 debug).
@@ -206,7 +219,14 @@ public:
     ~SegmentCopier();
     SegmentCopier(const SegmentCopier &) = delete;
     SegmentCopier &operator=(const SegmentCopier &) = delete;
-    void run(int dir, void *flat, void *const *segs, const size_t *bytes, int count, hipStream_t stream);
+    // DDL_ALLREDUCE_OP_AVG (`ops[i]` per segment, `divisor` = the communicator's size, `dtype` a
+    // float type): the scatter (dir 1) stores the quotient of the AVG segments' elements and copies
+    // the others — one launch of k_seg_div in place of k_seg_tiles; dir kDivInPlace divides the AVG
+    // segments where they are (`flat` unused, the other segments untouched). Without an AVG
+    // segment, or with divisor 1, dir 0 / 1 are the plain copies and kDivInPlace posts nothing.
+    static constexpr int kDivInPlace = 2;
+    void run(int dir, void *flat, void *const *segs, const size_t *bytes, int count, hipStream_t stream,
+             int dtype = 0, int divisor = 1, const int *ops = nullptr);
     static size_t flat_bytes(const size_t *bytes, int count);
 
 private:

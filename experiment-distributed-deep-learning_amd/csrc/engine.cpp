@@ -254,7 +254,7 @@ void Communicator::agree_config(hipStream_t stream) {
 
 void Communicator::allreduce(const void *send, void *recv, size_t n, int dtype, int op, hipStream_t stream,
                              size_t order_bytes) {
-    DDL_REQUIRE(op == DDL_ALLREDUCE_OP_SUM, DDL_STATUS_INVALID_ARGUMENT, "only SUM is supported (op " << op << ")");
+    check_allreduce_op(op, dtype);
     DDL_REQUIRE(dtype_size(dtype) != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported dtype " << dtype);
     DDL_REQUIRE(n == 0 || (send && recv), DDL_STATUS_INVALID_ARGUMENT, "null buffer");
     UserCollective uc(*this);
@@ -262,12 +262,12 @@ void Communicator::allreduce(const void *send, void *recv, size_t n, int dtype, 
     DeviceGuard dg(device_);
     RingConfig cfg = ring_config(n, dtype, stream);
     cfg.order_bytes = order_bytes;
-    exec_->allreduce(send, recv, n, dtype, stream, cfg);
+    exec_->allreduce(send, recv, n, dtype, stream, cfg, op);
 }
 
 void Communicator::allreduce_batch(const void *const *send, void *const *recv, const size_t *n, int count, int dtype,
                                    int op, hipStream_t stream) {
-    DDL_REQUIRE(op == DDL_ALLREDUCE_OP_SUM, DDL_STATUS_INVALID_ARGUMENT, "only SUM is supported (op " << op << ")");
+    check_allreduce_op(op, dtype);
     DDL_REQUIRE(dtype_size(dtype) != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported dtype " << dtype);
     DDL_REQUIRE(count >= 0 && (count == 0 || (send && recv && n)), DDL_STATUS_INVALID_ARGUMENT, "null bucket arrays");
     size_t largest = 0;
@@ -279,7 +279,7 @@ void Communicator::allreduce_batch(const void *const *send, void *const *recv, c
     std::lock_guard<std::mutex> g(mu_);
     DeviceGuard dg(device_);
     const RingConfig cfg = ring_config(largest, dtype, stream);
-    exec_->allreduce_batch(send, recv, n, count, dtype, stream, cfg);
+    exec_->allreduce_batch(send, recv, n, count, dtype, stream, cfg, op);
 }
 
 void Communicator::rccl_allreduce(const void *send, void *recv, size_t n, int dtype, hipStream_t stream) {
@@ -530,7 +530,7 @@ private:
 }  // namespace
 
 void Communicator::allreduce_host(const void *send, void *recv, size_t n, int dtype, int op) {
-    DDL_REQUIRE(op == DDL_ALLREDUCE_OP_SUM, DDL_STATUS_INVALID_ARGUMENT, "only SUM is supported (op " << op << ")");
+    check_allreduce_op(op, dtype);
     const size_t es = dtype_size(dtype);
     DDL_REQUIRE(es != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported dtype " << dtype);
     DDL_REQUIRE(n == 0 || (send && recv), DDL_STATUS_INVALID_ARGUMENT, "null buffer");
@@ -579,7 +579,7 @@ void Communicator::allreduce_host(const void *send, void *recv, size_t n, int dt
             DDL_HIP(hipMemcpyAsync(slots_[s], static_cast<const char *>(send) + off, bytes, hipMemcpyHostToDevice, h2d_));
             DDL_HIP(hipEventRecord(h2d_done, h2d_));
             DDL_HIP(hipStreamWaitEvent(ring_, h2d_done, 0));
-            exec_->allreduce(slots_[s], slots_[s], bytes / es, dtype, ring_, cfg);
+            exec_->allreduce(slots_[s], slots_[s], bytes / es, dtype, ring_, cfg, op);  // AVG: divided in the slot
             DDL_HIP(hipEventRecord(ring_done, ring_));
             DDL_HIP(hipStreamWaitEvent(d2h_, ring_done, 0));
             DDL_HIP(hipMemcpyAsync(static_cast<char *>(recv) + off, slots_[s], bytes, hipMemcpyDeviceToHost, d2h_));

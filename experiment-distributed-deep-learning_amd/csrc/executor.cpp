@@ -242,9 +242,13 @@ KernelStats RingExecutor::collect_stats() {
 }
 
 void RingExecutor::allreduce(const void *in, void *out, size_t n, int dtype, hipStream_t user,
-                             const RingConfig &cfg) {
+                             const RingConfig &cfg, int op) {
     const size_t es = dtype_size(dtype);
     DDL_REQUIRE(es != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported dtype " << dtype);
+    check_allreduce_op(op, dtype);
+    const bool avg = op == DDL_ALLREDUCE_OP_AVG && size_ > 1;
+    DDL_REQUIRE(!avg || !stream_capturing(user), DDL_STATUS_INVALID_ARGUMENT,
+                "an AVG allreduce cannot be captured into a graph: capture the SUM and divide");
     if (n == 0) return;
     if (size_ == 1) {  // P = 1: out = in (the reference never completes here)
         if (in != out) DDL_HIP(hipMemcpyAsync(out, in, n * es, hipMemcpyDeviceToDevice, user));
@@ -253,12 +257,20 @@ void RingExecutor::allreduce(const void *in, void *out, size_t n, int dtype, hip
     void *staging = res_.ensure_staging(program_staging_elems(n, es, size_, cfg) * es, stream_capturing(user));
     build_program(prog_, rank_, size_, in, out, staging, n, dtype, cfg);
     run_(dtype, user);
+    if (avg) {
+        const size_t bytes = n * es;
+        divider_.run(SegmentCopier::kDivInPlace, nullptr, &out, &bytes, 1, user, dtype, size_, &op);
+    }
 }
 
 void RingExecutor::allreduce_batch(const void *const *in, void *const *out, const size_t *n, int count, int dtype,
-                                   hipStream_t user, const RingConfig &cfg) {
+                                   hipStream_t user, const RingConfig &cfg, int op) {
     const size_t es = dtype_size(dtype);
     DDL_REQUIRE(es != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported dtype " << dtype);
+    check_allreduce_op(op, dtype);
+    const bool avg = op == DDL_ALLREDUCE_OP_AVG && size_ > 1;
+    DDL_REQUIRE(!avg || !stream_capturing(user), DDL_STATUS_INVALID_ARGUMENT,
+                "an AVG allreduce cannot be captured into a graph: capture the SUM and divide");
     if (size_ == 1) {
         for (int b = 0; b < count; ++b)
             if (n[b] && in[b] != out[b]) DDL_HIP(hipMemcpyAsync(out[b], in[b], n[b] * es, hipMemcpyDeviceToDevice, user));
@@ -268,6 +280,12 @@ void RingExecutor::allreduce_batch(const void *const *in, void *const *out, cons
                                         stream_capturing(user));
     build_batch_program(prog_, rank_, size_, in, out, n, count, staging, dtype, cfg);
     run_(dtype, user);
+    if (avg && count > 0) {  // one launch over every bucket's result
+        std::vector<size_t> bytes(count);
+        for (int b = 0; b < count; ++b) bytes[b] = n[b] * es;
+        const std::vector<int> ops(count, op);
+        divider_.run(SegmentCopier::kDivInPlace, nullptr, out, bytes.data(), count, user, dtype, size_, ops.data());
+    }
 }
 
 void RingExecutor::broadcast(void *buf, size_t n, int dtype, int root, hipStream_t user, const RingConfig &cfg) {

@@ -183,12 +183,16 @@ public:
     RingExecutor(int rank, int size, int device, std::unique_ptr<Transport> transport,
                  QueueClass qc = QueueClass::kPooled);
     ~RingExecutor();
+    // `op` DDL_ALLREDUCE_OP_AVG: once the program has joined `user`, one in-place launch of the
+    // dividing kernel (SegmentCopier::kDivInPlace) over the result on `user` alone — one segment,
+    // or one per bucket for the batch; nothing at size 1. Refused while `user` is captured (the
+    // copier's table upload and slot events are not capturable).
     void allreduce(const void *in, void *out, size_t n, int dtype, hipStream_t user,
-                   const RingConfig &cfg);
+                   const RingConfig &cfg, int op = DDL_ALLREDUCE_OP_SUM);
     // `count` buckets of one dtype as one grouped program (build_batch_program): one group and
     // batched folds per tick instead of a program per bucket
     void allreduce_batch(const void *const *in, void *const *out, const size_t *n, int count, int dtype,
-                         hipStream_t user, const RingConfig &cfg);
+                         hipStream_t user, const RingConfig &cfg, int op = DDL_ALLREDUCE_OP_SUM);
     void broadcast(void *buf, size_t n, int dtype, int root, hipStream_t user, const RingConfig &cfg);
     void allgatherv(const void *send, void *recv, const size_t *counts, const size_t *displs, int dtype,
                     hipStream_t user);
@@ -206,6 +210,7 @@ private:
     std::unique_ptr<Transport> transport_;
     RankResources res_;
     RingProgram prog_;
+    SegmentCopier divider_;  // the AVG quotient over a finished result
     bool timing_ = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> timed_;  // recorded, not yet collected
     std::vector<double> timed_bytes_;

@@ -40,9 +40,11 @@ hipEvent_t FusionPipe::event_(size_t i) {
 }
 
 void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<void *> &dsts,
-                     const std::vector<size_t> &bytes, int dt, size_t cap, hipStream_t stream, const Allreduce &ar) {
+                     const std::vector<size_t> &bytes, int dt, size_t cap, hipStream_t stream, const Allreduce &ar,
+                     const std::vector<int> *ops, int divisor) {
     const size_t es = dtype_size(dt);
     DDL_REQUIRE(es != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported dtype " << dt);
+    DDL_REQUIRE(!ops || ops->size() == bytes.size(), DDL_STATUS_INVALID_ARGUMENT, "fusion plan: one op per segment");
     DDL_REQUIRE(srcs.size() == bytes.size() && dsts.size() == bytes.size(), DDL_STATUS_INVALID_ARGUMENT,
                 "fusion plan: " << srcs.size() << " sources, " << dsts.size() << " destinations, " << bytes.size()
                                 << " sizes");
@@ -58,13 +60,14 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
         copier.run(0, fb, const_cast<void *const *>(reinterpret_cast<const void *const *>(srcs.data())), bytes.data(),
                    (int)srcs.size(), stream);
         ar(fb, total / es, message);
-        copier.run(1, fb, dsts.data(), bytes.data(), (int)dsts.size(), stream);
+        copier.run(1, fb, dsts.data(), bytes.data(), (int)dsts.size(), stream, dt, divisor, ops ? ops->data() : nullptr);
         return;
     }
     struct Sub {
         std::vector<const void *> src;
         std::vector<void *> dst;
         std::vector<size_t> bytes;
+        std::vector<int> ops;  // of each piece: its segment's (only with `ops`)
         size_t flat = 0;
     };
     std::vector<Sub> subs(1);
@@ -83,6 +86,7 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
             cur->src.push_back(static_cast<const char *>(srcs[i]) + off);
             cur->dst.push_back(static_cast<char *>(dsts[i]) + off);
             cur->bytes.push_back(len);
+            if (ops) cur->ops.push_back((*ops)[i]);
             cur->flat += (len + 255) & ~size_t(255);
             off += len;
         } while (off < bytes[i]);
@@ -102,7 +106,8 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
     auto unpack = [&](size_t j) {
         DDL_HIP(hipStreamWaitEvent(side_, events_[2 + 2 * j], 0));
         dep::wait(side_, events_[2 + 2 * j]);
-        copier.run(1, buf[j % 2], subs[j].dst.data(), subs[j].bytes.data(), (int)subs[j].dst.size(), side_);
+        copier.run(1, buf[j % 2], subs[j].dst.data(), subs[j].bytes.data(), (int)subs[j].dst.size(), side_, dt, divisor,
+                   ops ? subs[j].ops.data() : nullptr);
     };
     for (size_t j = 0; j < J; ++j) {
         Sub &sb = subs[j];

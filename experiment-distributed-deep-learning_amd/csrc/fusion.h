@@ -38,9 +38,13 @@ public:
     // = the whole plan's unpadded bytes (the reference's MPI_Allreduce message)
     using Allreduce = std::function<void(void *buf, size_t elems, size_t message_bytes)>;
     // pack -> allreduce -> unpack of srcs[i] -> dsts[i] (bytes[i] each) on `stream`, pipelined in
-    // sub-plans above `cap` bytes (0: never)
+    // sub-plans above `cap` bytes (0: never). `ops` (one ddl_allreduce_op per segment, or null =
+    // all SUM) with `divisor` = the communicator's size: the unpack of every (sub-)plan holding an
+    // AVG segment is the dividing unpack (pack.hip k_seg_div), which stores the quotients of those
+    // segments; the cuts, the packs and the allreduces do not depend on the ops
     void run(const std::vector<const void *> &srcs, const std::vector<void *> &dsts,
-             const std::vector<size_t> &bytes, int dtype, size_t cap, hipStream_t stream, const Allreduce &ar);
+             const std::vector<size_t> &bytes, int dtype, size_t cap, hipStream_t stream, const Allreduce &ar,
+             const std::vector<int> *ops = nullptr, int divisor = 1);
     size_t subplans() const { return last_subplans_; }  // of the last run
 
     SegmentCopier copier;

@@ -119,7 +119,7 @@ void validate(const Request &r, int size) {
     DDL_REQUIRE(dtype_size(r.dtype) != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported dtype " << r.dtype);
     switch (r.type) {
         case kReqAllreduce:
-            DDL_REQUIRE(r.op == DDL_ALLREDUCE_OP_SUM, DDL_STATUS_INVALID_ARGUMENT, "only SUM is supported");
+            check_allreduce_op(r.op, r.dtype);
             DDL_REQUIRE(r.n == 0 || (r.in && r.out), DDL_STATUS_INVALID_ARGUMENT, "null buffer");
             break;
         case kReqBroadcast:
@@ -463,6 +463,13 @@ void plan_slices(const Plan &p, const std::vector<Request> &reqs, const std::vec
         fn(static_cast<const char *>(r.in) + b * es, static_cast<char *>(r.out) + b * es, (e - b) * es);
     }
 }
+// The op of every slice plan_slices visits, in its order: a request's op is rank-local and applied
+// where its segment is written out; it never enters the group key or the plan cuts.
+std::vector<int> plan_ops(const Plan &p, const std::vector<Request> &reqs, const std::vector<size_t> &group) {
+    std::vector<int> ops;
+    for (size_t q = p.req_begin; q <= p.req_end; ++q) ops.push_back(reqs[group[q]].op);
+    return ops;
+}
 }  // namespace
 
 std::unique_lock<std::mutex> RequestHandler::lock_host_group_(const std::vector<Request> &reqs,
@@ -519,6 +526,8 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
                     segs.push_back(HostSeg{s, d, n});
                     message += n;
                 });
+                const std::vector<int> ops = plan_ops(p, reqs, g.second);
+                for (size_t k = 0; k < segs.size(); ++k) segs[k].op = ops[k];
                 if (data_->size() == 1 && config().one_rank_shortcut.load()) {
                     std::vector<CopyPool::Piece> pieces;
                     for (const HostSeg &sg : segs)
@@ -535,7 +544,7 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
                     const auto t_plan = std::chrono::steady_clock::now();
                     config().host_check_ns.fetch_add(
                         std::chrono::duration_cast<std::chrono::nanoseconds>(t_plan - t_check).count());
-                    host_->run(segs, es, true, coll, true, mapped);
+                    host_->run(segs, es, true, coll, true, mapped, dt, data_->size());
                     config().host_plan_ns.fetch_add(std::chrono::duration_cast<std::chrono::nanoseconds>(
                                                         std::chrono::steady_clock::now() - t_plan)
                                                         .count());
@@ -559,10 +568,12 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
                     dsts.push_back(d);
                     bytes.push_back(n);
                 });
+                const std::vector<int> ops = plan_ops(p, reqs, g.second);  // AVG segments leave as quotients
                 fp_.run(srcs, dsts, bytes, dt, (size_t)config().fusion_pipeline_bytes.load(), stream_,
                         [&](void *buf, size_t elems, size_t message) {
                             data_->allreduce(buf, buf, elems, dt, DDL_ALLREDUCE_OP_SUM, stream_, message);
-                        });
+                        },
+                        &ops, data_->size());
             }
             finish_plan_(p, reqs, g.second, dones, nplans);
         }

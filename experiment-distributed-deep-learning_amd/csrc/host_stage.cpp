@@ -190,7 +190,12 @@ CopyPool &HostStager::pool() {
 }
 
 void HostStager::run(const std::vector<HostSeg> &segs, size_t es, bool upload,
-                     const std::function<void(void *, size_t)> &coll, bool padded, bool device_unpack) {
+                     const std::function<void(void *, size_t)> &coll, bool padded, bool device_unpack, int dtype,
+                     int divisor) {
+    bool avg = false;
+    if (divisor > 1)
+        for (const HostSeg &sg : segs) avg = avg || (sg.op == DDL_ALLREDUCE_OP_AVG && sg.bytes);
+    std::vector<int> ops;  // of the pieces handed to the dividing kernel
     std::vector<size_t> starts;
     const size_t total = seg_starts(segs, padded || device_unpack, starts);
     if (total == 0) return;
@@ -279,6 +284,21 @@ void HostStager::run(const std::vector<HostSeg> &segs, size_t es, bool upload,
                 fail(DDL_STATUS_COMM_ERROR, "test fault: host plan collective of chunk " + std::to_string(i));
             }
             coll(dslot_[k], n / es);
+            if (avg && !device_unpack) {
+                // staged outputs: the AVG slices of this chunk become their quotients in the slot
+                dst.clear();
+                len.clear();
+                for (size_t j = (size_t)(std::upper_bound(starts.begin(), starts.end(), off) - starts.begin()) - 1;
+                     j < segs.size() && starts[j] < off + n; ++j) {
+                    const size_t lo = std::max(off, starts[j]), hi = std::min(off + n, starts[j] + segs[j].bytes);
+                    if (hi <= lo || segs[j].op != DDL_ALLREDUCE_OP_AVG) continue;
+                    dst.push_back(static_cast<char *>(dslot_[k]) + (lo - off));
+                    len.push_back(hi - lo);
+                }
+                ops.assign(dst.size(), DDL_ALLREDUCE_OP_AVG);
+                copier_.run(SegmentCopier::kDivInPlace, nullptr, dst.data(), len.data(), (int)dst.size(), stream_, dtype,
+                            divisor, ops.data());
+            }
             config().host_coll_ns.fetch_add(ns_since(t_coll));
             DDL_HIP(hipEventRecord(hev_[3 * k + 1], stream_));
             DDL_HIP(hipStreamWaitEvent(d2h_, hev_[3 * k + 1], 0));
@@ -289,6 +309,7 @@ void HostStager::run(const std::vector<HostSeg> &segs, size_t es, bool upload,
                 // falls inside a segment's padding)
                 dst.clear();
                 len.clear();
+                ops.clear();
                 size_t flat = 0;
                 for (size_t j = (size_t)(std::upper_bound(starts.begin(), starts.end(), off) - starts.begin()) - 1;
                      j < segs.size() && starts[j] < off + n; ++j) {
@@ -297,9 +318,11 @@ void HostStager::run(const std::vector<HostSeg> &segs, size_t es, bool upload,
                     DDL_REQUIRE(flat == lo - off, DDL_STATUS_ERROR_UNKNOWN, "device-unpack chunk layout");
                     dst.push_back(segs[j].ddst + (lo - starts[j]));  // the device's address of the output
                     len.push_back(hi - lo);
+                    if (avg) ops.push_back(segs[j].op);
                     flat += round256(hi - lo);
                 }
-                copier_.run(1, dslot_[k], dst.data(), len.data(), (int)dst.size(), d2h_);
+                copier_.run(1, dslot_[k], dst.data(), len.data(), (int)dst.size(), d2h_, dtype, divisor,
+                            avg ? ops.data() : nullptr);
             } else {
                 if (i >= (size_t)kHostSlots) wait_unpack(i - kHostSlots);  // download slot k free again
                 const clk::time_point t_post = clk::now();

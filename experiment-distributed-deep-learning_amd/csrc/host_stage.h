@@ -62,6 +62,7 @@ struct HostSeg {
     char *dst;
     size_t bytes;
     char *ddst = nullptr;  // the device's address of dst (device unpack; HostStager::mapped_dsts)
+    int op = 0;            // ddl_allreduce_op of the request (allreduce plans)
 };
 
 // Everything the host path allocates: pinned and device slots, its two copy streams and their
@@ -86,9 +87,13 @@ public:
     // place of the D2H copy and the host unpack; the host never waits for a chunk to come back
     // (measured 43 GB/s each way with the uploads running, vs 32 when the pack kernel also
     // reads the tensors over PCIe: profiles/r02/host/zero_copy_probe.jsonl).
+    // AVG segments (HostSeg::op, with `dtype` and `divisor` = the communicator's size > 1): a
+    // device-unpack plan's kernel stores their quotients into the pinned outputs; a staged plan
+    // divides their slices of a chunk in place in the device slot (the same kernel, on stream_
+    // after the chunk's collective) before the chunk's D2H copy. The chunk cuts do not change.
     void run(const std::vector<HostSeg> &segs, size_t es, bool upload,
              const std::function<void(void *dev, size_t elems)> &coll, bool padded = false,
-             bool device_unpack = false);
+             bool device_unpack = false, int dtype = 0, int divisor = 1);
     // true when every segment's destination range is 16-byte-aligned pinned host memory that the
     // device reaches at the same address, inside one allocation
     // fills every segment's ddst; false unless all of them are mapped

@@ -137,6 +137,113 @@ void launch_tiles(int dir, bool narrow, dim3 g, hipStream_t stream, char *fl, co
     }
 }
 
+// ---- the dividing scatter (DDL_ALLREDUCE_OP_AVG) ------------------------------------------------
+// k_seg_div: k_seg_tiles<1>'s mapping (segment-aligned 1 KiB tiles, the same index, 64 lanes) with
+// the mean's quotient in the store: the elements of a segment flagged kSegAvg (bit 1 of
+// SegDesc::vec; bit 0 stays "16-byte aligned") leave as q(x, P), the others unchanged. The source
+// is the flat buffer (the dividing unpack) or, with flat == nullptr, the segment itself (in place:
+// every lane reads and writes its own bytes only). Element granular throughout: a misaligned
+// tensor and a segment's last partial 16 bytes go element by element (the dtype guarantees element
+// alignment), never byte by byte — a quotient needs whole elements.
+// q: fp32 / fp64 the correctly rounded IEEE quotient by (float)P / (double)P (hipcc's default
+// correctly rounded division; subnormals kept, kernel mode float_denorm_mode_32 = 3); fp16 / bf16
+// widened to fp32, divided, rounded to nearest even into the type — what numpy and torch CPU
+// compute. No reciprocal multiply anywhere: at P = 3, 5, 6, 7 it differs in the last bit for
+// about a third of the values.
+constexpr uint32_t kSegVec = 1, kSegAvg = 2;
+enum DivType : int { kDivF32 = 0, kDivF64 = 1, kDivF16 = 2, kDivBF16 = 3 };
+
+template <int DT> struct DivTraits;
+template <> struct DivTraits<kDivF32> {
+    using T = float;
+    using D = float;
+    static __device__ inline T q(T x, D d) { return x / d; }
+};
+template <> struct DivTraits<kDivF64> {
+    using T = double;
+    using D = double;
+    static __device__ inline T q(T x, D d) { return x / d; }
+};
+template <> struct DivTraits<kDivF16> {
+    using T = _Float16;
+    using D = float;
+    static __device__ inline T q(T x, D d) { return (T)((float)x / d); }
+};
+template <> struct DivTraits<kDivBF16> {
+    using T = uint16_t;  // the bits
+    using D = float;
+    static __device__ inline T q(T x, D d) {
+        const float r = __uint_as_float((uint32_t)x << 16) / d;
+        const uint32_t u = __float_as_uint(r);
+        if ((u & 0x7fffffffu) > 0x7f800000u) return (T)((u >> 16) | 0x40u);  // NaN stays a NaN
+        return (T)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);                 // nearest even
+    }
+};
+
+template <int DT, bool NARROW>
+__global__ void __launch_bounds__(64) k_seg_div(const char *flat, const SegDesc *__restrict__ d,
+                                                const uint32_t *__restrict__ blk_base,
+                                                const void *__restrict__ map, double divisor) {
+    using Tr = DivTraits<DT>;
+    using T = typename Tr::T;
+    constexpr uint32_t kPer = 16 / sizeof(T);
+    union Vec {
+        u32x4 v;
+        T e[kPer];
+    };
+    const unsigned tile = blockIdx.x;
+    const int seg = NARROW ? (int)(blk_base[tile / kIdxBlock] +
+                                   ((static_cast<const uint32_t *>(map)[tile / 4] >> (8 * (tile % 4))) & 0xffu))
+                           : static_cast<const int *>(map)[tile];
+    const SegDesc sd = d[seg];
+    const typename Tr::D dv = (typename Tr::D)divisor;
+    const bool avg = (sd.vec & kSegAvg) != 0;
+    const uint64_t base = (uint64_t)(tile - sd.tile0) * 1024;  // tile start inside the segment
+    char *tp = reinterpret_cast<char *>(sd.ptr);
+    const char *sp = flat ? flat + sd.off : tp;
+    if (!(sd.vec & kSegVec)) {  // misaligned tensor: elements
+        const uint64_t end = sd.len < base + 1024 ? sd.len : base + 1024;
+        for (uint64_t b = base + threadIdx.x * sizeof(T); b + sizeof(T) <= end; b += 64 * sizeof(T)) {
+            const T x = *reinterpret_cast<const T *>(sp + b);
+            *reinterpret_cast<T *>(tp + b) = avg ? Tr::q(x, dv) : x;
+        }
+        return;
+    }
+    const uint64_t b = base + threadIdx.x * 16;
+    if (b + 16 <= sd.len) {
+        Vec x;
+        x.v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(sp + b));
+        if (avg) {
+#pragma unroll
+            for (uint32_t k = 0; k < kPer; ++k) x.e[k] = Tr::q(x.e[k], dv);
+        }
+        __builtin_nontemporal_store(x.v, reinterpret_cast<u32x4 *>(tp + b));
+    } else if (b < sd.len) {  // the segment's last partial 16 bytes: elements
+        for (uint64_t o = b; o + sizeof(T) <= sd.len; o += sizeof(T)) {
+            const T x = *reinterpret_cast<const T *>(sp + o);
+            *reinterpret_cast<T *>(tp + o) = avg ? Tr::q(x, dv) : x;
+        }
+    }
+}
+
+template <int DT>
+void launch_div_dt(bool narrow, dim3 g, hipStream_t stream, const char *fl, const SegDesc *dd, const uint32_t *db,
+                   const void *map, double divisor) {
+    if (narrow) hipLaunchKernelGGL((k_seg_div<DT, true>), g, dim3(64), 0, stream, fl, dd, db, map, divisor);
+    else hipLaunchKernelGGL((k_seg_div<DT, false>), g, dim3(64), 0, stream, fl, dd, db, map, divisor);
+}
+
+void launch_div(int dtype, bool narrow, dim3 g, hipStream_t stream, const char *fl, const SegDesc *dd,
+                const uint32_t *db, const void *map, double divisor) {
+    switch (dtype) {
+        case DDL_FLOAT: launch_div_dt<kDivF32>(narrow, g, stream, fl, dd, db, map, divisor); break;
+        case DDL_DOUBLE: launch_div_dt<kDivF64>(narrow, g, stream, fl, dd, db, map, divisor); break;
+        case DDL_HALF: launch_div_dt<kDivF16>(narrow, g, stream, fl, dd, db, map, divisor); break;
+        case DDL_BFLOAT16: launch_div_dt<kDivBF16>(narrow, g, stream, fl, dd, db, map, divisor); break;
+        default: fail(DDL_STATUS_UNSUPPORTED_DTYPE, std::string("AVG is not defined for ") + dtype_name(dtype));
+    }
+}
+
 }  // namespace
 
 SegmentCopier::~SegmentCopier() {
@@ -182,9 +289,37 @@ size_t SegmentCopier::flat_bytes(const size_t *bytes, int count) {
 }
 
 void SegmentCopier::run(int dir, void *flat, void *const *segs, const size_t *bytes, int count,
-                        hipStream_t stream) {
+                        hipStream_t stream, int dtype, int divisor, const int *ops) {
     if (count <= 0) return;
-    DDL_REQUIRE(flat && segs && bytes, DDL_STATUS_INVALID_ARGUMENT, "null pack arguments");
+    // the quotient only where some segment asks for it and it is not the identity: every other
+    // launch is the plain copy, its kernels and tables exactly as before
+    bool div = false;
+    if (ops && divisor > 1)
+        for (int i = 0; i < count && !div; ++i) div = ops[i] == DDL_ALLREDUCE_OP_AVG && bytes[i] != 0;
+    if (dir == kDivInPlace) {
+        if (!div) return;  // nothing to divide: the segments already hold their results
+        flat = nullptr;
+    } else {
+        DDL_REQUIRE(dir == 0 || dir == 1, DDL_STATUS_INVALID_ARGUMENT, "copier direction " << dir);
+        DDL_REQUIRE(!div || dir == 1, DDL_STATUS_INVALID_ARGUMENT, "the quotient belongs to the unpack");
+    }
+    DDL_REQUIRE((flat || dir == kDivInPlace) && segs && bytes, DDL_STATUS_INVALID_ARGUMENT, "null pack arguments");
+    const size_t es = div ? dtype_size(dtype) : 1;
+    if (div) {
+        DDL_REQUIRE(dtype == DDL_FLOAT || dtype == DDL_DOUBLE || dtype == DDL_HALF || dtype == DDL_BFLOAT16,
+                    DDL_STATUS_UNSUPPORTED_DTYPE, "AVG is not defined for dtype " << dtype);
+        for (int i = 0; i < count; ++i)
+            DDL_REQUIRE(bytes[i] % es == 0 && reinterpret_cast<uintptr_t>(segs[i]) % es == 0, DDL_STATUS_INVALID_ARGUMENT,
+                        "segment " << i << " is not whole, aligned " << dtype_name(dtype) << " elements");
+    }
+    // in place only the AVG segments have tiles (a SUM segment already is its result)
+    std::vector<size_t> own;
+    if (dir == kDivInPlace) {
+        own.assign(bytes, bytes + count);
+        for (int i = 0; i < count; ++i)
+            if (ops[i] != DDL_ALLREDUCE_OP_AVG) own[i] = 0;
+        bytes = own.data();
+    }
     Slot &sl = free_slot_();
     // segment-aligned tiles of kSegTile bytes per workgroup; tile0 = running tile count
     const uint64_t seg_tile = kSegTile;
@@ -210,7 +345,8 @@ void SegmentCopier::run(int dir, void *flat, void *const *segs, const size_t *by
         t[i].ptr = reinterpret_cast<uint64_t>(segs[i]);
         t[i].off = off;
         t[i].len = bytes[i];
-        t[i].vec = (reinterpret_cast<uintptr_t>(segs[i]) & 15u) == 0;
+        t[i].vec = (reinterpret_cast<uintptr_t>(segs[i]) & 15u) == 0 ? kSegVec : 0;
+        if (div && ops[i] == DDL_ALLREDUCE_OP_AVG) t[i].vec |= kSegAvg;
         t[i].tile0 = (uint32_t)tl;
         off += (bytes[i] + 255) & ~uint64_t(255);
         tl += (bytes[i] + seg_tile - 1) / seg_tile;
@@ -242,16 +378,17 @@ void SegmentCopier::run(int dir, void *flat, void *const *segs, const size_t *by
         const dim3 ig((unsigned)((tiles + 255) / 256)), g((unsigned)tiles);
         if (narrow) hipLaunchKernelGGL(k_tile_index<true>, ig, dim3(256), 0, stream, dd, count, (uint64_t)tiles, db, sl.idx);
         else hipLaunchKernelGGL(k_tile_index<false>, ig, dim3(256), 0, stream, dd, count, (uint64_t)tiles, db, sl.idx);
-        launch_tiles(dir, narrow, g, stream, fl, dd, db, sl.idx);
+        if (div) launch_div(dtype, narrow, g, stream, fl, dd, db, sl.idx, (double)divisor);
+        else launch_tiles(dir, narrow, g, stream, fl, dd, db, sl.idx);
     }
     DDL_HIP(hipGetLastError());
     DDL_HIP(hipEventRecord(sl.ready, stream));
     if (dep::on()) {  // happens-before trace (deptrace.h): the segments and the flat buffer
         std::vector<dep::Access> acc;
-        acc.push_back(dir == 0 ? dep::wr(flat, off) : dep::rd(flat, off));
+        if (flat) acc.push_back(dir == 0 ? dep::wr(flat, off) : dep::rd(flat, off));
         for (int i = 0; i < count; ++i)
             if (bytes[i]) acc.push_back(dir == 0 ? dep::rd(segs[i], bytes[i]) : dep::wr(segs[i], bytes[i]));
-        dep::op(stream, dir == 0 ? "pack" : "unpack", std::move(acc));
+        dep::op(stream, dir == 0 ? "pack" : dir == 1 ? (div ? "unpack avg" : "unpack") : "divide", std::move(acc));
     }
 }
 

@@ -262,8 +262,8 @@ void ThreadWorld::run_(hipStream_t user, const std::function<void(int, hipStream
 }
 
 void ThreadWorld::allreduce(const void *const *in, void *const *out, size_t n, int dtype, hipStream_t user,
-                            const RingConfig &cfg) {
-    run_(user, [&](int r, hipStream_t s) { ex_[r]->allreduce(in[r], out[r], n, dtype, s, cfg); });
+                            const RingConfig &cfg, int op) {
+    run_(user, [&](int r, hipStream_t s) { ex_[r]->allreduce(in[r], out[r], n, dtype, s, cfg, op); });
 }
 
 void ThreadWorld::broadcast(void *const *bufs, size_t n, int dtype, int root, hipStream_t user, const RingConfig &cfg) {
@@ -276,16 +276,17 @@ void ThreadWorld::allgatherv(const void *const *sends, void *const *recvs, const
 }
 
 void ThreadWorld::allreduce_batch(const void *const *in, void *const *out, const size_t *n, int count, int dtype,
-                                  hipStream_t user, const RingConfig &cfg) {
+                                  hipStream_t user, const RingConfig &cfg, int op) {
     run_(user, [&](int r, hipStream_t s) {
-        ex_[r]->allreduce_batch(in + (size_t)r * count, out + (size_t)r * count, n, count, dtype, s, cfg);
+        ex_[r]->allreduce_batch(in + (size_t)r * count, out + (size_t)r * count, n, count, dtype, s, cfg, op);
     });
 }
 
 size_t ThreadWorld::fused_allreduce(const void *const *srcs, void *const *dsts, const size_t *bytes, int count,
-                                    int dtype, hipStream_t user, const RingConfig &cfg, size_t cap) {
+                                    int dtype, hipStream_t user, const RingConfig &cfg, size_t cap, const int *ops) {
     while (pipes_.size() < (size_t)P_) pipes_.emplace_back(new FusionPipe);
     const std::vector<size_t> b(bytes, bytes + count);
+    const std::vector<int> o(ops ? ops : nullptr, ops ? ops + count : nullptr);
     run_(user, [&](int r, hipStream_t s) {
         const std::vector<const void *> src(srcs + (size_t)r * count, srcs + (size_t)(r + 1) * count);
         const std::vector<void *> dst(dsts + (size_t)r * count, dsts + (size_t)(r + 1) * count);
@@ -293,7 +294,7 @@ size_t ThreadWorld::fused_allreduce(const void *const *srcs, void *const *dsts, 
             RingConfig c = cfg;
             c.order_bytes = message;
             ex_[r]->allreduce(buf, buf, elems, dtype, s, c);
-        });
+        }, ops ? &o : nullptr, P_);
     });
     return pipes_[0]->subplans();
 }

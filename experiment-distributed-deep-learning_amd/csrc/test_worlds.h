@@ -160,19 +160,20 @@ public:
     long long loopback_pairs() const { return fab_->loopback_pairs; }
     ~ThreadWorld();
     void allreduce(const void *const *in, void *const *out, size_t n, int dtype, hipStream_t user,
-                   const RingConfig &cfg);
+                   const RingConfig &cfg, int op = DDL_ALLREDUCE_OP_SUM);
     // in[r * count + b] / out[r * count + b]: rank r's bucket b (RingExecutor::allreduce_batch)
     void allreduce_batch(const void *const *in, void *const *out, const size_t *n, int count, int dtype,
-                         hipStream_t user, const RingConfig &cfg);
+                         hipStream_t user, const RingConfig &cfg, int op = DDL_ALLREDUCE_OP_SUM);
     void broadcast(void *const *bufs, size_t n, int dtype, int root, hipStream_t user, const RingConfig &cfg);
     void allgatherv(const void *const *sends, void *const *recvs, const size_t *counts, const size_t *displs,
                     int dtype, hipStream_t user);
     // The keyed path's multi-request plan on every rank (FusionPipe::run, what the handler runs:
     // pack -> allreduce -> unpack, sub-plans above `cap` bytes), each sub-plan's allreduce through
     // the rank's RingExecutor with the whole plan's message size. srcs[r * count + i] /
-    // dsts[r * count + i]: rank r's segment i of bytes[i] bytes. Returns the sub-plans per rank.
+    // dsts[r * count + i]: rank r's segment i of bytes[i] bytes; ops[i] (optional) segment i's
+    // ddl_allreduce_op. Returns the sub-plans per rank.
     size_t fused_allreduce(const void *const *srcs, void *const *dsts, const size_t *bytes, int count, int dtype,
-                           hipStream_t user, const RingConfig &cfg, size_t cap);
+                           hipStream_t user, const RingConfig &cfg, size_t cap, const int *ops = nullptr);
 
 private:
     void run_(hipStream_t user, const std::function<void(int, hipStream_t)> &body);

@@ -39,7 +39,7 @@ STATUS_NAMES = {0: 'OK', 1: 'COMM_ERROR', 2: 'ERROR_UNKNOWN', 3: 'INVALID_ARGUME
                 4: 'UNSUPPORTED_DTYPE', 5: 'HIP_ERROR', 6: 'NOT_INITIALIZED', 7: 'DUPLICATE_KEY',
                 8: 'CONFIG_MISMATCH'}
 STATUS_CONFIG_MISMATCH = 8
-OP_SUM = 0
+OP_SUM, OP_AVG = 0, 1  # enum ddl_allreduce_op
 MEMORY_DEVICE, MEMORY_HOST = 0, 1  # enum ddl_memory
 
 DONE_FN = ctypes.CFUNCTYPE(None, ctypes.c_int, ctypes.c_void_p)
@@ -168,10 +168,16 @@ class CPPBackend:
             ctypes.POINTER(sz), ci, ci, vp)
         sig('ddl_pack', ci, vp, ctypes.POINTER(vp), ctypes.POINTER(sz), ci, vp)
         sig('ddl_unpack', ci, ctypes.POINTER(vp), vp, ctypes.POINTER(sz), ci, vp)
+        sig('ddl_unpack_ops', ci, ctypes.POINTER(vp), vp, ctypes.POINTER(sz), ctypes.POINTER(ci), ci, ci, ci, vp)
         sig('ddl_local_ring_allreduce', ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp), sz, ci, ci, vp)
         # RCCL loopback (test / diagnostic: the RCCL transport on one GPU)
         fp, lp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_longlong)
         sig('ddl_testing_thread_allreduce', ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp), sz, ci, vp)
+        sig('ddl_testing_thread_allreduce_op', ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp), sz, ci, ci, vp)
+        sig('ddl_testing_thread_allreduce_batch_op', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp),
+            ctypes.POINTER(sz), ci, ci, vp)
+        sig('ddl_testing_thread_fused_allreduce_ops', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp),
+            ctypes.POINTER(sz), ctypes.POINTER(ci), ci, vp, ctypes.POINTER(sz))
         sig('ddl_testing_thread_broadcast', ci, ci, ci, ctypes.POINTER(vp), sz, ci, vp)
         sig('ddl_testing_thread_allgatherv', ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(sz),
             ctypes.POINTER(sz), ci, vp)

@@ -23,12 +23,20 @@ step() only waits for them. The keys count backwards from the last parameter and
 plans are capped at `bucket_bytes`, so a round's plans run in backward order, each as soon as its
 own gradients are ready (DDP-style buckets). Gradient accumulation over several backward passes:
 run all but the last inside `no_sync()`, as with torch DDP.
+
+`fused_mean=True`: every dense gradient is submitted with the engine's AVG op, so the mean is
+taken on the GPU by the kernel that writes the reduced gradient (for pinned CPU gradients straight
+into them) and no `div_` per gradient runs here. The engine's quotient is the IEEE one — numpy's
+and torch CPU's; torch's `div_` on a device tensor multiplies by the reciprocal instead, so device
+gradients may differ from the default's in the last bit when the size is no power of two. Off by
+default.
 """
 import contextlib
 import functools
 
 import torch
 
+from ddl.torch import cpp_backend as cb
 from ddl.torch.communicator import Communicator
 from ddl.torch.tensor_communicate import allreduce_async, allreduce_async_batch, allreduce_gradient
 
@@ -37,6 +45,7 @@ class DataParallelismDistributedOptimizer:
     """Mixin placed in front of the wrapped optimizer class (the reference's approach)."""
     communicator: Communicator = None
     pin_host_gradients: bool = True
+    fused_mean: bool = False
     _ddl_name = 'DataParallelismDistributedOptimizer'
     _grad_handles = None  # overlap_backward: param -> Handle submitted by its hook
     _syncing = True
@@ -46,6 +55,9 @@ class DataParallelismDistributedOptimizer:
 
     def _comm(self) -> Communicator:
         return self.communicator or Communicator.world()
+
+    def _op(self) -> int:
+        return cb.OP_AVG if self.fused_mean else cb.OP_SUM
 
     def _register_overlap_hooks(self) -> None:
         # keys numbered from the last parameter back: the engine runs a round's plans in key
@@ -68,7 +80,7 @@ class DataParallelismDistributedOptimizer:
                                'earlier backward passes inside no_sync()')
         if self._pinning() and not g.is_cuda and not g.is_pinned():
             p.grad = g = g.pin_memory()
-        self._grad_handles[p] = allreduce_async(g, key, self._comm(), output=g)
+        self._grad_handles[p] = allreduce_async(g, key, self._comm(), output=g, op=self._op())
 
     @contextlib.contextmanager
     def no_sync(self):
@@ -96,8 +108,11 @@ class DataParallelismDistributedOptimizer:
             return
         # gradients already submitted by the backward hooks (overlap_backward)
         hooked = self._drain_hooked()
+        fused = self.fused_mean  # the engine has divided already
         for p, h in hooked.items():
-            h.wait().div_(comm.size)
+            out = h.wait()
+            if not fused:
+                out.div_(comm.size)
         pin = self._pinning()
         params, grads, keys, sparse = [], [], [], []
         for gi, group in enumerate(self.param_groups):
@@ -114,15 +129,16 @@ class DataParallelismDistributedOptimizer:
                 keys.append(self._key(gi, pi))
         # one keyed request per gradient (the reference builds one Allreduce op per grad,
         # distributed_optimizer.py:50-63), registered as one batch, reduced in place
-        handles = zip(params, allreduce_async_batch(grads, keys, comm, outputs=grads))
+        handles = zip(params, allreduce_async_batch(grads, keys, comm, outputs=grads, op=self._op()))
         for p, h in handles:
             out = h.wait()
-            out.div_(comm.size)
+            if not fused:
+                out.div_(comm.size)
             if out.data_ptr() != p.grad.data_ptr():
                 p.grad.copy_(out)
         # sparse gradients: every rank's rows gathered, values averaged (same order on all ranks)
         for p in sparse:
-            p.grad = allreduce_gradient(p.grad, comm)
+            p.grad = allreduce_gradient(p.grad, comm)  # (sparse: the allgather branch, fused_mean or not)
 
     def zero_grad(self, set_to_none: bool = True) -> None:
         # pinned host gradients survive zero_grad (zeroed in place), so the next backward
@@ -155,7 +171,8 @@ def data_parallelism_distributed_optimizer_wrapper(
         communicator: Communicator = None,
         pin_host_gradients: bool = True,
         overlap_backward: bool = False,
-        bucket_bytes: int = 32 << 20) -> torch.optim.Optimizer:
+        bucket_bytes: int = 32 << 20,
+        fused_mean: bool = False) -> torch.optim.Optimizer:
     """Return an optimizer of a subclass of `type(optimizer)` whose step() first averages the
     gradients across `communicator` (default: the world). Parameter groups and state are
     shared with `optimizer`. `pin_host_gradients`: keep CPU gradients in pinned memory;
@@ -163,7 +180,8 @@ def data_parallelism_distributed_optimizer_wrapper(
     docstring) and cap the engine's fusion plans at `bucket_bytes` (the engine-wide
     `fusion_threshold_bytes`, so every rank must build the wrapper the same way; None keeps the
     configured cap): a round's gradients then reduce as several plans in backward order, each
-    starting once its own gradients exist."""
+    starting once its own gradients exist. `fused_mean`: the engine's AVG op takes the mean of the
+    dense gradients in place of a `div_` per gradient (module docstring)."""
     opt_cls = optimizer.__class__
     assert issubclass(opt_cls, torch.optim.Optimizer)
     cls = type(opt_cls.__name__, (DataParallelismDistributedOptimizer, opt_cls), {})
@@ -171,6 +189,7 @@ def data_parallelism_distributed_optimizer_wrapper(
     res.__dict__.update(optimizer.__dict__)
     res.communicator = communicator
     res.pin_host_gradients = pin_host_gradients
+    res.fused_mean = bool(fused_mean)
     if overlap_backward:
         if bucket_bytes:
             from ddl.torch import config

@@ -2,7 +2,9 @@
 
 `allreduce(tensor, communicator)` returns a new tensor holding the elementwise SUM over the
 communicator's ranks — as the reference's `Allreduce` op does (AllreduceOp.cc:32-66, output
-allocated like the input). `allreduce_gradient` divides by the size. `allreduce_async` is the
+allocated like the input). `allreduce_gradient` divides by the size; every allreduce also takes
+`op=cb.OP_AVG` for the mean, which the engine divides on the GPU in the kernel that writes the
+result (the IEEE quotient, as numpy and torch CPU compute it). `allreduce_async` is the
 keyed request path (the TF op's asynchronous `handleRequest`): requests registered under
 a key are negotiated across ranks, fused by dtype in key order and completed through a
 callback.
@@ -31,40 +33,42 @@ def _comm(communicator):
     return Communicator.world() if communicator is None else communicator
 
 
-def _allreduce_device(src: torch.Tensor, dst: torch.Tensor, communicator: Communicator) -> None:
+def _allreduce_device(src: torch.Tensor, dst: torch.Tensor, communicator: Communicator,
+                      op: int = cb.OP_SUM) -> None:
     require_device_tensor(src, 'allreduce input')
     require_device_tensor(dst, 'allreduce output')
     check(CPPBackend.c_api().ddl_allreduce(
-        communicator.id, src.data_ptr(), dst.data_ptr(), src.numel(), ddl_dtype(src), cb.OP_SUM,
+        communicator.id, src.data_ptr(), dst.data_ptr(), src.numel(), ddl_dtype(src), int(op),
         current_stream_handle(src.device)), 'ddl_allreduce')
 
 
-def allreduce(tensor: torch.Tensor, communicator: Communicator = None) -> torch.Tensor:
-    """Sum `tensor` over all ranks of `communicator`; returns a new tensor."""
+def allreduce(tensor: torch.Tensor, communicator: Communicator = None, op: int = cb.OP_SUM) -> torch.Tensor:
+    """Sum of `tensor` over all ranks of `communicator` (`op=cb.OP_AVG`: the mean, divided by the
+    engine on the GPU); returns a new tensor."""
     communicator = _comm(communicator)
     if tensor.is_cuda:
         src = tensor.contiguous()
         out = torch.empty_like(src)
-        _allreduce_device(src, out, communicator)
+        _allreduce_device(src, out, communicator, op)
         return out.view_as(tensor)
     # host-resident bucket: the engine's chunked H2D -> device ring -> D2H pipeline
     src = tensor.contiguous()
     out = torch.empty(tensor.shape, dtype=tensor.dtype, pin_memory=True)
     check(CPPBackend.c_api().ddl_allreduce_host(
-        communicator.id, src.data_ptr(), out.data_ptr(), src.numel(), ddl_dtype(src), cb.OP_SUM),
+        communicator.id, src.data_ptr(), out.data_ptr(), src.numel(), ddl_dtype(src), int(op)),
         'ddl_allreduce_host')
     return out
 
 
-def allreduce_(tensor: torch.Tensor, communicator: Communicator = None) -> torch.Tensor:
+def allreduce_(tensor: torch.Tensor, communicator: Communicator = None, op: int = cb.OP_SUM) -> torch.Tensor:
     """In-place variant of `allreduce` (device tensors only)."""
     communicator = _comm(communicator)
-    _allreduce_device(tensor, tensor, communicator)
+    _allreduce_device(tensor, tensor, communicator, op)
     return tensor
 
 
-def allreduce_batch_(tensors, communicator: Communicator = None):
-    """In-place SUM of every device tensor in `tensors` (one dtype) over the ranks, as ONE grouped
+def allreduce_batch_(tensors, communicator: Communicator = None, op: int = cb.OP_SUM):
+    """In-place SUM (`op=cb.OP_AVG`: mean) of every device tensor in `tensors` (one dtype) over the ranks, as ONE grouped
     collective (ddl_allreduce_batch): a DDP-style bucket list reduced with one RCCL group per tick
     and the folds of up to 8 buckets per kernel launch. With reference_order 1 (the default) each
     result is bit for bit what `allreduce_` gives that tensor alone (MPICH's order for its own
@@ -82,14 +86,17 @@ def allreduce_batch_(tensors, communicator: Communicator = None):
     k = len(tensors)
     ptrs = (ctypes.c_void_p * k)(*[t.data_ptr() for t in tensors])
     counts = (ctypes.c_size_t * k)(*[t.numel() for t in tensors])
-    check(CPPBackend.c_api().ddl_allreduce_batch(communicator.id, k, ptrs, ptrs, counts, dt, cb.OP_SUM,
+    check(CPPBackend.c_api().ddl_allreduce_batch(communicator.id, k, ptrs, ptrs, counts, dt, int(op),
                                                   current_stream_handle(tensors[0].device)), 'ddl_allreduce_batch')
     return tensors
 
 
 def allreduce_gradient(tensor: torch.Tensor, communicator: Communicator = None,
-                       return_mean: bool = True) -> torch.Tensor:
-    """Dense gradient: allreduce, then divide by the size (tensor_communicate.py:21-25).
+                       return_mean: bool = True, fused_mean: bool = False) -> torch.Tensor:
+    """Dense gradient: allreduce, then divide by the size (tensor_communicate.py:21-25). With
+    `fused_mean` the engine takes the mean itself (`op=cb.OP_AVG`: the IEEE quotient, in the kernel
+    that writes the result) and no `div_` runs here; on a device tensor the last bit may then
+    differ from torch's `div_`, which multiplies by the reciprocal, when the size is no power of two.
 
     Sparse gradient (torch sparse COO, the counterpart of TF's IndexedSlices, :26-30): the
     values and the indices are allgathered — every rank's rows in rank order — and the mean
@@ -102,6 +109,8 @@ def allreduce_gradient(tensor: torch.Tensor, communicator: Communicator = None,
             values = values / communicator.size
         indices = allgather(tensor._indices().t().contiguous(), communicator).t()
         return torch.sparse_coo_tensor(indices, values, tensor.shape)
+    if return_mean and fused_mean:
+        return allreduce(tensor, communicator, op=cb.OP_AVG)
     summed = allreduce(tensor, communicator)
     if return_mean:
         summed.div_(communicator.size)
@@ -397,8 +406,8 @@ def _same_memory(a: torch.Tensor, b: torch.Tensor, what: str) -> int:
 
 
 def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator = None,
-                    output: torch.Tensor = None) -> Handle:
-    """Register a keyed allreduce; returns a Handle.
+                    output: torch.Tensor = None, op: int = cb.OP_SUM) -> Handle:
+    """Register a keyed allreduce (`op`: cb.OP_SUM, or cb.OP_AVG for the mean); returns a Handle.
 
     `name` plays the role of the TF op name: the same name on every rank identifies the same
     gradient, and only one request per name may be pending (TensorCommunicateRequest.h:21).
@@ -415,7 +424,7 @@ def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator 
     group = _Completion(1, (tensor, out))
     h = _NativeHandle(name, out, None, group, 0)  # the group holds the tensors
     st = CPPBackend.c_api().ddl_allreduce_submit_mem(
-        communicator.id, key, tensor.data_ptr(), out.data_ptr(), tensor.numel(), dt, cb.OP_SUM, mem, stream,
+        communicator.id, key, tensor.data_ptr(), out.data_ptr(), tensor.numel(), dt, int(op), mem, stream,
         _native_done(), group.slots()[0])
     if st != cb.STATUS_OK:
         group.fail([0], st)
@@ -423,9 +432,9 @@ def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator 
     return h
 
 
-def allreduce_async_batch(tensors, names, communicator: Communicator = None, outputs=None):
-    """Register several keyed allreduces at once (one engine wake-up, one input-ready event);
-    returns one Handle per tensor. Same key rules as `allreduce_async`; device and host tensors
+def allreduce_async_batch(tensors, names, communicator: Communicator = None, outputs=None, op: int = cb.OP_SUM):
+    """Register several keyed allreduces at once (one engine wake-up, one input-ready event), all
+    with `op` (cb.OP_SUM, or cb.OP_AVG for the mean); returns one Handle per tensor. Same key rules as `allreduce_async`; device and host tensors
     may be mixed (one submission per memory kind)."""
     import ctypes
     communicator = _comm(communicator)
@@ -466,7 +475,7 @@ def allreduce_async_batch(tensors, names, communicator: Communicator = None, out
             outs = ins if in_place else (ctypes.c_void_p * m)(*[o.data_ptr() for o in os_])
             st = CPPBackend.c_api().ddl_allreduce_submit_batch_mem(
                 communicator.id, m, (ctypes.c_char_p * m)(*ks), ins, outs,
-                (ctypes.c_size_t * m)(*[t.numel() for t in ts]), (ctypes.c_int * m)(*ds), cb.OP_SUM, mem,
+                (ctypes.c_size_t * m)(*[t.numel() for t in ts]), (ctypes.c_int * m)(*ds), int(op), mem,
                 stream_handle_for(tensors[idx[0]]), done, users)
         except BaseException:
             group.fail(rest, _STATUS_ERROR_UNKNOWN)  # not submitted: no slot may stay pending

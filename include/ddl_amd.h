@@ -75,8 +75,10 @@ enum ddl_status {
  * device and back; device requests stay in HBM. */
 enum ddl_memory { DDL_MEMORY_DEVICE = 0, DDL_MEMORY_HOST = 1 };
 
-/* Communicator::AllreduceOperation (reference Communicator.h:22-24): SUM only. */
-enum ddl_allreduce_op { DDL_ALLREDUCE_OP_SUM = 0 };
+/* Communicator::AllreduceOperation (reference Communicator.h:22-24 has SUM only). AVG (MI355X
+ * extension) is the SUM result divided by the communicator's size, the quotient taken on the GPU
+ * by the kernel that writes the result (see the data-plane section). */
+enum ddl_allreduce_op { DDL_ALLREDUCE_OP_SUM = 0, DDL_ALLREDUCE_OP_AVG = 1 };
 
 typedef long long ddl_communicator_id;
 
@@ -205,6 +207,23 @@ void py_debug(const char *log_str);
 void py_error(const char *log_str);
 
 /* ---- data plane ---------------------------------------------------------------------- */
+/* The `op` of every allreduce entry point below: DDL_ALLREDUCE_OP_SUM, or DDL_ALLREDUCE_OP_AVG =
+ * the SUM result (the same schedules and summation order, already rounded to the dtype) divided
+ * by the communicator's size P — what the reference's allreduce_gradient computes with
+ * `summed / communicator.size`. The quotient is the correctly rounded IEEE one by (float)P for
+ * fp32 and (double)P for fp64; fp16 / bf16 are widened to fp32, divided and rounded to nearest
+ * even into the type (numpy's and torch CPU's results, bit for bit). Subnormals are kept, signed
+ * zeros and infinities follow IEEE, a NaN stays a NaN. The division is part of the last device
+ * write of the result: the fused plans' unpack kernel stores the quotients (also straight into
+ * pinned host outputs), every other path divides the result in place with one launch of the same
+ * kernel on the caller's stream — no host pass, no launch per tensor. At P = 1 AVG is SUM. AVG on
+ * an integer dtype returns DDL_STATUS_UNSUPPORTED_DTYPE and any other op value
+ * DDL_STATUS_INVALID_ARGUMENT, from every entry point, before anything is posted. AVG direct
+ * collectives (ddl_allreduce, ddl_allreduce_batch) are refused inside a hipGraph capture.
+ * The op never influences what is communicated: it is a per-request, rank-local property like the
+ * output pointer (fusion groups, plans and schedules do not depend on it, and one round, plan or
+ * unpack launch may mix SUM and AVG requests). Ranks that disagree about a key's op therefore get
+ * different numbers, never a hang. */
 /* recv = SUM over ranks of send (elementwise), bit for bit the reference's MPI_Allreduce (MPICH
  * 3.3.2's order) with reference_order 1. The schedule is the tuned one for the bucket's size
  * class: by default at P > 2 the direct reduce-scatter (slices of every chunk to every peer over

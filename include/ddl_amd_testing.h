@@ -116,6 +116,12 @@ int ddl_reduce_fold_batch(int count, void *const *outs, const void *const *as, c
 int ddl_pack(void *dst, const void *const *srcs, const size_t *bytes, int count, void *hip_stream);
 int ddl_unpack(void *const *dsts, const void *src, const size_t *bytes, int count,
                void *hip_stream);
+/* The dividing unpack (DDL_ALLREDUCE_OP_AVG's kernel, csrc/pack.hip k_seg_div): as ddl_unpack, but
+ * the elements (of `dtype`, a float type) of every segment with ops[i] == DDL_ALLREDUCE_OP_AVG are
+ * stored as their quotient by `divisor`; the other segments are copied. src == NULL: in place —
+ * every AVG segment is divided where it is, the others are not touched. */
+int ddl_unpack_ops(void *const *dsts, const void *src, const size_t *bytes, const int *ops, int count, int dtype,
+                   int divisor, void *hip_stream);
 
 /* ---- single-GPU rehearsal of the ring schedule --------------------------------------- */
 /* Runs the exact per-rank ring schedule for `nranks` virtual ranks inside this process on
@@ -132,6 +138,12 @@ int ddl_local_allreduce_batch(int nranks, int count, const void *const *sends, v
                               const size_t *elements, int dtype, void *hip_stream);
 int ddl_testing_thread_allreduce_batch(int nranks, int count, const void *const *sends, void *const *recvs,
                                        const size_t *elements, int dtype, void *hip_stream);
+/* ddl_testing_thread_allreduce / _batch with the op (ddl_allreduce_op) handed to every rank's
+ * RingExecutor, as ddl_allreduce / ddl_allreduce_batch hand it over. */
+int ddl_testing_thread_allreduce_op(int nranks, const void *const *sends, void *const *recvs, size_t elements,
+                                    int dtype, int op, void *hip_stream);
+int ddl_testing_thread_allreduce_batch_op(int nranks, int count, const void *const *sends, void *const *recvs,
+                                          const size_t *elements, int dtype, int op, void *hip_stream);
 
 /* Broadcast / allgatherv of P virtual ranks on one GPU (as ddl_local_ring_allreduce). */
 int ddl_local_broadcast(int nranks, int root, void *const *bufs, size_t elements, int dtype, void *hip_stream);
@@ -158,6 +170,11 @@ int ddl_testing_thread_allgatherv(int nranks, const void *const *sends, void *co
  * bytes[i] bytes (whole elements of dtype); *subplans (may be NULL) = the sub-plans per rank. */
 int ddl_testing_thread_fused_allreduce(int nranks, int count, const void *const *srcs, void *const *dsts,
                                        const size_t *bytes, int dtype, void *hip_stream, size_t *subplans);
+/* The same with ops[i] = segment i's ddl_allreduce_op, as the keyed handler passes the requests'
+ * ops to FusionPipe::run (AVG segments are divided by nranks in the unpack of their sub-plans). */
+int ddl_testing_thread_fused_allreduce_ops(int nranks, int count, const void *const *srcs, void *const *dsts,
+                                           const size_t *bytes, const int *ops, int dtype, void *hip_stream,
+                                           size_t *subplans);
 /* Data movement of the thread worlds made from now on: rccl = 0 device copies (default); 1 every
  * matched send / receive pair goes through RcclTransport::group as a self send + self receive on
  * the RCCL loopback communicator (ddl_rccl_loopback_init first), posted on the receiver's stream
