@@ -36,6 +36,9 @@ def parse():
     p.add_argument('--samples', default=60000, type=int, help='synthetic training samples (all ranks)')
     p.add_argument('--fused-mean', action='store_true',
                    help='let the engine average the gradients (DDL_ALLREDUCE_OP_AVG) instead of a div_ per gradient')
+    p.add_argument('--compression', default='none', choices=['none', 'fp16', 'bf16'],
+                   help='send the fp32 device gradients as 16-bit values (Compression.fp16 / .bf16; bf16 for unscaled '
+                        'gradients)')
     return p.parse_args()
 
 
@@ -65,6 +68,7 @@ def get_processing_data(data, communicator):
 
 def main():
     args = parse()
+    from ddl.torch import Compression
     from ddl.torch.communicator import Communicator
     from ddl.torch.parallelism.data import (InitialParametersBroadcast, LearningRateWarmup, MetricAverage,
                                             data_parallelism_distributed_optimizer_wrapper)
@@ -77,7 +81,8 @@ def main():
     # scale the lr by the number of replicas; the warm-up ramps to it from slightly above base_lr
     scaled_lr = world.size * args.lr
     optimizer = data_parallelism_distributed_optimizer_wrapper(torch.optim.Adam(model.parameters(), lr=scaled_lr),
-                                                               world, fused_mean=args.fused_mean)
+                                                               world, fused_mean=args.fused_mean,
+                                                               compression=getattr(Compression, args.compression))
     if world.size > 1:
         InitialParametersBroadcast(model, 0, optimizer, communicator=world).broadcast()
     steps = max(1, len(x_train) // args.batch_size)

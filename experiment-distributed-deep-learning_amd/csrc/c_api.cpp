@@ -330,10 +330,10 @@ int ddl_allreduce_submit_mem(ddl_communicator_id id, const char *key, const void
         r.out = out;
         r.n = elements;
         r.dtype = dtype;
-        r.op = op;
+        r.host = memory == DDL_MEMORY_HOST;
+        r.wire = decode_keyed_op(op, dtype, r.host, &r.op);  // refusals before anything is posted
         r.done = done;
         r.user = user;
-        r.host = memory == DDL_MEMORY_HOST;
         r.ready = ready_event(memory, hip_stream);
         c->handler().submit(r);
     });
@@ -411,7 +411,8 @@ int ddl_allreduce_submit_batch_mem(ddl_communicator_id id, int count, const char
         if (count == 0) return;
         auto c = Registry::get().find(id);
         DeviceGuard g(c->device());
-        auto ready = ready_event(memory, hip_stream);
+        // one op for the batch: with a wire flag every entry must be fp32 (all-or-nothing, decided
+        // before the ready event is recorded)
         std::vector<Request> rs(count);
         for (int i = 0; i < count; ++i) {
             DDL_REQUIRE(keys[i], DDL_STATUS_INVALID_ARGUMENT, "null key " << i);
@@ -420,12 +421,13 @@ int ddl_allreduce_submit_batch_mem(ddl_communicator_id id, int count, const char
             rs[i].out = outs[i];
             rs[i].n = elements[i];
             rs[i].dtype = dtypes[i];
-            rs[i].op = op;
+            rs[i].host = memory == DDL_MEMORY_HOST;
+            rs[i].wire = decode_keyed_op(op, dtypes[i], rs[i].host, &rs[i].op);
             rs[i].done = done;
             rs[i].user = users ? users[i] : nullptr;
-            rs[i].host = memory == DDL_MEMORY_HOST;
-            rs[i].ready = ready;
         }
+        auto ready = ready_event(memory, hip_stream);
+        for (Request &r : rs) r.ready = ready;
         c->handler().submit_batch(rs);
     });
 }

@@ -154,6 +154,14 @@ struct RegisterFinalize {
     RegisterFinalize() { add_finalize_hook(&testing_finalize); }
 } g_register_finalize;
 
+// wire-side byte lengths of `elements` fp32 values sent as wire_dtype (ddl_pack_cvt, ...)
+std::vector<size_t> wire_bytes(const size_t *elements, int count, int wire_dtype) {
+    DDL_REQUIRE(wire_dtype == DDL_HALF || wire_dtype == DDL_BFLOAT16, DDL_STATUS_UNSUPPORTED_DTYPE,
+                "wire dtype " << wire_dtype << " is neither float16 nor bfloat16");
+    std::vector<size_t> b(count);
+    for (int i = 0; i < count; ++i) b[i] = elements[i] * dtype_size(wire_dtype);
+    return b;
+}
 }  // namespace
 
 extern "C" {
@@ -392,6 +400,31 @@ int ddl_unpack_ops(void *const *dsts, const void *src, const size_t *bytes, cons
     });
 }
 
+int ddl_pack_cvt(void *dst, const void *const *srcs, const size_t *elements, int count, int wire_dtype,
+                 void *hip_stream) {
+    return guarded([&] {
+        DDL_REQUIRE(count >= 0 && (count == 0 || (dst && srcs && elements)), DDL_STATUS_INVALID_ARGUMENT,
+                    "bad pack_cvt args");
+        const std::vector<size_t> b = wire_bytes(elements, count, wire_dtype);
+        std::lock_guard<std::mutex> g(abi_copier_mu());
+        abi_copier().run_cvt(0, dst, const_cast<void *const *>(srcs), b.data(), count, as_stream(hip_stream), DDL_FLOAT,
+                             wire_dtype);
+    });
+}
+
+int ddl_unpack_cvt(void *const *dsts, const void *src, const size_t *elements, const int *ops, int count,
+                   int wire_dtype, int divisor, void *hip_stream) {
+    return guarded([&] {
+        DDL_REQUIRE(count >= 0 && (count == 0 || (src && dsts && elements)) && divisor >= 1, DDL_STATUS_INVALID_ARGUMENT,
+                    "bad unpack_cvt args");
+        for (int i = 0; ops && i < count; ++i) check_allreduce_op(ops[i], DDL_FLOAT);
+        const std::vector<size_t> b = wire_bytes(elements, count, wire_dtype);
+        std::lock_guard<std::mutex> g(abi_copier_mu());
+        abi_copier().run_cvt(1, const_cast<void *>(src), dsts, b.data(), count, as_stream(hip_stream), DDL_FLOAT,
+                             wire_dtype, divisor, ops);
+    });
+}
+
 int ddl_local_ring_allreduce(int nranks, const void *const *sends, void *const *recvs, size_t elements,
                              int dtype, int op, void *hip_stream) {
     return guarded([&] {
@@ -509,6 +542,22 @@ int ddl_testing_thread_fused_allreduce_ops(int nranks, int count, const void *co
         const size_t j = thread_world(nranks).fused_allreduce(srcs, dsts, bytes, count, dtype, as_stream(hip_stream),
                                                               config().ring(),
                                                               (size_t)config().fusion_pipeline_bytes.load(), ops);
+        if (subplans) *subplans = j;
+    });
+}
+
+int ddl_testing_thread_fused_allreduce_wire(int nranks, int count, const void *const *srcs, void *const *dsts,
+                                            const size_t *elements, const int *ops, int wire_dtype,
+                                            void *hip_stream, size_t *subplans) {
+    return guarded([&] {
+        DDL_REQUIRE(nranks >= 1 && nranks <= 64 && count >= 1 && srcs && dsts && elements, DDL_STATUS_INVALID_ARGUMENT,
+                    "bad thread fused allreduce");
+        for (int i = 0; ops && i < count; ++i) check_allreduce_op(ops[i], DDL_FLOAT);
+        const std::vector<size_t> b = wire_bytes(elements, count, wire_dtype);
+        const size_t j = thread_world(nranks).fused_allreduce(srcs, dsts, b.data(), count, wire_dtype,
+                                                              as_stream(hip_stream), config().ring(),
+                                                              (size_t)config().fusion_pipeline_bytes.load(), ops,
+                                                              DDL_FLOAT);
         if (subplans) *subplans = j;
     });
 }

@@ -86,6 +86,23 @@ inline void check_allreduce_op(int op, int dtype) {
                 DDL_STATUS_UNSUPPORTED_DTYPE, "AVG is not defined for " << dtype_name(dtype));
 }
 
+// The `op` of a keyed allreduce request: SUM / AVG in the low bits, optionally one
+// ddl_allreduce_wire flag. Returns the wire dtype (DDL_HALF / DDL_BFLOAT16; 0 = uncompressed) and
+// leaves SUM / AVG in *base. Refusals as ddl_amd.h lists them, before anything is registered.
+inline int decode_keyed_op(int op, int dtype, bool host, int *base) {
+    constexpr int kWire = DDL_ALLREDUCE_WIRE_FP16 | DDL_ALLREDUCE_WIRE_BF16;
+    *base = op & ~kWire;
+    const int w = op & kWire;
+    DDL_REQUIRE(w != kWire, DDL_STATUS_INVALID_ARGUMENT, "both wire flags in allreduce op " << op);
+    DDL_REQUIRE(*base == DDL_ALLREDUCE_OP_SUM || *base == DDL_ALLREDUCE_OP_AVG, DDL_STATUS_INVALID_ARGUMENT,
+                "unknown allreduce op " << op << " (SUM = 0, AVG = 1, | WIRE_FP16 = 0x100 or WIRE_BF16 = 0x200)");
+    if (!w) return 0;
+    DDL_REQUIRE(!host, DDL_STATUS_INVALID_ARGUMENT, "wire compression is for device requests only");
+    DDL_REQUIRE(dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
+                "wire compression is defined for float32 only, not " << dtype_name(dtype));
+    return w == DDL_ALLREDUCE_WIRE_FP16 ? DDL_HALF : DDL_BFLOAT16;
+}
+
 // Logging (the reference logs per rank to log-<rank>.txt, GlobalLog.cc:17-49; here
 // stderr, gated by the "log_level" config: 0 errors, 1 info, 2 debug).
 int log_level();
@@ -227,9 +244,19 @@ public:
     static constexpr int kDivInPlace = 2;
     void run(int dir, void *flat, void *const *segs, const size_t *bytes, int count, hipStream_t stream,
              int dtype = 0, int divisor = 1, const int *ops = nullptr);
+    // The converting copies of the wire compression (ddl_allreduce_wire): the tensors hold `src_dtype`
+    // (DDL_FLOAT) elements, the flat buffer `wire_dtype` (DDL_HALF / DDL_BFLOAT16) ones. `wire_bytes[i]`
+    // = segment i's bytes on the FLAT side (elements x 2), so offsets, tiles and flat_bytes are those
+    // of run() on the wire stream; the tensor side is twice as long. dir 0: round to nearest even
+    // into the flat buffer (k_seg_cvt_pack); dir 1: widen, AVG segments divided by (float)divisor
+    // (k_seg_cvt_unpack).
+    void run_cvt(int dir, void *flat, void *const *segs, const size_t *wire_bytes, int count, hipStream_t stream,
+                 int src_dtype, int wire_dtype, int divisor = 1, const int *ops = nullptr);
     static size_t flat_bytes(const size_t *bytes, int count);
 
 private:
+    void run_(int dir, void *flat, void *const *segs, const size_t *bytes, int count, hipStream_t stream, int dtype,
+              int divisor, const int *ops, int wire);
     struct Slot {
         void *host = nullptr, *dev = nullptr;
         size_t cap = 0;

@@ -41,9 +41,18 @@ hipEvent_t FusionPipe::event_(size_t i) {
 
 void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<void *> &dsts,
                      const std::vector<size_t> &bytes, int dt, size_t cap, hipStream_t stream, const Allreduce &ar,
-                     const std::vector<int> *ops, int divisor) {
+                     const std::vector<int> *ops, int divisor, int src_dt) {
     const size_t es = dtype_size(dt);
     DDL_REQUIRE(es != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported dtype " << dt);
+    const bool cvt = src_dt != 0 && src_dt != dt;
+    const size_t ses = cvt ? dtype_size(src_dt) : es;  // the tensors' element size
+    DDL_REQUIRE(ses != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported source dtype " << src_dt);
+    // gather (dir 0) / scatter (dir 1) of one (sub-)plan: the converting kernels with a wire dtype
+    auto copy = [&](int dir, void *fb, void *const *segs, const size_t *b, int n, hipStream_t s, const int *o) {
+        if (cvt) copier.run_cvt(dir, fb, segs, b, n, s, src_dt, dt, divisor, o);
+        else if (dir == 0) copier.run(0, fb, segs, b, n, s);
+        else copier.run(1, fb, segs, b, n, s, dt, divisor, o);
+    };
     DDL_REQUIRE(!ops || ops->size() == bytes.size(), DDL_STATUS_INVALID_ARGUMENT, "fusion plan: one op per segment");
     DDL_REQUIRE(srcs.size() == bytes.size() && dsts.size() == bytes.size(), DDL_STATUS_INVALID_ARGUMENT,
                 "fusion plan: " << srcs.size() << " sources, " << dsts.size() << " destinations, " << bytes.size()
@@ -57,10 +66,10 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
     if (cap == 0 || total <= cap) {
         last_subplans_ = 1;
         void *fb = ensure(0, total, stream);
-        copier.run(0, fb, const_cast<void *const *>(reinterpret_cast<const void *const *>(srcs.data())), bytes.data(),
-                   (int)srcs.size(), stream);
+        copy(0, fb, const_cast<void *const *>(reinterpret_cast<const void *const *>(srcs.data())), bytes.data(),
+             (int)srcs.size(), stream, nullptr);
         ar(fb, total / es, message);
-        copier.run(1, fb, dsts.data(), bytes.data(), (int)dsts.size(), stream, dt, divisor, ops ? ops->data() : nullptr);
+        copy(1, fb, dsts.data(), bytes.data(), (int)dsts.size(), stream, ops ? ops->data() : nullptr);
         return;
     }
     struct Sub {
@@ -83,8 +92,8 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
             // the element size) from the segment start
             const size_t room = cap - cur->flat, left = bytes[i] - off;
             const size_t len = left <= room ? left : room;
-            cur->src.push_back(static_cast<const char *>(srcs[i]) + off);
-            cur->dst.push_back(static_cast<char *>(dsts[i]) + off);
+            cur->src.push_back(static_cast<const char *>(srcs[i]) + off / es * ses);
+            cur->dst.push_back(static_cast<char *>(dsts[i]) + off / es * ses);
             cur->bytes.push_back(len);
             if (ops) cur->ops.push_back((*ops)[i]);
             cur->flat += (len + 255) & ~size_t(255);
@@ -106,13 +115,13 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
     auto unpack = [&](size_t j) {
         DDL_HIP(hipStreamWaitEvent(side_, events_[2 + 2 * j], 0));
         dep::wait(side_, events_[2 + 2 * j]);
-        copier.run(1, buf[j % 2], subs[j].dst.data(), subs[j].bytes.data(), (int)subs[j].dst.size(), side_, dt, divisor,
-                   ops ? subs[j].ops.data() : nullptr);
+        copy(1, buf[j % 2], subs[j].dst.data(), subs[j].bytes.data(), (int)subs[j].dst.size(), side_,
+             ops ? subs[j].ops.data() : nullptr);
     };
     for (size_t j = 0; j < J; ++j) {
         Sub &sb = subs[j];
-        copier.run(0, buf[j % 2], const_cast<void *const *>(reinterpret_cast<const void *const *>(sb.src.data())),
-                   sb.bytes.data(), (int)sb.src.size(), side_);
+        copy(0, buf[j % 2], const_cast<void *const *>(reinterpret_cast<const void *const *>(sb.src.data())),
+             sb.bytes.data(), (int)sb.src.size(), side_, nullptr);
         DDL_HIP(hipEventRecord(events_[1 + 2 * j], side_));
         dep::record(events_[1 + 2 * j], side_);
         DDL_HIP(hipStreamWaitEvent(stream, events_[1 + 2 * j], 0));

@@ -11,6 +11,9 @@
 // pack j+2, issued on `side` after unpack j. Each sub-plan is an allreduce of its own; it is told
 // the whole plan's message size, so with reference_order every sub-plan folds in the order MPICH
 // uses for the whole plan and the cut changes no bit.
+// A compressed plan (fp32 tensors over an fp16 / bf16 wire, ddl_allreduce_wire) is the same
+// pipeline over the wire stream: the converting pack / unpack kernels, cuts at 256-byte multiples
+// of the wire bytes (a tensor's offset is twice the wire offset), the allreduce in the wire dtype.
 //
 // One FusionPipe per engine thread: the keyed handler owns one (handler.cpp) and the thread world
 // one per virtual rank (executor.cpp, ddl_testing_thread_fused_allreduce), so the same code runs
@@ -41,10 +44,14 @@ public:
     // sub-plans above `cap` bytes (0: never). `ops` (one ddl_allreduce_op per segment, or null =
     // all SUM) with `divisor` = the communicator's size: the unpack of every (sub-)plan holding an
     // AVG segment is the dividing unpack (pack.hip k_seg_div), which stores the quotients of those
-    // segments; the cuts, the packs and the allreduces do not depend on the ops
+    // segments; the cuts, the packs and the allreduces do not depend on the ops.
+    // `src_dtype` != 0 and != dtype (DDL_FLOAT over a 16-bit `dtype`: wire compression): the tensors
+    // hold src_dtype elements, `bytes`, `cap`, the cuts and the allreduce are those of the WIRE stream
+    // in `dtype` (a tensor's offset at a cut is the wire offset scaled by the element sizes), and
+    // the pack / unpack are the converting kernels (SegmentCopier::run_cvt)
     void run(const std::vector<const void *> &srcs, const std::vector<void *> &dsts,
              const std::vector<size_t> &bytes, int dtype, size_t cap, hipStream_t stream, const Allreduce &ar,
-             const std::vector<int> *ops = nullptr, int divisor = 1);
+             const std::vector<int> *ops = nullptr, int divisor = 1, int src_dtype = 0);
     size_t subplans() const { return last_subplans_; }  // of the last run
 
     SegmentCopier copier;

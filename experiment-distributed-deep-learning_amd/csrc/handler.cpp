@@ -120,6 +120,8 @@ void validate(const Request &r, int size) {
     switch (r.type) {
         case kReqAllreduce:
             check_allreduce_op(r.op, r.dtype);
+            DDL_REQUIRE(r.wire == 0 || (r.dtype == DDL_FLOAT && !r.host && (r.wire == DDL_HALF || r.wire == DDL_BFLOAT16)),
+                        DDL_STATUS_INVALID_ARGUMENT, "wire dtype " << r.wire << " on a " << dtype_name(r.dtype) << " request");
             DDL_REQUIRE(r.n == 0 || (r.in && r.out), DDL_STATUS_INVALID_ARGUMENT, "null buffer");
             break;
         case kReqBroadcast:
@@ -463,8 +465,9 @@ void plan_slices(const Plan &p, const std::vector<Request> &reqs, const std::vec
         fn(static_cast<const char *>(r.in) + b * es, static_cast<char *>(r.out) + b * es, (e - b) * es);
     }
 }
-// The op of every slice plan_slices visits, in its order: a request's op is rank-local and applied
-// where its segment is written out; it never enters the group key or the plan cuts.
+// The op of every slice plan_slices visits, in its order: a request's SUM / AVG is rank-local and
+// applied where its segment is written out; it never enters the group key or the plan cuts (the wire
+// dtype of a compressed request, Request::wire, does: it is communicated).
 std::vector<int> plan_ops(const Plan &p, const std::vector<Request> &reqs, const std::vector<size_t> &group) {
     std::vector<int> ops;
     for (size_t q = p.req_begin; q <= p.req_end; ++q) ops.push_back(reqs[group[q]].op);
@@ -497,18 +500,29 @@ void RequestHandler::finish_plan_(const Plan &p, const std::vector<Request> &req
 // allreduceRequests (MPIRingTokenCommunication.cc:105-157): dtype groups in ascending enum order,
 // ids lexicographic inside, plans capped at the fusion threshold.
 void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Done> &dones, size_t &nplans) {
-    // (dtype, host): dtype groups in ascending enum order; host-resident requests — all of them
-    // in the reference, which only has CPU tensors — form their own groups after the device ones
-    std::map<std::pair<int, int>, std::vector<size_t>> groups;
+    // (wire dtype, compressed, host): dtype groups in ascending enum order; host-resident requests —
+    // all of them in the reference, which only has CPU tensors — form their own groups after the
+    // device ones. The wire dtype is the request's own dtype unless it is an fp32 request with a
+    // wire flag (Request::wire), whose group comes right after the native group of that 16-bit
+    // dtype — the same order on every rank, the wire being a property of the key. Groups of
+    // uncompressed requests are formed and ordered as without the flag.
+    std::map<std::tuple<int, int, int>, std::vector<size_t>> groups;
     for (size_t i = 0; i < reqs.size(); ++i) {
         if (reqs[i].n == 0) dones.push_back(Done{kNoPlan, i, DDL_STATUS_OK});  // nothing to reduce
-        else groups[std::make_pair(reqs[i].dtype, reqs[i].host ? 1 : 0)].push_back(i);
+        else
+            groups[std::make_tuple(reqs[i].wire ? reqs[i].wire : reqs[i].dtype, reqs[i].wire ? 1 : 0,
+                                   reqs[i].host ? 1 : 0)]
+                .push_back(i);
     }
     std::vector<hipEvent_t> waited;
     for (auto &g : groups) {
-        const int dt = g.first.first;
-        const bool host = g.first.second != 0;
-        const size_t es = dtype_size(dt);
+        const int dt = std::get<0>(g.first);  // what is communicated and summed
+        const bool comp = std::get<1>(g.first) != 0;
+        const bool host = std::get<2>(g.first) != 0;
+        const int sdt = comp ? DDL_FLOAT : dt;  // what the tensors hold
+        // plans, the fusion threshold and the message size count wire bytes (es); the tensors'
+        // slices their own (ses)
+        const size_t es = dtype_size(dt), ses = dtype_size(sdt);
         std::vector<size_t> elems, esz;
         for (size_t i : g.second) {
             elems.push_back(reqs[i].n);
@@ -550,11 +564,12 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
                                                         .count());
                 }
             } else if (data_->size() == 1 && config().one_rank_shortcut.load()) {
-                // a one-rank world: the sum is the input; move bytes only where out != in
-                plan_slices(p, reqs, g.second, es, [&](const char *s, char *d, size_t n) {
+                // a one-rank world: the sum is the input; move bytes only where out != in (nothing
+                // is communicated, so nothing is compressed either)
+                plan_slices(p, reqs, g.second, ses, [&](const char *s, char *d, size_t n) {
                     if (s != d && n) DDL_HIP(hipMemcpyAsync(d, s, n, hipMemcpyDeviceToDevice, stream_));
                 });
-            } else if (p.req_begin == p.req_end) {
+            } else if (p.req_begin == p.req_end && !comp) {
                 const Request &r = reqs[g.second[p.req_begin]];
                 const size_t cnt = p.elem_end - p.elem_begin;
                 data_->allreduce(static_cast<const char *>(r.in) + p.elem_begin * es,
@@ -563,17 +578,19 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
                 std::vector<const void *> srcs;
                 std::vector<void *> dsts;
                 std::vector<size_t> bytes;
-                plan_slices(p, reqs, g.second, es, [&](const char *s, char *d, size_t n) {
+                // a compressed plan always comes here, also with one request: the conversion is
+                // the pack's and the unpack's, so the in-place direct path cannot apply
+                plan_slices(p, reqs, g.second, ses, [&](const char *s, char *d, size_t n) {
                     srcs.push_back(s);
                     dsts.push_back(d);
-                    bytes.push_back(n);
+                    bytes.push_back(n / ses * es);  // on the wire
                 });
                 const std::vector<int> ops = plan_ops(p, reqs, g.second);  // AVG segments leave as quotients
                 fp_.run(srcs, dsts, bytes, dt, (size_t)config().fusion_pipeline_bytes.load(), stream_,
                         [&](void *buf, size_t elems, size_t message) {
                             data_->allreduce(buf, buf, elems, dt, DDL_ALLREDUCE_OP_SUM, stream_, message);
                         },
-                        &ops, data_->size());
+                        &ops, data_->size(), sdt);
             }
             finish_plan_(p, reqs, g.second, dones, nplans);
         }

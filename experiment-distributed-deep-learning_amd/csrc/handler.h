@@ -54,7 +54,8 @@ struct Request {
     void *out = nullptr;
     size_t n = 0;  // elements of `in`
     int dtype = 0;
-    int op = 0;
+    int op = 0;                       // allreduce: SUM / AVG (the wire flag decoded into `wire`)
+    int wire = 0;                     // allreduce: wire dtype of a compressed fp32 request (0: its own dtype)
     int root = 0;                     // broadcast: TensorBroadcastRequest::rootRank()
     size_t first_dim = 0;             // allgather: rows of `in` (n = first_dim * row_elems)
     size_t row_elems = 1;             //   elements per row (the shape without its first dim)

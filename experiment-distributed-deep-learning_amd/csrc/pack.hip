@@ -244,6 +244,156 @@ void launch_div(int dtype, bool narrow, dim3 g, hipStream_t stream, const char *
     }
 }
 
+// ---- the converting copies (ddl_allreduce_wire: fp32 tensors, 16-bit flat buffer) -----------------
+// k_seg_cvt_pack / k_seg_cvt_unpack: k_seg_tiles' mapping with the tiles defined on the WIRE side.
+// SegDesc::len / off and the 1 KiB tile count wire bytes (512 elements), so the segment table, the
+// tile index and flat_bytes are those of a plain copy of the wire stream; the tensor side of a tile
+// is 2 KiB of fp32. A lane handles 8 elements: two 16-byte fp32 vectors on the tensor side, one
+// 16-byte wire vector on the flat side (6 bytes moved per element against the plain copy's 8).
+// Pack: round to nearest even — the plain fptrunc, which hipcc lowers for gfx950 to v_cvt_pk_f16_f32
+// (the kernel's rounding mode, nearest even; NOT the round-toward-zero v_cvt_pkrtz_f16_f32; overflow
+// gives inf, subnormals are kept: the kernel's fp16 denormal mode) and to v_cvt_pk_bf16_f32, the
+// hardware's packed RNE conversion (profiles/wire_compress/kernel_resource_usage.txt); a NaN stays a
+// NaN in both. Unpack: widen (exact) and, for a kSegAvg segment,
+// the correctly rounded fp32 quotient by (float)P — true division, as k_seg_div. Element granular
+// at the edges like k_seg_div: a tensor that is only 4-byte aligned and a segment's last partial
+// vector go element by element.
+enum WireType : int { kWireF16 = 0, kWireBF16 = 1 };
+template <int WIRE> struct WireTraits;
+template <> struct WireTraits<kWireF16> {
+    using T = _Float16;
+    static __device__ inline T narrow(float x) { return (T)x; }
+    static __device__ inline float widen(T x) { return (float)x; }
+};
+template <> struct WireTraits<kWireBF16> {
+    using T = __bf16;
+    static __device__ inline T narrow(float x) { return (T)x; }
+    static __device__ inline float widen(T x) { return (float)x; }
+};
+
+template <bool NARROW>
+__device__ inline int tile_segment(unsigned tile, const uint32_t *__restrict__ blk_base, const void *__restrict__ map) {
+    return NARROW ? (int)(blk_base[tile / kIdxBlock] +
+                          ((static_cast<const uint32_t *>(map)[tile / 4] >> (8 * (tile % 4))) & 0xffu))
+                  : static_cast<const int *>(map)[tile];
+}
+
+template <int WIRE, bool NARROW>
+__global__ void __launch_bounds__(64) k_seg_cvt_pack(char *flat, const SegDesc *__restrict__ d,
+                                                     const uint32_t *__restrict__ blk_base,
+                                                     const void *__restrict__ map) {
+    using Tr = WireTraits<WIRE>;
+    using T = typename Tr::T;
+    union In {
+        u32x4 v;
+        float e[4];
+    };
+    union Out {
+        u32x4 v;
+        T e[8];
+    };
+    const unsigned tile = blockIdx.x;
+    const SegDesc sd = d[tile_segment<NARROW>(tile, blk_base, map)];
+    const uint64_t base = (uint64_t)(tile - sd.tile0) * 1024;  // tile start inside the segment, wire bytes
+    T *fl = reinterpret_cast<T *>(flat + sd.off);
+    const float *tp = reinterpret_cast<const float *>(sd.ptr);
+    if (!(sd.vec & kSegVec)) {  // tensor only 4-byte aligned: elements
+        const uint64_t end = (sd.len < base + 1024 ? sd.len : base + 1024) / sizeof(T);
+        for (uint64_t e = base / sizeof(T) + threadIdx.x; e < end; e += 64) fl[e] = Tr::narrow(tp[e]);
+        return;
+    }
+    const uint64_t b = base + threadIdx.x * 16;  // wire byte of the lane's vector; the tensor's byte 2b
+    if (b + 16 <= sd.len) {
+        const u32x4 *src = reinterpret_cast<const u32x4 *>(tp + b / sizeof(T));
+        In lo, hi;
+        lo.v = __builtin_nontemporal_load(src);
+        hi.v = __builtin_nontemporal_load(src + 1);
+        Out o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            o.e[k] = Tr::narrow(lo.e[k]);
+            o.e[4 + k] = Tr::narrow(hi.e[k]);
+        }
+        __builtin_nontemporal_store(o.v, reinterpret_cast<u32x4 *>(flat + sd.off + b));
+    } else if (b < sd.len) {  // the segment's last partial vector: elements
+        for (uint64_t e = b / sizeof(T); e < sd.len / sizeof(T); ++e) fl[e] = Tr::narrow(tp[e]);
+    }
+}
+
+template <int WIRE, bool NARROW>
+__global__ void __launch_bounds__(64) k_seg_cvt_unpack(const char *flat, const SegDesc *__restrict__ d,
+                                                       const uint32_t *__restrict__ blk_base,
+                                                       const void *__restrict__ map, float divisor) {
+    using Tr = WireTraits<WIRE>;
+    using T = typename Tr::T;
+    union In {
+        u32x4 v;
+        T e[8];
+    };
+    union Out {
+        u32x4 v;
+        float e[4];
+    };
+    const unsigned tile = blockIdx.x;
+    const SegDesc sd = d[tile_segment<NARROW>(tile, blk_base, map)];
+    const bool avg = (sd.vec & kSegAvg) != 0;
+    const uint64_t base = (uint64_t)(tile - sd.tile0) * 1024;
+    const T *fl = reinterpret_cast<const T *>(flat + sd.off);
+    float *tp = reinterpret_cast<float *>(sd.ptr);
+    if (!(sd.vec & kSegVec)) {
+        const uint64_t end = (sd.len < base + 1024 ? sd.len : base + 1024) / sizeof(T);
+        for (uint64_t e = base / sizeof(T) + threadIdx.x; e < end; e += 64) {
+            const float x = Tr::widen(fl[e]);
+            tp[e] = avg ? x / divisor : x;
+        }
+        return;
+    }
+    const uint64_t b = base + threadIdx.x * 16;
+    if (b + 16 <= sd.len) {
+        In x;
+        x.v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(flat + sd.off + b));
+        Out lo, hi;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            lo.e[k] = Tr::widen(x.e[k]);
+            hi.e[k] = Tr::widen(x.e[4 + k]);
+        }
+        if (avg) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                lo.e[k] = lo.e[k] / divisor;
+                hi.e[k] = hi.e[k] / divisor;
+            }
+        }
+        u32x4 *dst = reinterpret_cast<u32x4 *>(tp + b / sizeof(T));
+        __builtin_nontemporal_store(lo.v, dst);
+        __builtin_nontemporal_store(hi.v, dst + 1);
+    } else if (b < sd.len) {
+        for (uint64_t e = b / sizeof(T); e < sd.len / sizeof(T); ++e) {
+            const float x = Tr::widen(fl[e]);
+            tp[e] = avg ? x / divisor : x;
+        }
+    }
+}
+
+template <int WIRE>
+void launch_cvt_wire(int dir, bool narrow, dim3 g, hipStream_t stream, char *fl, const SegDesc *dd, const uint32_t *db,
+                     const void *map, float divisor) {
+    if (dir == 0) {
+        if (narrow) hipLaunchKernelGGL((k_seg_cvt_pack<WIRE, true>), g, dim3(64), 0, stream, fl, dd, db, map);
+        else hipLaunchKernelGGL((k_seg_cvt_pack<WIRE, false>), g, dim3(64), 0, stream, fl, dd, db, map);
+    } else {
+        if (narrow) hipLaunchKernelGGL((k_seg_cvt_unpack<WIRE, true>), g, dim3(64), 0, stream, fl, dd, db, map, divisor);
+        else hipLaunchKernelGGL((k_seg_cvt_unpack<WIRE, false>), g, dim3(64), 0, stream, fl, dd, db, map, divisor);
+    }
+}
+
+void launch_cvt(int wire, int dir, bool narrow, dim3 g, hipStream_t stream, char *fl, const SegDesc *dd,
+                const uint32_t *db, const void *map, float divisor) {
+    if (wire == DDL_HALF) launch_cvt_wire<kWireF16>(dir, narrow, g, stream, fl, dd, db, map, divisor);
+    else launch_cvt_wire<kWireBF16>(dir, narrow, g, stream, fl, dd, db, map, divisor);
+}
+
 }  // namespace
 
 SegmentCopier::~SegmentCopier() {
@@ -290,6 +440,27 @@ size_t SegmentCopier::flat_bytes(const size_t *bytes, int count) {
 
 void SegmentCopier::run(int dir, void *flat, void *const *segs, const size_t *bytes, int count,
                         hipStream_t stream, int dtype, int divisor, const int *ops) {
+    run_(dir, flat, segs, bytes, count, stream, dtype, divisor, ops, 0);
+}
+
+void SegmentCopier::run_cvt(int dir, void *flat, void *const *segs, const size_t *wire_bytes, int count,
+                            hipStream_t stream, int src_dtype, int wire_dtype, int divisor, const int *ops) {
+    DDL_REQUIRE(src_dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
+                "wire compression is defined for float32 sources, not " << dtype_name(src_dtype));
+    DDL_REQUIRE(wire_dtype == DDL_HALF || wire_dtype == DDL_BFLOAT16, DDL_STATUS_UNSUPPORTED_DTYPE,
+                "wire dtype " << wire_dtype << " is neither float16 nor bfloat16");
+    DDL_REQUIRE(dir == 0 || dir == 1, DDL_STATUS_INVALID_ARGUMENT, "copier direction " << dir);
+    DDL_REQUIRE(divisor >= 1, DDL_STATUS_INVALID_ARGUMENT, "divisor " << divisor);
+    for (int i = 0; i < count && segs && wire_bytes; ++i)
+        DDL_REQUIRE(wire_bytes[i] % 2 == 0 && reinterpret_cast<uintptr_t>(segs[i]) % 4 == 0, DDL_STATUS_INVALID_ARGUMENT,
+                    "segment " << i << " is not whole, aligned float32 elements");
+    run_(dir, flat, segs, wire_bytes, count, stream, src_dtype, divisor, dir == 1 ? ops : nullptr, wire_dtype);
+}
+
+// wire == 0: the plain copies and the dividing scatter over `bytes` of `dtype`; else the converting
+// copies, `bytes` the wire-side lengths
+void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *bytes, int count, hipStream_t stream,
+                         int dtype, int divisor, const int *ops, int wire) {
     if (count <= 0) return;
     // the quotient only where some segment asks for it and it is not the identity: every other
     // launch is the plain copy, its kernels and tables exactly as before
@@ -305,7 +476,7 @@ void SegmentCopier::run(int dir, void *flat, void *const *segs, const size_t *by
     }
     DDL_REQUIRE((flat || dir == kDivInPlace) && segs && bytes, DDL_STATUS_INVALID_ARGUMENT, "null pack arguments");
     const size_t es = div ? dtype_size(dtype) : 1;
-    if (div) {
+    if (div && !wire) {
         DDL_REQUIRE(dtype == DDL_FLOAT || dtype == DDL_DOUBLE || dtype == DDL_HALF || dtype == DDL_BFLOAT16,
                     DDL_STATUS_UNSUPPORTED_DTYPE, "AVG is not defined for dtype " << dtype);
         for (int i = 0; i < count; ++i)
@@ -378,7 +549,8 @@ void SegmentCopier::run(int dir, void *flat, void *const *segs, const size_t *by
         const dim3 ig((unsigned)((tiles + 255) / 256)), g((unsigned)tiles);
         if (narrow) hipLaunchKernelGGL(k_tile_index<true>, ig, dim3(256), 0, stream, dd, count, (uint64_t)tiles, db, sl.idx);
         else hipLaunchKernelGGL(k_tile_index<false>, ig, dim3(256), 0, stream, dd, count, (uint64_t)tiles, db, sl.idx);
-        if (div) launch_div(dtype, narrow, g, stream, fl, dd, db, sl.idx, (double)divisor);
+        if (wire) launch_cvt(wire, dir, narrow, g, stream, fl, dd, db, sl.idx, (float)divisor);
+        else if (div) launch_div(dtype, narrow, g, stream, fl, dd, db, sl.idx, (double)divisor);
         else launch_tiles(dir, narrow, g, stream, fl, dd, db, sl.idx);
     }
     DDL_HIP(hipGetLastError());
@@ -386,9 +558,14 @@ void SegmentCopier::run(int dir, void *flat, void *const *segs, const size_t *by
     if (dep::on()) {  // happens-before trace (deptrace.h): the segments and the flat buffer
         std::vector<dep::Access> acc;
         if (flat) acc.push_back(dir == 0 ? dep::wr(flat, off) : dep::rd(flat, off));
+        const size_t widen = wire ? dtype_size(dtype) / dtype_size(wire) : 1;  // the tensor side in its own bytes
         for (int i = 0; i < count; ++i)
-            if (bytes[i]) acc.push_back(dir == 0 ? dep::rd(segs[i], bytes[i]) : dep::wr(segs[i], bytes[i]));
-        dep::op(stream, dir == 0 ? "pack" : dir == 1 ? (div ? "unpack avg" : "unpack") : "divide", std::move(acc));
+            if (bytes[i])
+                acc.push_back(dir == 0 ? dep::rd(segs[i], bytes[i] * widen) : dep::wr(segs[i], bytes[i] * widen));
+        dep::op(stream,
+                wire ? (dir == 0 ? "pack cvt" : div ? "unpack cvt avg" : "unpack cvt")
+                     : dir == 0 ? "pack" : dir == 1 ? (div ? "unpack avg" : "unpack") : "divide",
+                std::move(acc));
     }
 }
 

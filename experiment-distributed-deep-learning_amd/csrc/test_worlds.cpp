@@ -283,7 +283,8 @@ void ThreadWorld::allreduce_batch(const void *const *in, void *const *out, const
 }
 
 size_t ThreadWorld::fused_allreduce(const void *const *srcs, void *const *dsts, const size_t *bytes, int count,
-                                    int dtype, hipStream_t user, const RingConfig &cfg, size_t cap, const int *ops) {
+                                    int dtype, hipStream_t user, const RingConfig &cfg, size_t cap, const int *ops,
+                                    int src_dtype) {
     while (pipes_.size() < (size_t)P_) pipes_.emplace_back(new FusionPipe);
     const std::vector<size_t> b(bytes, bytes + count);
     const std::vector<int> o(ops ? ops : nullptr, ops ? ops + count : nullptr);
@@ -294,7 +295,7 @@ size_t ThreadWorld::fused_allreduce(const void *const *srcs, void *const *dsts, 
             RingConfig c = cfg;
             c.order_bytes = message;
             ex_[r]->allreduce(buf, buf, elems, dtype, s, c);
-        }, ops ? &o : nullptr, P_);
+        }, ops ? &o : nullptr, P_, src_dtype);
     });
     return pipes_[0]->subplans();
 }

@@ -173,7 +173,8 @@ public:
     // dsts[r * count + i]: rank r's segment i of bytes[i] bytes; ops[i] (optional) segment i's
     // ddl_allreduce_op. Returns the sub-plans per rank.
     size_t fused_allreduce(const void *const *srcs, void *const *dsts, const size_t *bytes, int count, int dtype,
-                           hipStream_t user, const RingConfig &cfg, size_t cap, const int *ops = nullptr);
+                           hipStream_t user, const RingConfig &cfg, size_t cap, const int *ops = nullptr,
+                           int src_dtype = 0);  // != 0: a compressed plan (FusionPipe::run), bytes on the wire
 
 private:
     void run_(hipStream_t user, const std::function<void(int, hipStream_t)> &body);

@@ -40,6 +40,7 @@ STATUS_NAMES = {0: 'OK', 1: 'COMM_ERROR', 2: 'ERROR_UNKNOWN', 3: 'INVALID_ARGUME
                 8: 'CONFIG_MISMATCH'}
 STATUS_CONFIG_MISMATCH = 8
 OP_SUM, OP_AVG = 0, 1  # enum ddl_allreduce_op
+WIRE_FP16, WIRE_BF16 = 0x100, 0x200  # enum ddl_allreduce_wire: OR-ed into a keyed fp32 device request's op
 MEMORY_DEVICE, MEMORY_HOST = 0, 1  # enum ddl_memory
 
 DONE_FN = ctypes.CFUNCTYPE(None, ctypes.c_int, ctypes.c_void_p)
@@ -169,6 +170,10 @@ class CPPBackend:
         sig('ddl_pack', ci, vp, ctypes.POINTER(vp), ctypes.POINTER(sz), ci, vp)
         sig('ddl_unpack', ci, ctypes.POINTER(vp), vp, ctypes.POINTER(sz), ci, vp)
         sig('ddl_unpack_ops', ci, ctypes.POINTER(vp), vp, ctypes.POINTER(sz), ctypes.POINTER(ci), ci, ci, ci, vp)
+        sig('ddl_pack_cvt', ci, vp, ctypes.POINTER(vp), ctypes.POINTER(sz), ci, ci, vp)
+        sig('ddl_unpack_cvt', ci, ctypes.POINTER(vp), vp, ctypes.POINTER(sz), ctypes.POINTER(ci), ci, ci, ci, vp)
+        sig('ddl_testing_thread_fused_allreduce_wire', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp),
+            ctypes.POINTER(sz), ctypes.POINTER(ci), ci, vp, ctypes.POINTER(sz))
         sig('ddl_local_ring_allreduce', ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp), sz, ci, ci, vp)
         # RCCL loopback (test / diagnostic: the RCCL transport on one GPU)
         fp, lp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_longlong)

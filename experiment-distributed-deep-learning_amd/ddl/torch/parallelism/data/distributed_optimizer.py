@@ -30,6 +30,12 @@ into them) and no `div_` per gradient runs here. The engine's quotient is the IE
 and torch CPU's; torch's `div_` on a device tensor multiplies by the reciprocal instead, so device
 gradients may differ from the default's in the last bit when the size is no power of two. Off by
 default.
+
+`compression=Compression.fp16` / `Compression.bf16` (ddl.torch.compression): every dense fp32 device
+gradient travels and is summed as 16-bit values and comes back as fp32, converted inside the engine's
+fusion pack and unpack; the other gradients (other dtypes, CPU, sparse) are reduced as before. It
+composes with `fused_mean` (the mean of the widened sum, one fp32 rounding); without it the `div_`
+runs on the fp32 result. Off by default.
 """
 import contextlib
 import functools
@@ -38,6 +44,7 @@ import torch
 
 from ddl.torch import cpp_backend as cb
 from ddl.torch.communicator import Communicator
+from ddl.torch.compression import Compression, wire_flag
 from ddl.torch.tensor_communicate import allreduce_async, allreduce_async_batch, allreduce_gradient
 
 
@@ -46,6 +53,7 @@ class DataParallelismDistributedOptimizer:
     communicator: Communicator = None
     pin_host_gradients: bool = True
     fused_mean: bool = False
+    compression = Compression.none
     _ddl_name = 'DataParallelismDistributedOptimizer'
     _grad_handles = None  # overlap_backward: param -> Handle submitted by its hook
     _syncing = True
@@ -80,7 +88,8 @@ class DataParallelismDistributedOptimizer:
                                'earlier backward passes inside no_sync()')
         if self._pinning() and not g.is_cuda and not g.is_pinned():
             p.grad = g = g.pin_memory()
-        self._grad_handles[p] = allreduce_async(g, key, self._comm(), output=g, op=self._op())
+        self._grad_handles[p] = allreduce_async(g, key, self._comm(), output=g, op=self._op(),
+                                               compression=self.compression)
 
     @contextlib.contextmanager
     def no_sync(self):
@@ -129,7 +138,8 @@ class DataParallelismDistributedOptimizer:
                 keys.append(self._key(gi, pi))
         # one keyed request per gradient (the reference builds one Allreduce op per grad,
         # distributed_optimizer.py:50-63), registered as one batch, reduced in place
-        handles = zip(params, allreduce_async_batch(grads, keys, comm, outputs=grads, op=self._op()))
+        handles = zip(params, allreduce_async_batch(grads, keys, comm, outputs=grads, op=self._op(),
+                                                          compression=self.compression))
         for p, h in handles:
             out = h.wait()
             if not fused:
@@ -172,7 +182,8 @@ def data_parallelism_distributed_optimizer_wrapper(
         pin_host_gradients: bool = True,
         overlap_backward: bool = False,
         bucket_bytes: int = 32 << 20,
-        fused_mean: bool = False) -> torch.optim.Optimizer:
+        fused_mean: bool = False,
+        compression=Compression.none) -> torch.optim.Optimizer:
     """Return an optimizer of a subclass of `type(optimizer)` whose step() first averages the
     gradients across `communicator` (default: the world). Parameter groups and state are
     shared with `optimizer`. `pin_host_gradients`: keep CPU gradients in pinned memory;
@@ -181,7 +192,13 @@ def data_parallelism_distributed_optimizer_wrapper(
     `fusion_threshold_bytes`, so every rank must build the wrapper the same way; None keeps the
     configured cap): a round's gradients then reduce as several plans in backward order, each
     starting once its own gradients exist. `fused_mean`: the engine's AVG op takes the mean of the
-    dense gradients in place of a `div_` per gradient (module docstring)."""
+    dense gradients in place of a `div_` per gradient (module docstring). `compression`
+    (Compression.fp16 / Compression.bf16): the dense fp32 device gradients are sent and summed as
+    16-bit values on both paths, step() and the `overlap_backward` hooks, and every rank must build
+    the wrapper with the same value. fp16 OVERFLOWS: a gradient, or a partial sum over the ranks,
+    above 65504 in magnitude becomes inf and one below 6e-8 becomes 0, so use fp16 only with a loss
+    scale that keeps the gradients in range; bf16 has fp32's range (8 bits of precision) and is the
+    recommended choice for unscaled gradients."""
     opt_cls = optimizer.__class__
     assert issubclass(opt_cls, torch.optim.Optimizer)
     cls = type(opt_cls.__name__, (DataParallelismDistributedOptimizer, opt_cls), {})
@@ -190,6 +207,8 @@ def data_parallelism_distributed_optimizer_wrapper(
     res.communicator = communicator
     res.pin_host_gradients = pin_host_gradients
     res.fused_mean = bool(fused_mean)
+    wire_flag(compression)  # a TypeError here, not at the first step
+    res.compression = Compression.none if compression is None else compression
     if overlap_backward:
         if bucket_bytes:
             from ddl.torch import config

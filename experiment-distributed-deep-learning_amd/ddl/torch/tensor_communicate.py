@@ -24,6 +24,7 @@ import torch
 
 from ddl.torch import cpp_backend as cb
 from ddl.torch.communicator import Communicator
+from ddl.torch.compression import Compression, wire_flag
 from ddl.torch.cpp_backend import CPPBackend, check
 from ddl.torch.util import (current_stream_handle, ddl_dtype, memory_kind, require_device_tensor,
                            stream_handle_for)
@@ -92,11 +93,15 @@ def allreduce_batch_(tensors, communicator: Communicator = None, op: int = cb.OP
 
 
 def allreduce_gradient(tensor: torch.Tensor, communicator: Communicator = None,
-                       return_mean: bool = True, fused_mean: bool = False) -> torch.Tensor:
+                       return_mean: bool = True, fused_mean: bool = False,
+                       compression=Compression.none) -> torch.Tensor:
     """Dense gradient: allreduce, then divide by the size (tensor_communicate.py:21-25). With
     `fused_mean` the engine takes the mean itself (`op=cb.OP_AVG`: the IEEE quotient, in the kernel
     that writes the result) and no `div_` runs here; on a device tensor the last bit may then
     differ from torch's `div_`, which multiplies by the reciprocal, when the size is no power of two.
+    `compression` (Compression.fp16 / .bf16; a dense fp32 device gradient at size > 1): the gradient
+    goes through the keyed path and travels as 16-bit values (ddl.torch.compression); every other
+    gradient is reduced as without it.
 
     Sparse gradient (torch sparse COO, the counterpart of TF's IndexedSlices, :26-30): the
     values and the indices are allgathered — every rank's rows in rank order — and the mean
@@ -109,6 +114,16 @@ def allreduce_gradient(tensor: torch.Tensor, communicator: Communicator = None,
             values = values / communicator.size
         indices = allgather(tensor._indices().t().contiguous(), communicator).t()
         return torch.sparse_coo_tensor(indices, values, tensor.shape)
+    if _compressible(tensor, communicator, wire_flag(compression)):
+        # the wire format belongs to the keyed requests: one request under a per-communicator
+        # running name (every rank reduces its gradients in the same order)
+        src = tensor.contiguous()
+        name = f'allreduce_gradient/compressed/{next(_gradient_ids[communicator.id]):08d}'
+        op = cb.OP_AVG if return_mean and fused_mean else cb.OP_SUM
+        summed = allreduce_async(src, name, communicator, op=op, compression=compression).wait().view_as(tensor)
+        if return_mean and not fused_mean:
+            summed.div_(communicator.size)
+        return summed
     if return_mean and fused_mean:
         return allreduce(tensor, communicator, op=cb.OP_AVG)
     summed = allreduce(tensor, communicator)
@@ -398,6 +413,21 @@ def _watch_host(tensors):
         _release_range(a, b)
 
 
+_gradient_ids = collections.defaultdict(lambda: itertools.count())  # allreduce_gradient's compressed requests
+
+
+def _compressible(tensor: torch.Tensor, communicator: Communicator, flag: int, mem: int = None) -> bool:
+    """Whether `compression` applies to this request: a dense fp32 device tensor at size > 1. Every
+    other tensor of a call with `compression` is submitted uncompressed — not an error."""
+    if not flag or tensor.is_sparse or tensor.dtype != torch.float32:
+        return False
+    if (memory_kind(tensor) if mem is None else mem) != cb.MEMORY_DEVICE:
+        return False
+    # a one-rank world communicates nothing; only with the test setting one_rank_shortcut 0 does
+    # its data plane run, and then the wire format with it
+    return communicator.size > 1 or CPPBackend.c_api().ddl_get_config(b'one_rank_shortcut') == 0
+
+
 def _same_memory(a: torch.Tensor, b: torch.Tensor, what: str) -> int:
     ma, mb = memory_kind(a, f'{what} input'), memory_kind(b, f'{what} output')
     if ma != mb:
@@ -406,8 +436,11 @@ def _same_memory(a: torch.Tensor, b: torch.Tensor, what: str) -> int:
 
 
 def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator = None,
-                    output: torch.Tensor = None, op: int = cb.OP_SUM) -> Handle:
+                    output: torch.Tensor = None, op: int = cb.OP_SUM, compression=Compression.none) -> Handle:
     """Register a keyed allreduce (`op`: cb.OP_SUM, or cb.OP_AVG for the mean); returns a Handle.
+    `compression` (Compression.fp16 / .bf16): a dense fp32 device tensor at size > 1 is sent and
+    summed as 16-bit values and comes back as fp32 (ddl.torch.compression; every rank must pass the
+    same compression for a name); any other tensor is submitted as without it.
 
     `name` plays the role of the TF op name: the same name on every rank identifies the same
     gradient, and only one request per name may be pending (TensorCommunicateRequest.h:21).
@@ -421,6 +454,8 @@ def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator 
         _watch_host((tensor, out))
     # argument errors first: a group whose slot is never submitted would stay pending
     key, dt, stream = name.encode(), ddl_dtype(tensor), stream_handle_for(tensor)
+    if _compressible(tensor, communicator, wire_flag(compression), mem):
+        op = int(op) | wire_flag(compression)
     group = _Completion(1, (tensor, out))
     h = _NativeHandle(name, out, None, group, 0)  # the group holds the tensors
     st = CPPBackend.c_api().ddl_allreduce_submit_mem(
@@ -432,10 +467,14 @@ def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator 
     return h
 
 
-def allreduce_async_batch(tensors, names, communicator: Communicator = None, outputs=None, op: int = cb.OP_SUM):
+def allreduce_async_batch(tensors, names, communicator: Communicator = None, outputs=None, op: int = cb.OP_SUM,
+                          compression=Compression.none):
     """Register several keyed allreduces at once (one engine wake-up, one input-ready event), all
     with `op` (cb.OP_SUM, or cb.OP_AVG for the mean); returns one Handle per tensor. Same key rules as `allreduce_async`; device and host tensors
-    may be mixed (one submission per memory kind)."""
+    may be mixed (one submission per memory kind). `compression` (Compression.fp16 / .bf16) applies
+    to the dense fp32 device tensors at size > 1 (ddl.torch.compression); the others are submitted
+    uncompressed, so a mixed batch goes as one compressed and one plain submission. The handles
+    come back in the caller's order either way."""
     import ctypes
     communicator = _comm(communicator)
     tensors = list(tensors)
@@ -459,23 +498,29 @@ def allreduce_async_batch(tensors, names, communicator: Communicator = None, out
     group = _Completion(k, (tensors, outputs))
     handles = [_NativeHandle(n, o, None, group, i) for i, (n, o) in enumerate(zip(names, outputs))]
     done, slots = _native_done(), group.slots()
-    kinds = sorted(set(mems))
-    for mem in kinds:
-        if len(kinds) == 1:  # one memory kind (the usual batch): the arrays straight from the lists
+    # one submission per (memory kind, wire flag): the engine takes one op per batch, so the fp32
+    # device tensors that travel compressed go apart from the rest
+    flag = wire_flag(compression)
+    wires = [flag if flag and _compressible(t, communicator, flag, m_) else 0 for t, m_ in zip(tensors, mems)]
+    part = list(zip(mems, wires))
+    kinds = sorted(set(part))
+    for kind in kinds:
+        mem, wire = kind
+        if len(kinds) == 1:  # one kind (the usual batch): the arrays straight from the lists
             idx, ts, os_, ks, ds, users = range(k), tensors, outputs, keys_all, dts_all, slots
         else:
-            idx = [i for i in range(k) if mems[i] == mem]
+            idx = [i for i in range(k) if part[i] == kind]
             ts, os_ = [tensors[i] for i in idx], [outputs[i] for i in idx]
             ks, ds = [keys_all[i] for i in idx], [dts_all[i] for i in idx]
             users = (ctypes.c_void_p * len(idx))(*[slots[i] for i in idx])
         m = len(idx)
-        rest = [i for i in range(k) if mems[i] >= mem]  # this submission and the ones not made
+        rest = [i for i in range(k) if part[i] >= kind]  # this submission and the ones not made
         try:
             ins = (ctypes.c_void_p * m)(*[t.data_ptr() for t in ts])
             outs = ins if in_place else (ctypes.c_void_p * m)(*[o.data_ptr() for o in os_])
             st = CPPBackend.c_api().ddl_allreduce_submit_batch_mem(
                 communicator.id, m, (ctypes.c_char_p * m)(*ks), ins, outs,
-                (ctypes.c_size_t * m)(*[t.numel() for t in ts]), (ctypes.c_int * m)(*ds), int(op), mem,
+                (ctypes.c_size_t * m)(*[t.numel() for t in ts]), (ctypes.c_int * m)(*ds), int(op) | wire, mem,
                 stream_handle_for(tensors[idx[0]]), done, users)
         except BaseException:
             group.fail(rest, _STATUS_ERROR_UNKNOWN)  # not submitted: no slot may stay pending

@@ -79,6 +79,10 @@ enum ddl_memory { DDL_MEMORY_DEVICE = 0, DDL_MEMORY_HOST = 1 };
  * extension) is the SUM result divided by the communicator's size, the quotient taken on the GPU
  * by the kernel that writes the result (see the data-plane section). */
 enum ddl_allreduce_op { DDL_ALLREDUCE_OP_SUM = 0, DDL_ALLREDUCE_OP_AVG = 1 };
+/* Wire format of a keyed device allreduce of DDL_FLOAT tensors (MI355X extension, Horovod's
+ * Compression.fp16): at most one flag, OR-ed into `op`. The gradients travel and are summed as
+ * 16-bit values and come back as fp32 (see the data-plane section). */
+enum ddl_allreduce_wire { DDL_ALLREDUCE_WIRE_FP16 = 0x100, DDL_ALLREDUCE_WIRE_BF16 = 0x200 };
 
 typedef long long ddl_communicator_id;
 
@@ -220,10 +224,36 @@ void py_error(const char *log_str);
  * an integer dtype returns DDL_STATUS_UNSUPPORTED_DTYPE and any other op value
  * DDL_STATUS_INVALID_ARGUMENT, from every entry point, before anything is posted. AVG direct
  * collectives (ddl_allreduce, ddl_allreduce_batch) are refused inside a hipGraph capture.
- * The op never influences what is communicated: it is a per-request, rank-local property like the
- * output pointer (fusion groups, plans and schedules do not depend on it, and one round, plan or
- * unpack launch may mix SUM and AVG requests). Ranks that disagree about a key's op therefore get
- * different numbers, never a hang. */
+ * SUM against AVG never influences what is communicated: it is a per-request, rank-local property
+ * like the output pointer (fusion groups, plans and schedules do not depend on it, and one round,
+ * plan or unpack launch may mix SUM and AVG requests). Ranks that disagree about a key's SUM / AVG
+ * therefore get different numbers, never a hang.
+ *
+ * Wire compression: `op` = SUM or AVG, optionally OR-ed with ONE ddl_allreduce_wire flag, on a keyed
+ * device request of dtype DDL_FLOAT (ddl_allreduce_submit, _submit_batch, and _submit_mem /
+ * _submit_batch_mem with DDL_MEMORY_DEVICE). Definition: every rank's fp32 input is rounded to the
+ * wire type (fp16 or bf16) with round-to-nearest-even — overflow becomes +-inf, fp16 subnormals and
+ * signed zeros are kept, a NaN stays a NaN (its payload is not pinned); the rounded values are
+ * summed in the wire type exactly as a plain DDL_HALF / DDL_BFLOAT16 allreduce of them would be
+ * (MPICH's order for the plan's message size with reference_order 1, the message being the plan's
+ * unpadded WIRE bytes); the 16-bit sum is widened to fp32, which is exact; with AVG the widened sum
+ * is divided by (float)P with the correctly rounded fp32 quotient (one rounding fewer than a 16-bit
+ * AVG). Every step is what numpy / torch CPU compute. The conversions are part of the fusion pack
+ * and unpack kernels (csrc/pack.hip k_seg_cvt_pack / k_seg_cvt_unpack): no extra pass over the
+ * tensors; the fusion threshold and the pipeline cuts count wire bytes, and a compressed request
+ * always goes through the fusion buffer, also alone in its plan.
+ * Unlike SUM / AVG the wire IS communicated: it is a property of a key that every rank must agree
+ * on, like its dtype and element count (fp32-over-fp16 requests form a fusion group of their own,
+ * after the uncompressed group of the wire dtype, in the same order on every rank). Ranks that
+ * disagree about a key's wire flag post different collectives.
+ * Refusals, all before anything is registered or posted (the communicator works afterwards): a
+ * wire flag on any dtype but DDL_FLOAT returns DDL_STATUS_UNSUPPORTED_DTYPE (a batch takes one
+ * `op`, so a non-fp32 entry fails the whole batch: split such batches); both flags together or any
+ * other unknown bit, a wire flag with DDL_MEMORY_HOST, and a wire flag on ddl_allreduce,
+ * ddl_allreduce_batch or ddl_allreduce_host return DDL_STATUS_INVALID_ARGUMENT.
+ * P = 1: with "one_rank_shortcut" 1 nothing is communicated and nothing is compressed — the result
+ * is the input, bit for bit; with 0 the data plane runs and the result is the input round-tripped
+ * through the wire type. */
 /* recv = SUM over ranks of send (elementwise), bit for bit the reference's MPI_Allreduce (MPICH
  * 3.3.2's order) with reference_order 1. The schedule is the tuned one for the bucket's size
  * class: by default at P > 2 the direct reduce-scatter (slices of every chunk to every peer over

@@ -122,6 +122,16 @@ int ddl_unpack(void *const *dsts, const void *src, const size_t *bytes, int coun
  * every AVG segment is divided where it is, the others are not touched. */
 int ddl_unpack_ops(void *const *dsts, const void *src, const size_t *bytes, const int *ops, int count, int dtype,
                    int divisor, void *hip_stream);
+/* The converting pack / unpack of the wire compression (ddl_allreduce_wire; csrc/pack.hip
+ * k_seg_cvt_pack / k_seg_cvt_unpack). wire_dtype = DDL_HALF or DDL_BFLOAT16; the tensors hold
+ * elements[i] fp32 values (4-byte aligned), segment i of the flat buffer its elements[i] wire values
+ * at the running sum of the 256-byte-rounded wire lengths. _pack_cvt rounds to nearest even;
+ * _unpack_cvt widens and, where ops[i] == DDL_ALLREDUCE_OP_AVG, divides by (float)divisor
+ * (ops == NULL: all SUM). */
+int ddl_pack_cvt(void *dst, const void *const *srcs, const size_t *elements, int count, int wire_dtype,
+                 void *hip_stream);
+int ddl_unpack_cvt(void *const *dsts, const void *src, const size_t *elements, const int *ops, int count,
+                   int wire_dtype, int divisor, void *hip_stream);
 
 /* ---- single-GPU rehearsal of the ring schedule --------------------------------------- */
 /* Runs the exact per-rank ring schedule for `nranks` virtual ranks inside this process on
@@ -175,6 +185,13 @@ int ddl_testing_thread_fused_allreduce(int nranks, int count, const void *const 
 int ddl_testing_thread_fused_allreduce_ops(int nranks, int count, const void *const *srcs, void *const *dsts,
                                            const size_t *bytes, const int *ops, int dtype, void *hip_stream,
                                            size_t *subplans);
+/* The compressed plan: srcs / dsts are fp32 tensors of elements[i] values, the plan runs over
+ * wire_dtype (DDL_HALF / DDL_BFLOAT16) as the keyed handler runs a request group with a wire flag:
+ * converting pack, sub-plans cut on the wire stream, allreduce SUM in the wire dtype with the
+ * plan's unpadded wire bytes as its message, converting unpack with the segments' ops. */
+int ddl_testing_thread_fused_allreduce_wire(int nranks, int count, const void *const *srcs, void *const *dsts,
+                                            const size_t *elements, const int *ops, int wire_dtype,
+                                            void *hip_stream, size_t *subplans);
 /* Data movement of the thread worlds made from now on: rccl = 0 device copies (default); 1 every
  * matched send / receive pair goes through RcclTransport::group as a self send + self receive on
  * the RCCL loopback communicator (ddl_rccl_loopback_init first), posted on the receiver's stream
