@@ -148,6 +148,7 @@ int ddl_set_config(const char *key, long long value) {
             DDL_REQUIRE(value >= 0, DDL_STATUS_INVALID_ARGUMENT, "fusion_pipeline_bytes must be >= 0");
             c.fusion_pipeline_bytes = value;
         } else if (k == "one_rank_shortcut") c.one_rank_shortcut = value ? 1 : 0;
+        else if (k == "wire_feedback_epoch") c.wire_feedback_epoch = value;
         else if (k == "pipeline_rounds") c.pipeline_rounds = value ? 1 : 0;
         else if (k == "reference_order") c.reference_order = value ? 1 : 0;
         else if (k == "capture_mode") {
@@ -212,6 +213,7 @@ long long ddl_get_config(const char *key) {
     if (k == "host_lane_jobs") return c.host_lane_jobs;                       // statistic, not settable
     if (k == "fusion_pipeline_bytes") return c.fusion_pipeline_bytes;
     if (k == "one_rank_shortcut") return c.one_rank_shortcut;
+    if (k == "wire_feedback_epoch") return c.wire_feedback_epoch;
     if (k == "pipeline_rounds") return c.pipeline_rounds;
     if (k == "reference_order") return c.reference_order;
     if (k == "capture_mode") return c.capture_mode;
@@ -331,7 +333,7 @@ int ddl_allreduce_submit_mem(ddl_communicator_id id, const char *key, const void
         r.n = elements;
         r.dtype = dtype;
         r.host = memory == DDL_MEMORY_HOST;
-        r.wire = decode_keyed_op(op, dtype, r.host, &r.op);  // refusals before anything is posted
+        r.wire = decode_keyed_op(op, dtype, r.host, &r.op, &r.feedback);  // refusals before anything is posted
         r.done = done;
         r.user = user;
         r.ready = ready_event(memory, hip_stream);
@@ -422,7 +424,7 @@ int ddl_allreduce_submit_batch_mem(ddl_communicator_id id, int count, const char
             rs[i].n = elements[i];
             rs[i].dtype = dtypes[i];
             rs[i].host = memory == DDL_MEMORY_HOST;
-            rs[i].wire = decode_keyed_op(op, dtypes[i], rs[i].host, &rs[i].op);
+            rs[i].wire = decode_keyed_op(op, dtypes[i], rs[i].host, &rs[i].op, &rs[i].feedback);
             rs[i].done = done;
             rs[i].user = users ? users[i] : nullptr;
         }

@@ -412,6 +412,18 @@ int ddl_pack_cvt(void *dst, const void *const *srcs, const size_t *elements, int
     });
 }
 
+int ddl_pack_cvt_fb(void *dst, const void *const *srcs, void *const *residuals, const size_t *elements, int count,
+                    int wire_dtype, void *hip_stream) {
+    return guarded([&] {
+        DDL_REQUIRE(count >= 0 && (count == 0 || (dst && srcs && residuals && elements)), DDL_STATUS_INVALID_ARGUMENT,
+                    "bad pack_cvt_fb args");
+        const std::vector<size_t> b = wire_bytes(elements, count, wire_dtype);
+        std::lock_guard<std::mutex> g(abi_copier_mu());
+        abi_copier().run_cvt(0, dst, const_cast<void *const *>(srcs), b.data(), count, as_stream(hip_stream), DDL_FLOAT,
+                             wire_dtype, 1, nullptr, residuals);
+    });
+}
+
 int ddl_unpack_cvt(void *const *dsts, const void *src, const size_t *elements, const int *ops, int count,
                    int wire_dtype, int divisor, void *hip_stream) {
     return guarded([&] {
@@ -558,6 +570,22 @@ int ddl_testing_thread_fused_allreduce_wire(int nranks, int count, const void *c
                                                               as_stream(hip_stream), config().ring(),
                                                               (size_t)config().fusion_pipeline_bytes.load(), ops,
                                                               DDL_FLOAT);
+        if (subplans) *subplans = j;
+    });
+}
+
+int ddl_testing_thread_fused_allreduce_wire_fb(int nranks, int count, const void *const *srcs, void *const *dsts,
+                                               void *const *residuals, const size_t *elements, const int *ops,
+                                               int wire_dtype, void *hip_stream, size_t *subplans) {
+    return guarded([&] {
+        DDL_REQUIRE(nranks >= 1 && nranks <= 64 && count >= 1 && srcs && dsts && residuals && elements,
+                    DDL_STATUS_INVALID_ARGUMENT, "bad thread fused allreduce");
+        for (int i = 0; ops && i < count; ++i) check_allreduce_op(ops[i], DDL_FLOAT);
+        const std::vector<size_t> b = wire_bytes(elements, count, wire_dtype);
+        const size_t j = thread_world(nranks).fused_allreduce(srcs, dsts, b.data(), count, wire_dtype,
+                                                              as_stream(hip_stream), config().ring(),
+                                                              (size_t)config().fusion_pipeline_bytes.load(), ops,
+                                                              DDL_FLOAT, residuals);
         if (subplans) *subplans = j;
     });
 }

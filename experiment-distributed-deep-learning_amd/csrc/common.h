@@ -87,15 +87,20 @@ inline void check_allreduce_op(int op, int dtype) {
 }
 
 // The `op` of a keyed allreduce request: SUM / AVG in the low bits, optionally one
-// ddl_allreduce_wire flag. Returns the wire dtype (DDL_HALF / DDL_BFLOAT16; 0 = uncompressed) and
-// leaves SUM / AVG in *base. Refusals as ddl_amd.h lists them, before anything is registered.
-inline int decode_keyed_op(int op, int dtype, bool host, int *base) {
+// ddl_allreduce_wire format flag, optionally DDL_ALLREDUCE_WIRE_FEEDBACK with it. Returns the wire
+// dtype (DDL_HALF / DDL_BFLOAT16; 0 = uncompressed), leaves SUM / AVG in *base and the feedback bit
+// in *feedback. Refusals as ddl_amd.h lists them, before anything is registered.
+inline int decode_keyed_op(int op, int dtype, bool host, int *base, bool *feedback) {
     constexpr int kWire = DDL_ALLREDUCE_WIRE_FP16 | DDL_ALLREDUCE_WIRE_BF16;
-    *base = op & ~kWire;
+    *base = op & ~(kWire | DDL_ALLREDUCE_WIRE_FEEDBACK);
+    *feedback = (op & DDL_ALLREDUCE_WIRE_FEEDBACK) != 0;
     const int w = op & kWire;
     DDL_REQUIRE(w != kWire, DDL_STATUS_INVALID_ARGUMENT, "both wire flags in allreduce op " << op);
     DDL_REQUIRE(*base == DDL_ALLREDUCE_OP_SUM || *base == DDL_ALLREDUCE_OP_AVG, DDL_STATUS_INVALID_ARGUMENT,
-                "unknown allreduce op " << op << " (SUM = 0, AVG = 1, | WIRE_FP16 = 0x100 or WIRE_BF16 = 0x200)");
+                "unknown allreduce op " << op << " (SUM = 0, AVG = 1, | WIRE_FP16 = 0x100 or WIRE_BF16 = 0x200, "
+                                                 "| WIRE_FEEDBACK = 0x1000 with one of them)");
+    DDL_REQUIRE(w || !*feedback, DDL_STATUS_INVALID_ARGUMENT,
+                "WIRE_FEEDBACK without WIRE_FP16 or WIRE_BF16 in allreduce op " << op);
     if (!w) return 0;
     DDL_REQUIRE(!host, DDL_STATUS_INVALID_ARGUMENT, "wire compression is for device requests only");
     DDL_REQUIRE(dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
@@ -249,14 +254,19 @@ public:
     // = segment i's bytes on the FLAT side (elements x 2), so offsets, tiles and flat_bytes are those
     // of run() on the wire stream; the tensor side is twice as long. dir 0: round to nearest even
     // into the flat buffer (k_seg_cvt_pack); dir 1: widen, AVG segments divided by (float)divisor
-    // (k_seg_cvt_unpack).
+    // (k_seg_cvt_unpack). `residuals` (dir 0 only; parallel to `segs`, null entries allowed): error
+    // feedback (DDL_ALLREDUCE_WIRE_FEEDBACK) — segment i with residuals[i] != null packs
+    // narrow(tensor + residual) and leaves what the rounding removed in residuals[i] (fp32, the
+    // segment's element count; k_seg_cvt_pack_fb). With no non-null residual of a non-empty segment
+    // the launch is k_seg_cvt_pack, unchanged.
     void run_cvt(int dir, void *flat, void *const *segs, const size_t *wire_bytes, int count, hipStream_t stream,
-                 int src_dtype, int wire_dtype, int divisor = 1, const int *ops = nullptr);
+                 int src_dtype, int wire_dtype, int divisor = 1, const int *ops = nullptr,
+                 void *const *residuals = nullptr);
     static size_t flat_bytes(const size_t *bytes, int count);
 
 private:
     void run_(int dir, void *flat, void *const *segs, const size_t *bytes, int count, hipStream_t stream, int dtype,
-              int divisor, const int *ops, int wire);
+              int divisor, const int *ops, int wire, void *const *residuals);
     struct Slot {
         void *host = nullptr, *dev = nullptr;
         size_t cap = 0;

@@ -99,6 +99,11 @@ struct Config {
     // a one-rank world skips the keyed data plane (the sum is the input); 0 runs pack ->
     // allreduce -> unpack anyway (tests of the fusion path on one GPU)
     std::atomic<long long> one_rank_shortcut{1};
+    // error feedback of the 16-bit wire (DDL_ALLREDUCE_WIRE_FEEDBACK): a key's residual restarts
+    // from zero when this differs from the value under which it was last written (raise it after
+    // loading a checkpoint or a large change of the loss scale). Per process, not in shared_hash:
+    // the residuals are rank-local and change nothing that is communicated.
+    std::atomic<long long> wire_feedback_epoch{0};
     // keyed rounds: 1 — a completion thread waits for a round's data plane and fires its done()
     // calls while the engine thread negotiates and enqueues the next round; 0 — the engine
     // thread waits for each round before negotiating the next (as the reference's recv thread
@@ -146,7 +151,7 @@ struct Config {
     // fusion_threshold_bytes, tune, fusion_pipeline_bytes, reference_order, host_chunk_bytes,
     // rccl_min_ctas, rccl_max_ctas.
     // Never 0 or kCfgMismatch. Local tunables (log_level, cycle_time_us, host_copy_threads,
-    // host_zero_copy, pipeline_rounds, one_rank_shortcut) are not in it.
+    // host_zero_copy, pipeline_rounds, one_rank_shortcut, wire_feedback_epoch) are not in it.
     uint64_t shared_hash() const;
     RingConfig ring() const {
         RingConfig c;

@@ -41,19 +41,23 @@ hipEvent_t FusionPipe::event_(size_t i) {
 
 void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<void *> &dsts,
                      const std::vector<size_t> &bytes, int dt, size_t cap, hipStream_t stream, const Allreduce &ar,
-                     const std::vector<int> *ops, int divisor, int src_dt) {
+                     const std::vector<int> *ops, int divisor, int src_dt, const std::vector<void *> *residuals) {
     const size_t es = dtype_size(dt);
     DDL_REQUIRE(es != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported dtype " << dt);
     const bool cvt = src_dt != 0 && src_dt != dt;
     const size_t ses = cvt ? dtype_size(src_dt) : es;  // the tensors' element size
     DDL_REQUIRE(ses != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported source dtype " << src_dt);
     // gather (dir 0) / scatter (dir 1) of one (sub-)plan: the converting kernels with a wire dtype
-    auto copy = [&](int dir, void *fb, void *const *segs, const size_t *b, int n, hipStream_t s, const int *o) {
-        if (cvt) copier.run_cvt(dir, fb, segs, b, n, s, src_dt, dt, divisor, o);
+    // (`res`: the pack's residuals of a plan with error feedback)
+    auto copy = [&](int dir, void *fb, void *const *segs, const size_t *b, int n, hipStream_t s, const int *o,
+                    void *const *res = nullptr) {
+        if (cvt) copier.run_cvt(dir, fb, segs, b, n, s, src_dt, dt, divisor, o, dir == 0 ? res : nullptr);
         else if (dir == 0) copier.run(0, fb, segs, b, n, s);
         else copier.run(1, fb, segs, b, n, s, dt, divisor, o);
     };
     DDL_REQUIRE(!ops || ops->size() == bytes.size(), DDL_STATUS_INVALID_ARGUMENT, "fusion plan: one op per segment");
+    DDL_REQUIRE(!residuals || (cvt && residuals->size() == bytes.size()), DDL_STATUS_INVALID_ARGUMENT,
+                "fusion plan: one residual per segment of a compressed plan");
     DDL_REQUIRE(srcs.size() == bytes.size() && dsts.size() == bytes.size(), DDL_STATUS_INVALID_ARGUMENT,
                 "fusion plan: " << srcs.size() << " sources, " << dsts.size() << " destinations, " << bytes.size()
                                 << " sizes");
@@ -67,7 +71,7 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
         last_subplans_ = 1;
         void *fb = ensure(0, total, stream);
         copy(0, fb, const_cast<void *const *>(reinterpret_cast<const void *const *>(srcs.data())), bytes.data(),
-             (int)srcs.size(), stream, nullptr);
+             (int)srcs.size(), stream, nullptr, residuals ? residuals->data() : nullptr);
         ar(fb, total / es, message);
         copy(1, fb, dsts.data(), bytes.data(), (int)dsts.size(), stream, ops ? ops->data() : nullptr);
         return;
@@ -77,6 +81,7 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
         std::vector<void *> dst;
         std::vector<size_t> bytes;
         std::vector<int> ops;  // of each piece: its segment's (only with `ops`)
+        std::vector<void *> res;  // of each piece: its slice of the segment's residual (only with `residuals`)
         size_t flat = 0;
     };
     std::vector<Sub> subs(1);
@@ -96,6 +101,9 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
             cur->dst.push_back(static_cast<char *>(dsts[i]) + off / es * ses);
             cur->bytes.push_back(len);
             if (ops) cur->ops.push_back((*ops)[i]);
+            // the residual is indexed like the tensor: the same fp32 element offset at a cut
+            if (residuals)
+                cur->res.push_back((*residuals)[i] ? static_cast<char *>((*residuals)[i]) + off / es * ses : nullptr);
             cur->flat += (len + 255) & ~size_t(255);
             off += len;
         } while (off < bytes[i]);
@@ -121,7 +129,7 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
     for (size_t j = 0; j < J; ++j) {
         Sub &sb = subs[j];
         copy(0, buf[j % 2], const_cast<void *const *>(reinterpret_cast<const void *const *>(sb.src.data())),
-             sb.bytes.data(), (int)sb.src.size(), side_, nullptr);
+             sb.bytes.data(), (int)sb.src.size(), side_, nullptr, residuals ? sb.res.data() : nullptr);
         DDL_HIP(hipEventRecord(events_[1 + 2 * j], side_));
         dep::record(events_[1 + 2 * j], side_);
         DDL_HIP(hipStreamWaitEvent(stream, events_[1 + 2 * j], 0));

@@ -48,10 +48,15 @@ public:
     // `src_dtype` != 0 and != dtype (DDL_FLOAT over a 16-bit `dtype`: wire compression): the tensors
     // hold src_dtype elements, `bytes`, `cap`, the cuts and the allreduce are those of the WIRE stream
     // in `dtype` (a tensor's offset at a cut is the wire offset scaled by the element sizes), and
-    // the pack / unpack are the converting kernels (SegmentCopier::run_cvt)
+    // the pack / unpack are the converting kernels (SegmentCopier::run_cvt).
+    // `residuals` (a compressed plan only; one per segment, null entries = no feedback): the error
+    // feedback residuals of DDL_ALLREDUCE_WIRE_FEEDBACK, fp32 arrays indexed like the tensors — a
+    // sub-plan's piece takes its residual at the tensor's own element offset. The pack adds them in
+    // and rewrites them (k_seg_cvt_pack_fb); cuts, allreduces and unpacks do not depend on them.
     void run(const std::vector<const void *> &srcs, const std::vector<void *> &dsts,
              const std::vector<size_t> &bytes, int dtype, size_t cap, hipStream_t stream, const Allreduce &ar,
-             const std::vector<int> *ops = nullptr, int divisor = 1, int src_dtype = 0);
+             const std::vector<int> *ops = nullptr, int divisor = 1, int src_dtype = 0,
+             const std::vector<void *> *residuals = nullptr);
     size_t subplans() const { return last_subplans_; }  // of the last run
 
     SegmentCopier copier;

@@ -110,6 +110,8 @@ RequestHandler::~RequestHandler() {
     for (hipEvent_t e : free_events_) (void)hipEventDestroy(e);
     if (gather_) (void)hipFree(gather_);
     if (dims_) (void)hipFree(dims_);
+    for (auto &kv : residuals_)  // the error-feedback residuals live as long as the handler
+        if (kv.second.ptr) (void)hipFree(kv.second.ptr);
     host_.reset();  // the host path's slots, streams and registrations (its work waits on stream_)
     if (stream_) (void)hipStreamDestroy(stream_);
 }
@@ -122,6 +124,7 @@ void validate(const Request &r, int size) {
             check_allreduce_op(r.op, r.dtype);
             DDL_REQUIRE(r.wire == 0 || (r.dtype == DDL_FLOAT && !r.host && (r.wire == DDL_HALF || r.wire == DDL_BFLOAT16)),
                         DDL_STATUS_INVALID_ARGUMENT, "wire dtype " << r.wire << " on a " << dtype_name(r.dtype) << " request");
+            DDL_REQUIRE(!r.feedback || r.wire != 0, DDL_STATUS_INVALID_ARGUMENT, "error feedback without a wire dtype");
             DDL_REQUIRE(r.n == 0 || (r.in && r.out), DDL_STATUS_INVALID_ARGUMENT, "null buffer");
             break;
         case kReqBroadcast:
@@ -475,6 +478,25 @@ std::vector<int> plan_ops(const Plan &p, const std::vector<Request> &reqs, const
 }
 }  // namespace
 
+// Engine thread only. hipMalloc does not wait for the device (profiles/r06/s17); the zeroing is
+// posted on stream_, so it runs after every earlier pack of this key and before the next one. A
+// residual of another element count is retired, not freed: its last pack may still be running.
+void *RequestHandler::residual_(const Request &r) {
+    const long long epoch = config().wire_feedback_epoch.load();
+    Residual &res = residuals_[r.key];
+    if (res.ptr && res.n == r.n && res.epoch == epoch) return res.ptr;
+    if (res.n != r.n) {
+        if (res.ptr) retire_device(res.ptr);
+        res.ptr = nullptr;
+        res.n = 0;
+        DDL_HIP(hipMalloc(&res.ptr, r.n * sizeof(float)));
+        res.n = r.n;
+    }
+    res.epoch = epoch;
+    DDL_HIP(hipMemsetAsync(res.ptr, 0, r.n * sizeof(float), stream_));
+    return res.ptr;
+}
+
 std::unique_lock<std::mutex> RequestHandler::lock_host_group_(const std::vector<Request> &reqs,
                                                               const std::vector<size_t> &group, size_t es, bool host) {
     if (!host) return {};
@@ -529,6 +551,19 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
             esz.push_back(es);
         }
         const std::unique_lock<std::mutex> rg = lock_host_group_(reqs, g.second, es, host);
+        // error feedback (Request::feedback, rank-local like the op): the residual of every request
+        // of a compressed group that asks for it, found or made once per round; none where the
+        // one-rank shortcut skips the data plane
+        std::vector<void *> resid;
+        if (comp && !(data_->size() == 1 && config().one_rank_shortcut.load())) {
+            bool any = false;
+            for (size_t i : g.second) any = any || reqs[i].feedback;
+            if (any) {
+                resid.assign(g.second.size(), nullptr);
+                for (size_t q = 0; q < g.second.size(); ++q)
+                    if (reqs[g.second[q]].feedback) resid[q] = residual_(reqs[g.second[q]]);
+            }
+        }
         for (const Plan &p : make_plans(elems, esz, (size_t)config().fusion_threshold_bytes.load())) {
             for (size_t q = p.req_begin; q <= p.req_end; ++q) wait_inputs_(reqs[g.second[q]], waited);
             if (host) {
@@ -586,11 +621,17 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
                     bytes.push_back(n / ses * es);  // on the wire
                 });
                 const std::vector<int> ops = plan_ops(p, reqs, g.second);  // AVG segments leave as quotients
+                // the plan's slices of the residuals, at the tensors' own element offsets. A plan
+                // that fails after its pack has already updated them: that is not undone.
+                std::vector<void *> res;
+                for (size_t q = p.req_begin; q <= p.req_end && !resid.empty(); ++q)
+                    res.push_back(resid[q] ? static_cast<char *>(resid[q]) + (q == p.req_begin ? p.elem_begin : 0) * ses
+                                           : nullptr);
                 fp_.run(srcs, dsts, bytes, dt, (size_t)config().fusion_pipeline_bytes.load(), stream_,
                         [&](void *buf, size_t elems, size_t message) {
                             data_->allreduce(buf, buf, elems, dt, DDL_ALLREDUCE_OP_SUM, stream_, message);
                         },
-                        &ops, data_->size(), sdt);
+                        &ops, data_->size(), sdt, resid.empty() ? nullptr : &res);
             }
             finish_plan_(p, reqs, g.second, dones, nplans);
         }

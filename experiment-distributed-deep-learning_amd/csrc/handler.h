@@ -56,6 +56,7 @@ struct Request {
     int dtype = 0;
     int op = 0;                       // allreduce: SUM / AVG (the wire flag decoded into `wire`)
     int wire = 0;                     // allreduce: wire dtype of a compressed fp32 request (0: its own dtype)
+    bool feedback = false;            // allreduce: DDL_ALLREDUCE_WIRE_FEEDBACK (only with `wire`; rank-local)
     int root = 0;                     // broadcast: TensorBroadcastRequest::rootRank()
     size_t first_dim = 0;             // allgather: rows of `in` (n = first_dim * row_elems)
     size_t row_elems = 1;             //   elements per row (the shape without its first dim)
@@ -158,6 +159,19 @@ private:
     // multi-request plans: pack -> allreduce -> unpack, pipelined in sub-plans above
     // fusion_pipeline_bytes (fusion.h); its buffer 0 also packs broadcast / allgather plans
     FusionPipe fp_;
+    // Error feedback (DDL_ALLREDUCE_WIRE_FEEDBACK): what the wire's rounding removed from this rank's
+    // contribution to a key, added back at the key's next request. One fp32 array per key that ever
+    // asked for feedback, owned here and freed with the handler (a replaced one is retired, never
+    // freed on a data path). Touched by the engine thread only (allreduce_reqs_ posts the packs).
+    struct Residual {
+        void *ptr = nullptr;
+        size_t n = 0;         // elements
+        long long epoch = 0;  // config wire_feedback_epoch when it was last (re)started
+    };
+    std::unordered_map<std::string, Residual> residuals_;
+    // the residual of request r for a pack posted on stream_: made, or restarted from zero (another
+    // element count, another epoch), by work posted on stream_ ahead of that pack
+    void *residual_(const Request &r);
     // host-resident requests: made once stream_ exists, destroyed (both threads joined) before it
     std::unique_ptr<HostStager> host_;
     void *gather_ = nullptr;  // allgather receive side

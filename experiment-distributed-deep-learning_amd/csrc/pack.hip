@@ -320,6 +320,108 @@ __global__ void __launch_bounds__(64) k_seg_cvt_pack(char *flat, const SegDesc *
     }
 }
 
+// ---- the converting pack with error feedback (DDL_ALLREDUCE_WIRE_FEEDBACK) -----------------------
+// k_seg_cvt_pack_fb: k_seg_cvt_pack's mapping (the same segment table, tile index, 1 KiB wire tiles,
+// 64 lanes, 8 elements per lane) plus one table of residual addresses, res[seg] (0: the segment is
+// converted as k_seg_cvt_pack converts it). Per element of a segment with a residual r (fp32, the
+// segment's element count, indexed like the tensor):
+//     v = g + r;  w = narrow(v);  r' = isfinite(widen(w)) ? v - widen(w) : 0
+// w goes to the flat buffer, r' replaces r. One fp32 rounding (g + r, nearest even, subnormals kept)
+// beyond the wire's own: v - widen(w) is exact whenever widen(w) is finite. A NaN or inf in v, or
+// an overflow of the narrowing, clears the residual. No multiply, so nothing can contract; no
+// reciprocal. Moves 14 bytes per element against the plain converting pack's 6: the vector path
+// (tensor AND residual 16-byte aligned) is two 16-byte loads from each, one 16-byte wire store and
+// two 16-byte residual stores. The tensor loads and all stores are non-temporal (the residual is
+// next read a whole step later); the residual LOADS are plain: with non-temporal loads of both read
+// streams the C5 set took 1.73 ms against 1.49-1.53 ms (profiles/wire_feedback/feedback_probe_nt_loads.json
+// against feedback_probe.json). Otherwise, and for a segment's last partial vector, element by
+// element.
+template <int WIRE>
+__device__ inline typename WireTraits<WIRE>::T feedback(float g, float &r) {
+    using Tr = WireTraits<WIRE>;
+    const float v = g + r;
+    const typename Tr::T w = Tr::narrow(v);
+    const float wf = Tr::widen(w);
+    r = __builtin_isfinite(wf) ? v - wf : 0.0f;
+    return w;
+}
+
+template <int WIRE, bool NARROW>
+__global__ void __launch_bounds__(64) k_seg_cvt_pack_fb(char *flat, const SegDesc *__restrict__ d,
+                                                        const uint32_t *__restrict__ blk_base,
+                                                        const void *__restrict__ map,
+                                                        const uint64_t *__restrict__ res) {
+    using Tr = WireTraits<WIRE>;
+    using T = typename Tr::T;
+    union In {
+        u32x4 v;
+        float e[4];
+    };
+    union Out {
+        u32x4 v;
+        T e[8];
+    };
+    const unsigned tile = blockIdx.x;
+    const int seg = tile_segment<NARROW>(tile, blk_base, map);
+    const SegDesc sd = d[seg];
+    const uint64_t rp = res[seg];
+    const uint64_t base = (uint64_t)(tile - sd.tile0) * 1024;  // tile start inside the segment, wire bytes
+    T *fl = reinterpret_cast<T *>(flat + sd.off);
+    const float *tp = reinterpret_cast<const float *>(sd.ptr);
+    float *rs = reinterpret_cast<float *>(rp);
+    if (!(sd.vec & kSegVec) || (rp & 15u)) {  // tensor or residual only 4-byte aligned: elements
+        const uint64_t end = (sd.len < base + 1024 ? sd.len : base + 1024) / sizeof(T);
+        for (uint64_t e = base / sizeof(T) + threadIdx.x; e < end; e += 64) {
+            if (rs) {
+                float r = rs[e];
+                fl[e] = feedback<WIRE>(tp[e], r);
+                rs[e] = r;
+            } else {
+                fl[e] = Tr::narrow(tp[e]);
+            }
+        }
+        return;
+    }
+    const uint64_t b = base + threadIdx.x * 16;  // wire byte of the lane's vector; the tensor's byte 2b
+    if (b + 16 <= sd.len) {
+        const u32x4 *src = reinterpret_cast<const u32x4 *>(tp + b / sizeof(T));
+        In lo, hi;
+        lo.v = __builtin_nontemporal_load(src);
+        hi.v = __builtin_nontemporal_load(src + 1);
+        Out o;
+        if (rs) {
+            u32x4 *rv = reinterpret_cast<u32x4 *>(rs + b / sizeof(T));
+            In rlo, rhi;
+            rlo.v = rv[0];  // plain loads: measured faster than non-temporal ones (above)
+            rhi.v = rv[1];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                o.e[k] = feedback<WIRE>(lo.e[k], rlo.e[k]);
+                o.e[4 + k] = feedback<WIRE>(hi.e[k], rhi.e[k]);
+            }
+            __builtin_nontemporal_store(rlo.v, rv);
+            __builtin_nontemporal_store(rhi.v, rv + 1);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                o.e[k] = Tr::narrow(lo.e[k]);
+                o.e[4 + k] = Tr::narrow(hi.e[k]);
+            }
+        }
+        __builtin_nontemporal_store(o.v, reinterpret_cast<u32x4 *>(flat + sd.off + b));
+    } else if (b < sd.len) {  // the segment's last partial vector: elements
+        for (uint64_t e = b / sizeof(T); e < sd.len / sizeof(T); ++e) {
+            if (rs) {
+                float r = rs[e];
+                fl[e] = feedback<WIRE>(tp[e], r);
+                rs[e] = r;
+            } else {
+                fl[e] = Tr::narrow(tp[e]);
+            }
+        }
+    }
+}
+
 template <int WIRE, bool NARROW>
 __global__ void __launch_bounds__(64) k_seg_cvt_unpack(const char *flat, const SegDesc *__restrict__ d,
                                                        const uint32_t *__restrict__ blk_base,
@@ -394,6 +496,19 @@ void launch_cvt(int wire, int dir, bool narrow, dim3 g, hipStream_t stream, char
     else launch_cvt_wire<kWireBF16>(dir, narrow, g, stream, fl, dd, db, map, divisor);
 }
 
+template <int WIRE>
+void launch_cvt_fb_wire(bool narrow, dim3 g, hipStream_t stream, char *fl, const SegDesc *dd, const uint32_t *db,
+                        const void *map, const uint64_t *res) {
+    if (narrow) hipLaunchKernelGGL((k_seg_cvt_pack_fb<WIRE, true>), g, dim3(64), 0, stream, fl, dd, db, map, res);
+    else hipLaunchKernelGGL((k_seg_cvt_pack_fb<WIRE, false>), g, dim3(64), 0, stream, fl, dd, db, map, res);
+}
+
+void launch_cvt_fb(int wire, bool narrow, dim3 g, hipStream_t stream, char *fl, const SegDesc *dd, const uint32_t *db,
+                   const void *map, const uint64_t *res) {
+    if (wire == DDL_HALF) launch_cvt_fb_wire<kWireF16>(narrow, g, stream, fl, dd, db, map, res);
+    else launch_cvt_fb_wire<kWireBF16>(narrow, g, stream, fl, dd, db, map, res);
+}
+
 }  // namespace
 
 SegmentCopier::~SegmentCopier() {
@@ -440,11 +555,12 @@ size_t SegmentCopier::flat_bytes(const size_t *bytes, int count) {
 
 void SegmentCopier::run(int dir, void *flat, void *const *segs, const size_t *bytes, int count,
                         hipStream_t stream, int dtype, int divisor, const int *ops) {
-    run_(dir, flat, segs, bytes, count, stream, dtype, divisor, ops, 0);
+    run_(dir, flat, segs, bytes, count, stream, dtype, divisor, ops, 0, nullptr);
 }
 
 void SegmentCopier::run_cvt(int dir, void *flat, void *const *segs, const size_t *wire_bytes, int count,
-                            hipStream_t stream, int src_dtype, int wire_dtype, int divisor, const int *ops) {
+                            hipStream_t stream, int src_dtype, int wire_dtype, int divisor, const int *ops,
+                            void *const *residuals) {
     DDL_REQUIRE(src_dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
                 "wire compression is defined for float32 sources, not " << dtype_name(src_dtype));
     DDL_REQUIRE(wire_dtype == DDL_HALF || wire_dtype == DDL_BFLOAT16, DDL_STATUS_UNSUPPORTED_DTYPE,
@@ -454,13 +570,23 @@ void SegmentCopier::run_cvt(int dir, void *flat, void *const *segs, const size_t
     for (int i = 0; i < count && segs && wire_bytes; ++i)
         DDL_REQUIRE(wire_bytes[i] % 2 == 0 && reinterpret_cast<uintptr_t>(segs[i]) % 4 == 0, DDL_STATUS_INVALID_ARGUMENT,
                     "segment " << i << " is not whole, aligned float32 elements");
-    run_(dir, flat, segs, wire_bytes, count, stream, src_dtype, divisor, dir == 1 ? ops : nullptr, wire_dtype);
+    // error feedback only where some non-empty segment of a pack has a residual: every other launch
+    // is the plain converting copy, its kernel and tables exactly as before
+    bool fb = false;
+    for (int i = 0; i < count && residuals && wire_bytes && dir == 0; ++i) {
+        if (!residuals[i] || !wire_bytes[i]) continue;
+        DDL_REQUIRE(reinterpret_cast<uintptr_t>(residuals[i]) % 4 == 0, DDL_STATUS_INVALID_ARGUMENT,
+                    "residual " << i << " is not aligned float32 elements");
+        fb = true;
+    }
+    run_(dir, flat, segs, wire_bytes, count, stream, src_dtype, divisor, dir == 1 ? ops : nullptr, wire_dtype,
+         fb ? residuals : nullptr);
 }
 
 // wire == 0: the plain copies and the dividing scatter over `bytes` of `dtype`; else the converting
-// copies, `bytes` the wire-side lengths
+// copies, `bytes` the wire-side lengths; `residuals` (a converting pack only): the feedback pack
 void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *bytes, int count, hipStream_t stream,
-                         int dtype, int divisor, const int *ops, int wire) {
+                         int dtype, int divisor, const int *ops, int wire, void *const *residuals) {
     if (count <= 0) return;
     // the quotient only where some segment asks for it and it is not the identity: every other
     // launch is the plain copy, its kernels and tables exactly as before
@@ -499,7 +625,9 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
     DDL_REQUIRE(tiles < (1ull << 31), DDL_STATUS_INVALID_ARGUMENT, "fusion buffer too large");
     const uint64_t nblk = (tiles + kIdxBlock - 1) / kIdxBlock;
     const size_t table = (size_t)count * sizeof(SegDesc);
-    const size_t need = table + nblk * sizeof(uint32_t);  // descriptors, then the block bases
+    // descriptors, then the block bases, then (feedback pack) one residual address per segment
+    const size_t rtab = (table + nblk * sizeof(uint32_t) + 7) & ~size_t(7);
+    const size_t need = residuals ? rtab + (size_t)count * sizeof(uint64_t) : table + nblk * sizeof(uint32_t);
     if (need > sl.cap) {  // outgrown tables kept until ddl_finalize: no hipFree on a data path (engine.h)
         retire_host(sl.host);
         retire_device(sl.dev);
@@ -523,6 +651,10 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
         tl += (bytes[i] + seg_tile - 1) / seg_tile;
     }
     if (off == 0) return;
+    if (residuals) {
+        uint64_t *rt = reinterpret_cast<uint64_t *>(static_cast<char *>(sl.host) + rtab);
+        for (int i = 0; i < count; ++i) rt[i] = bytes[i] ? reinterpret_cast<uint64_t>(residuals[i]) : 0;
+    }
     // block b's base: the segment of tile b * 128 (the last one with tile0 <= it, as
     // k_tile_index resolves); narrow when no block spans more than 255 segments
     bool narrow = true;
@@ -549,7 +681,10 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
         const dim3 ig((unsigned)((tiles + 255) / 256)), g((unsigned)tiles);
         if (narrow) hipLaunchKernelGGL(k_tile_index<true>, ig, dim3(256), 0, stream, dd, count, (uint64_t)tiles, db, sl.idx);
         else hipLaunchKernelGGL(k_tile_index<false>, ig, dim3(256), 0, stream, dd, count, (uint64_t)tiles, db, sl.idx);
-        if (wire) launch_cvt(wire, dir, narrow, g, stream, fl, dd, db, sl.idx, (float)divisor);
+        if (residuals)
+            launch_cvt_fb(wire, narrow, g, stream, fl, dd, db, sl.idx,
+                          reinterpret_cast<const uint64_t *>(static_cast<char *>(sl.dev) + rtab));
+        else if (wire) launch_cvt(wire, dir, narrow, g, stream, fl, dd, db, sl.idx, (float)divisor);
         else if (div) launch_div(dtype, narrow, g, stream, fl, dd, db, sl.idx, (double)divisor);
         else launch_tiles(dir, narrow, g, stream, fl, dd, db, sl.idx);
     }
@@ -562,8 +697,13 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
         for (int i = 0; i < count; ++i)
             if (bytes[i])
                 acc.push_back(dir == 0 ? dep::rd(segs[i], bytes[i] * widen) : dep::wr(segs[i], bytes[i] * widen));
+        for (int i = 0; i < count && residuals; ++i)
+            if (bytes[i] && residuals[i]) {  // read and written: both, so the race check sees either side
+                acc.push_back(dep::rd(residuals[i], bytes[i] * widen));
+                acc.push_back(dep::wr(residuals[i], bytes[i] * widen));
+            }
         dep::op(stream,
-                wire ? (dir == 0 ? "pack cvt" : div ? "unpack cvt avg" : "unpack cvt")
+                wire ? (dir == 0 ? (residuals ? "pack cvt fb" : "pack cvt") : div ? "unpack cvt avg" : "unpack cvt")
                      : dir == 0 ? "pack" : dir == 1 ? (div ? "unpack avg" : "unpack") : "divide",
                 std::move(acc));
     }

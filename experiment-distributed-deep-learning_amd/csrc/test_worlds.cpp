@@ -284,18 +284,20 @@ void ThreadWorld::allreduce_batch(const void *const *in, void *const *out, const
 
 size_t ThreadWorld::fused_allreduce(const void *const *srcs, void *const *dsts, const size_t *bytes, int count,
                                     int dtype, hipStream_t user, const RingConfig &cfg, size_t cap, const int *ops,
-                                    int src_dtype) {
+                                    int src_dtype, void *const *residuals) {
     while (pipes_.size() < (size_t)P_) pipes_.emplace_back(new FusionPipe);
     const std::vector<size_t> b(bytes, bytes + count);
     const std::vector<int> o(ops ? ops : nullptr, ops ? ops + count : nullptr);
     run_(user, [&](int r, hipStream_t s) {
         const std::vector<const void *> src(srcs + (size_t)r * count, srcs + (size_t)(r + 1) * count);
         const std::vector<void *> dst(dsts + (size_t)r * count, dsts + (size_t)(r + 1) * count);
+        std::vector<void *> res;
+        if (residuals) res.assign(residuals + (size_t)r * count, residuals + (size_t)(r + 1) * count);
         pipes_[r]->run(src, dst, b, dtype, cap, s, [&](void *buf, size_t elems, size_t message) {
             RingConfig c = cfg;
             c.order_bytes = message;
             ex_[r]->allreduce(buf, buf, elems, dtype, s, c);
-        }, ops ? &o : nullptr, P_, src_dtype);
+        }, ops ? &o : nullptr, P_, src_dtype, residuals ? &res : nullptr);
     });
     return pipes_[0]->subplans();
 }

@@ -174,7 +174,8 @@ public:
     // ddl_allreduce_op. Returns the sub-plans per rank.
     size_t fused_allreduce(const void *const *srcs, void *const *dsts, const size_t *bytes, int count, int dtype,
                            hipStream_t user, const RingConfig &cfg, size_t cap, const int *ops = nullptr,
-                           int src_dtype = 0);  // != 0: a compressed plan (FusionPipe::run), bytes on the wire
+                           int src_dtype = 0,  // != 0: a compressed plan (FusionPipe::run), bytes on the wire
+                           void *const *residuals = nullptr);  // [r * count + i]: error feedback of a compressed plan
 
 private:
     void run_(hipStream_t user, const std::function<void(int, hipStream_t)> &body);

@@ -9,6 +9,21 @@ ddl_allreduce_wire). `Compression.none` (the default everywhere) changes nothing
 fp16 overflows: a gradient or a partial sum beyond 65504 in magnitude becomes inf, and values
 below 6e-8 become zero — use it with a loss scale that keeps the gradients in range. bf16 keeps
 fp32's range with 8 bits of precision and is the choice for unscaled gradients.
+
+Error feedback: `Compression.fp16_feedback` / `Compression.bf16_feedback` (EF-SGD, 1-bit SGD). What
+the rounding removes is otherwise lost at every step, in the same direction for a gradient that
+changes slowly: a constant 1 + 2**-10 reads 1.0 over bf16 for ever, and an fp16 gradient of 1e-8 is
+always zero. With feedback every rank keeps what the rounding removed from its own contribution to
+a name and adds it to that name's next tensor before rounding again, inside the same fusion pack
+(include/ddl_amd.h, DDL_ALLREDUCE_WIRE_FEEDBACK): nothing small is lost, it accumulates until it
+registers on the wire, and the sum of what was sent equals the sum of the true values.
+What it costs: one fp32 copy of every compressed gradient in device memory (the engine's residual,
+kept per request NAME until the communicator goes — so only for names that are stable from step to
+step, as the data-parallel wrapper's are; never with names made fresh per call), and a pack that
+moves 14 bytes per element instead of 6. What travels between the ranks is unchanged.
+When to reset: the residuals belong to the gradients' recent past. Call `reset_error_feedback()`
+after loading a checkpoint, and after a change of the loss scale by a large factor (the residuals
+were scaled by the old one).
 """
 from ddl.torch import cpp_backend as cb
 
@@ -19,22 +34,42 @@ class _Wire:
     def __init__(self, name: str, flag: int):
         self.name, self.flag = name, flag
 
+    @property
+    def feedback(self) -> bool:
+        return bool(self.flag & cb.WIRE_FEEDBACK)
+
     def __repr__(self):
         return f'Compression.{self.name}'
 
 
 class Compression:
     """`compression=` of allreduce_async, allreduce_async_batch, allreduce_gradient and the
-    data-parallel optimizer wrapper."""
+    data-parallel optimizer wrapper. The `_feedback` kinds keep an error-feedback residual per
+    request name (module docstring: one fp32 copy of every compressed gradient in device memory, a
+    14-byte-per-element pack instead of 6; `reset_error_feedback()` after loading a checkpoint or
+    a large change of the loss scale); allreduce_gradient does not take them."""
     none = _Wire('none', 0)
     fp16 = _Wire('fp16', cb.WIRE_FP16)
     bf16 = _Wire('bf16', cb.WIRE_BF16)
+    fp16_feedback = _Wire('fp16_feedback', cb.WIRE_FP16 | cb.WIRE_FEEDBACK)
+    bf16_feedback = _Wire('bf16_feedback', cb.WIRE_BF16 | cb.WIRE_FEEDBACK)
 
 
 def wire_flag(compression) -> int:
-    """The ddl_allreduce_wire flag of a `compression=` argument (None = Compression.none)."""
+    """The ddl_allreduce_wire flags of a `compression=` argument (None = Compression.none)."""
     if compression is None:
         return 0
     if not isinstance(compression, _Wire):
-        raise TypeError(f'compression must be Compression.none, .fp16 or .bf16, not {compression!r}')
+        raise TypeError('compression must be Compression.none, .fp16, .bf16, .fp16_feedback or .bf16_feedback, '
+                        f'not {compression!r}')
     return compression.flag
+
+
+def reset_error_feedback() -> None:
+    """Restart every error-feedback residual of this process from zero at its next use (raises the
+    engine's per-process `wire_feedback_epoch` by one). Call it after loading a checkpoint, or after
+    a change of the loss scale by a large factor: the residuals describe gradients that no longer
+    exist. Rank-local: nothing is communicated, the ranks need not call it together."""
+    lib = cb.CPPBackend.c_api()
+    cb.check(lib.ddl_set_config(b'wire_feedback_epoch', int(lib.ddl_get_config(b'wire_feedback_epoch')) + 1),
+             'ddl_set_config(wire_feedback_epoch)')

@@ -41,6 +41,7 @@ STATUS_NAMES = {0: 'OK', 1: 'COMM_ERROR', 2: 'ERROR_UNKNOWN', 3: 'INVALID_ARGUME
 STATUS_CONFIG_MISMATCH = 8
 OP_SUM, OP_AVG = 0, 1  # enum ddl_allreduce_op
 WIRE_FP16, WIRE_BF16 = 0x100, 0x200  # enum ddl_allreduce_wire: OR-ed into a keyed fp32 device request's op
+WIRE_FEEDBACK = 0x1000  # error feedback: only together with exactly one of the two wire flags
 MEMORY_DEVICE, MEMORY_HOST = 0, 1  # enum ddl_memory
 
 DONE_FN = ctypes.CFUNCTYPE(None, ctypes.c_int, ctypes.c_void_p)
@@ -171,6 +172,9 @@ class CPPBackend:
         sig('ddl_unpack', ci, ctypes.POINTER(vp), vp, ctypes.POINTER(sz), ci, vp)
         sig('ddl_unpack_ops', ci, ctypes.POINTER(vp), vp, ctypes.POINTER(sz), ctypes.POINTER(ci), ci, ci, ci, vp)
         sig('ddl_pack_cvt', ci, vp, ctypes.POINTER(vp), ctypes.POINTER(sz), ci, ci, vp)
+        sig('ddl_pack_cvt_fb', ci, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(sz), ci, ci, vp)
+        sig('ddl_testing_thread_fused_allreduce_wire_fb', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp),
+            ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(ci), ci, vp, ctypes.POINTER(sz))
         sig('ddl_unpack_cvt', ci, ctypes.POINTER(vp), vp, ctypes.POINTER(sz), ctypes.POINTER(ci), ci, ci, ci, vp)
         sig('ddl_testing_thread_fused_allreduce_wire', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp),
             ctypes.POINTER(sz), ctypes.POINTER(ci), ci, vp, ctypes.POINTER(sz))

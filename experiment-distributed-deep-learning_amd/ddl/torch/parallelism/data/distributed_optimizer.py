@@ -36,6 +36,16 @@ gradient travels and is summed as 16-bit values and comes back as fp32, converte
 fusion pack and unpack; the other gradients (other dtypes, CPU, sparse) are reduced as before. It
 composes with `fused_mean` (the mean of the widened sum, one fp32 rounding); without it the `div_`
 runs on the fp32 result. Off by default.
+
+`compression=Compression.fp16_feedback` / `Compression.bf16_feedback`: the same wire with error
+feedback — every rank keeps what the rounding removed from each of its gradients and adds it to
+that parameter's next gradient before rounding again, so small components accumulate until they
+register instead of being lost at every step. The request names are stable per parameter on both
+paths (step() and the `overlap_backward` hooks), which is what the engine's per-name residuals need.
+Cost: one fp32 copy of every compressed gradient in device memory, and a fusion pack that moves 14
+bytes per element instead of 6; what travels between the ranks is unchanged. Call
+`ddl.torch.compression.reset_error_feedback()` after loading a checkpoint and after a change of the
+loss scale by a large factor.
 """
 import contextlib
 import functools
@@ -198,7 +208,11 @@ def data_parallelism_distributed_optimizer_wrapper(
     the wrapper with the same value. fp16 OVERFLOWS: a gradient, or a partial sum over the ranks,
     above 65504 in magnitude becomes inf and one below 6e-8 becomes 0, so use fp16 only with a loss
     scale that keeps the gradients in range; bf16 has fp32's range (8 bits of precision) and is the
-    recommended choice for unscaled gradients."""
+    recommended choice for unscaled gradients. Compression.fp16_feedback / .bf16_feedback add error
+    feedback (module docstring): it costs one fp32 copy of every compressed gradient in device
+    memory and a pack of 14 instead of 6 bytes per element; reset it with
+    ddl.torch.compression.reset_error_feedback() after loading a checkpoint or a change of the loss
+    scale by a large factor."""
     opt_cls = optimizer.__class__
     assert issubclass(opt_cls, torch.optim.Optimizer)
     cls = type(opt_cls.__name__, (DataParallelismDistributedOptimizer, opt_cls), {})

@@ -101,13 +101,20 @@ def allreduce_gradient(tensor: torch.Tensor, communicator: Communicator = None,
     differ from torch's `div_`, which multiplies by the reciprocal, when the size is no power of two.
     `compression` (Compression.fp16 / .bf16; a dense fp32 device gradient at size > 1): the gradient
     goes through the keyed path and travels as 16-bit values (ddl.torch.compression); every other
-    gradient is reduced as without it.
+    gradient is reduced as without it. The error-feedback kinds (Compression.fp16_feedback /
+    .bf16_feedback) raise ValueError: the compressed path here makes a fresh request name per call,
+    and the engine keeps one residual per name, so every call would leak one — use
+    allreduce_async[_batch] or the optimizer wrapper, whose names are stable.
 
     Sparse gradient (torch sparse COO, the counterpart of TF's IndexedSlices, :26-30): the
     values and the indices are allgathered — every rank's rows in rank order — and the mean
     divides the values; duplicate indices stay uncoalesced, as IndexedSlices keeps them.
     """
     communicator = _comm(communicator)
+    if wire_flag(compression) & cb.WIRE_FEEDBACK:
+        raise ValueError(f'allreduce_gradient does not take {compression!r}: its compressed requests get a fresh '
+                         'name per call, which would leak one error-feedback residual per call; use allreduce_async '
+                         'with a stable name')
     if tensor.is_sparse:
         values = allgather(tensor._values(), communicator)
         if return_mean:
@@ -440,7 +447,12 @@ def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator 
     """Register a keyed allreduce (`op`: cb.OP_SUM, or cb.OP_AVG for the mean); returns a Handle.
     `compression` (Compression.fp16 / .bf16): a dense fp32 device tensor at size > 1 is sent and
     summed as 16-bit values and comes back as fp32 (ddl.torch.compression; every rank must pass the
-    same compression for a name); any other tensor is submitted as without it.
+    same compression for a name); any other tensor is submitted as without it. With
+    Compression.fp16_feedback / .bf16_feedback the engine also keeps what the rounding removed under
+    `name` and adds it to the next tensor submitted under that name (error feedback: one fp32 copy
+    of the tensor in device memory per distinct name until the communicator goes, so keep the names
+    stable from step to step; ddl.torch.compression.reset_error_feedback after loading a checkpoint
+    or a large change of the loss scale).
 
     `name` plays the role of the TF op name: the same name on every rank identifies the same
     gradient, and only one request per name may be pending (TensorCommunicateRequest.h:21).
@@ -474,7 +486,8 @@ def allreduce_async_batch(tensors, names, communicator: Communicator = None, out
     may be mixed (one submission per memory kind). `compression` (Compression.fp16 / .bf16) applies
     to the dense fp32 device tensors at size > 1 (ddl.torch.compression); the others are submitted
     uncompressed, so a mixed batch goes as one compressed and one plain submission. The handles
-    come back in the caller's order either way."""
+    come back in the caller's order either way. The error-feedback kinds as in `allreduce_async`:
+    one residual per name, so stable names."""
     import ctypes
     communicator = _comm(communicator)
     tensors = list(tensors)

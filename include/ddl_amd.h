@@ -82,7 +82,9 @@ enum ddl_allreduce_op { DDL_ALLREDUCE_OP_SUM = 0, DDL_ALLREDUCE_OP_AVG = 1 };
 /* Wire format of a keyed device allreduce of DDL_FLOAT tensors (MI355X extension, Horovod's
  * Compression.fp16): at most one flag, OR-ed into `op`. The gradients travel and are summed as
  * 16-bit values and come back as fp32 (see the data-plane section). */
-enum ddl_allreduce_wire { DDL_ALLREDUCE_WIRE_FP16 = 0x100, DDL_ALLREDUCE_WIRE_BF16 = 0x200 };
+enum ddl_allreduce_wire { DDL_ALLREDUCE_WIRE_FP16 = 0x100, DDL_ALLREDUCE_WIRE_BF16 = 0x200,
+                          /* error feedback: only OR-ed with exactly one of the two above */
+                          DDL_ALLREDUCE_WIRE_FEEDBACK = 0x1000 };
 
 typedef long long ddl_communicator_id;
 
@@ -170,7 +172,10 @@ int ddl_is_initialized(void);
  * DDL_QUEUE_ISOLATION seeds it; read when a communicator is created; local),
  * "fusion_pipeline_bytes" (keyed fusion plans above this run as a pack / allreduce / unpack
  * pipeline of sub-plans of at most this size; 0 = unpipelined), "one_rank_shortcut" (1: a
- * one-rank world skips the keyed data plane; 0: runs it, for tests), "pipeline_rounds" (1,
+ * one-rank world skips the keyed data plane; 0: runs it, for tests), "wire_feedback_epoch" (0,
+ * default; per process: a key's error-feedback residual — DDL_ALLREDUCE_WIRE_FEEDBACK, the data-plane
+ * section — restarts from zero when this differs from the value it was last written under: raise it
+ * after loading a checkpoint or after a change of the loss scale by a large factor), "pipeline_rounds" (1,
  * default: a completion thread fires a keyed round's done() calls as its plans land while the
  * engine thread negotiates the next round; 0: each round is waited for first), "reference_order" (1,
  * default: every allreduce sum equals the reference's MPI_Allreduce — MPICH 3.3.2 — bit for
@@ -253,7 +258,41 @@ void py_error(const char *log_str);
  * ddl_allreduce_batch or ddl_allreduce_host return DDL_STATUS_INVALID_ARGUMENT.
  * P = 1: with "one_rank_shortcut" 1 nothing is communicated and nothing is compressed — the result
  * is the input, bit for bit; with 0 the data plane runs and the result is the input round-tripped
- * through the wire type. */
+ * through the wire type.
+ *
+ * Error feedback (EF-SGD, 1-bit SGD): DDL_ALLREDUCE_WIRE_FEEDBACK, valid only OR-ed with exactly
+ * one of WIRE_FP16 / WIRE_BF16 on a keyed DDL_FLOAT device request (ddl_allreduce_submit,
+ * _submit_batch, _submit_mem, _submit_batch_mem). The rank keeps what the rounding removed from its
+ * own contribution to a key and adds it to the key's next input before rounding again, so nothing
+ * small is lost: it accumulates until it registers on the wire. Per element, with r the rank's
+ * residual for the key (zero the first time), all arithmetic in fp32, round-to-nearest-even,
+ * subnormals kept:
+ *     v  = g + r
+ *     w  = narrow(v)                          the wire value, the rounding rule above
+ *     r' = isfinite(widen(w)) ? v - widen(w) : 0
+ * w goes to the wire and r' replaces r; from there on the request is the compressed request above
+ * (sum in the wire dtype in MPICH's order for the plan's unpadded wire bytes, widen, AVG's
+ * quotient). v - widen(w) is exact in fp32 whenever widen(w) is finite, so the rule has one rounding
+ * (g + r) beyond the wire's own. A NaN or inf in v, or an overflow of the narrowing, clears the
+ * residual: it can never poison later steps. The rule is part of the fusion pack
+ * (csrc/pack.hip k_seg_cvt_pack_fb): no extra pass, 14 bytes moved per element against 6.
+ * The residual is owned by the engine: fp32, the request's element count, in device memory,
+ * found by the request's key, kept by the communicator until the communicator is destroyed.
+ * EVERY DISTINCT KEY THAT EVER CARRIED THE BIT HOLDS 4 BYTES PER ELEMENT UNTIL THEN: a caller that
+ * makes fresh key names per step must not set the bit.
+ * The bit changes nothing that is communicated, so it is rank-local like SUM / AVG: it is in no
+ * fusion group key, plan cut or negotiation, one pack launch may mix requests with and without it,
+ * and ranks that disagree about it get different numbers, never a hang.
+ * A key's residual restarts from zero when the key comes back with another element count, and
+ * when the per-process config "wire_feedback_epoch" differs from the value under which the
+ * residual was last written. A request of the key without the bit leaves the residual untouched
+ * and unused. A plan that fails may already have updated its residuals; that is not undone.
+ * Refusals, before anything is registered (the communicator works afterwards): the bit without a
+ * wire flag, with both wire flags, or on ddl_allreduce, ddl_allreduce_batch or ddl_allreduce_host
+ * returns DDL_STATUS_INVALID_ARGUMENT; with host memory or another dtype than DDL_FLOAT the wire
+ * flag's own refusals apply.
+ * P = 1: with "one_rank_shortcut" 1 nothing is touched and no residual is made; with 0 the data
+ * plane runs and the feedback applies. */
 /* recv = SUM over ranks of send (elementwise), bit for bit the reference's MPI_Allreduce (MPICH
  * 3.3.2's order) with reference_order 1. The schedule is the tuned one for the bucket's size
  * class: by default at P > 2 the direct reduce-scatter (slices of every chunk to every peer over

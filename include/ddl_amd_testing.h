@@ -132,6 +132,12 @@ int ddl_pack_cvt(void *dst, const void *const *srcs, const size_t *elements, int
                  void *hip_stream);
 int ddl_unpack_cvt(void *const *dsts, const void *src, const size_t *elements, const int *ops, int count,
                    int wire_dtype, int divisor, void *hip_stream);
+/* ddl_pack_cvt with error feedback (DDL_ALLREDUCE_WIRE_FEEDBACK; k_seg_cvt_pack_fb) on caller-owned
+ * residuals: residuals[i] = elements[i] fp32 values (4-byte aligned), added to segment i before the
+ * rounding and overwritten with what the rounding removed; NULL = segment i is converted as
+ * ddl_pack_cvt converts it. With every residual NULL the launch is ddl_pack_cvt's. */
+int ddl_pack_cvt_fb(void *dst, const void *const *srcs, void *const *residuals, const size_t *elements, int count,
+                    int wire_dtype, void *hip_stream);
 
 /* ---- single-GPU rehearsal of the ring schedule --------------------------------------- */
 /* Runs the exact per-rank ring schedule for `nranks` virtual ranks inside this process on
@@ -192,6 +198,13 @@ int ddl_testing_thread_fused_allreduce_ops(int nranks, int count, const void *co
 int ddl_testing_thread_fused_allreduce_wire(int nranks, int count, const void *const *srcs, void *const *dsts,
                                             const size_t *elements, const int *ops, int wire_dtype,
                                             void *hip_stream, size_t *subplans);
+/* The same with error feedback on caller-owned residuals: residuals[r * count + i] = rank r's
+ * residual of segment i (elements[i] fp32 values, or NULL = no feedback), handed to the plan as the
+ * keyed handler hands over its own (a sub-plan's piece takes its residual at the tensor's element
+ * offset). */
+int ddl_testing_thread_fused_allreduce_wire_fb(int nranks, int count, const void *const *srcs, void *const *dsts,
+                                               void *const *residuals, const size_t *elements, const int *ops,
+                                               int wire_dtype, void *hip_stream, size_t *subplans);
 /* Data movement of the thread worlds made from now on: rccl = 0 device copies (default); 1 every
  * matched send / receive pair goes through RcclTransport::group as a self send + self receive on
  * the RCCL loopback communicator (ddl_rccl_loopback_init first), posted on the receiver's stream
