@@ -243,7 +243,7 @@ public:
     SegmentCopier &operator=(const SegmentCopier &) = delete;
     // DDL_ALLREDUCE_OP_AVG (`ops[i]` per segment, `divisor` = the communicator's size, `dtype` a
     // float type): the scatter (dir 1) stores the quotient of the AVG segments' elements and copies
-    // the others — one launch of k_seg_div in place of k_seg_tiles; dir kDivInPlace divides the AVG
+    // the others — one launch of k_seg<DivOp> in place of k_seg<CopyOp>; dir kDivInPlace divides the AVG
     // segments where they are (`flat` unused, the other segments untouched). Without an AVG
     // segment, or with divisor 1, dir 0 / 1 are the plain copies and kDivInPlace posts nothing.
     static constexpr int kDivInPlace = 2;
@@ -253,12 +253,12 @@ public:
     // (DDL_FLOAT) elements, the flat buffer `wire_dtype` (DDL_HALF / DDL_BFLOAT16) ones. `wire_bytes[i]`
     // = segment i's bytes on the FLAT side (elements x 2), so offsets, tiles and flat_bytes are those
     // of run() on the wire stream; the tensor side is twice as long. dir 0: round to nearest even
-    // into the flat buffer (k_seg_cvt_pack); dir 1: widen, AVG segments divided by (float)divisor
-    // (k_seg_cvt_unpack). `residuals` (dir 0 only; parallel to `segs`, null entries allowed): error
+    // into the flat buffer (k_seg<CvtPackOp>); dir 1: widen, AVG segments divided by (float)divisor
+    // (k_seg<CvtUnpackOp>). `residuals` (dir 0 only; parallel to `segs`, null entries allowed): error
     // feedback (DDL_ALLREDUCE_WIRE_FEEDBACK) — segment i with residuals[i] != null packs
     // narrow(tensor + residual) and leaves what the rounding removed in residuals[i] (fp32, the
-    // segment's element count; k_seg_cvt_pack_fb). With no non-null residual of a non-empty segment
-    // the launch is k_seg_cvt_pack, unchanged.
+    // segment's element count; CvtPackOp<WIRE, true>). With no non-null residual of a non-empty
+    // segment the launch is the feedback-free CvtPackOp<WIRE, false>, unchanged.
     void run_cvt(int dir, void *flat, void *const *segs, const size_t *wire_bytes, int count, hipStream_t stream,
                  int src_dtype, int wire_dtype, int divisor = 1, const int *ops = nullptr,
                  void *const *residuals = nullptr);
@@ -270,7 +270,7 @@ private:
     struct Slot {
         void *host = nullptr, *dev = nullptr;
         size_t cap = 0;
-        void *idx = nullptr;  // first segment per span (k_span_index)
+        void *idx = nullptr;  // device tile -> segment map (k_tile_index): a byte or an int32 per tile
         size_t idx_cap = 0;
         hipEvent_t ready = nullptr;
     };

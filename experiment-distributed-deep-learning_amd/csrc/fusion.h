@@ -43,7 +43,7 @@ public:
     // pack -> allreduce -> unpack of srcs[i] -> dsts[i] (bytes[i] each) on `stream`, pipelined in
     // sub-plans above `cap` bytes (0: never). `ops` (one ddl_allreduce_op per segment, or null =
     // all SUM) with `divisor` = the communicator's size: the unpack of every (sub-)plan holding an
-    // AVG segment is the dividing unpack (pack.hip k_seg_div), which stores the quotients of those
+    // AVG segment is the dividing unpack (pack.hip k_seg<DivOp>), which stores the quotients of those
     // segments; the cuts, the packs and the allreduces do not depend on the ops.
     // `src_dtype` != 0 and != dtype (DDL_FLOAT over a 16-bit `dtype`: wire compression): the tensors
     // hold src_dtype elements, `bytes`, `cap`, the cuts and the allreduce are those of the WIRE stream
@@ -52,7 +52,7 @@ public:
     // `residuals` (a compressed plan only; one per segment, null entries = no feedback): the error
     // feedback residuals of DDL_ALLREDUCE_WIRE_FEEDBACK, fp32 arrays indexed like the tensors — a
     // sub-plan's piece takes its residual at the tensor's own element offset. The pack adds them in
-    // and rewrites them (k_seg_cvt_pack_fb); cuts, allreduces and unpacks do not depend on them.
+    // and rewrites them (k_seg<CvtPackOp<WIRE, true>>); cuts, allreduces and unpacks do not depend on them.
     void run(const std::vector<const void *> &srcs, const std::vector<void *> &dsts,
              const std::vector<size_t> &bytes, int dtype, size_t cap, hipStream_t stream, const Allreduce &ar,
              const std::vector<int> *ops = nullptr, int divisor = 1, int src_dtype = 0,

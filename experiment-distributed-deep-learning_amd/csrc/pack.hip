@@ -9,8 +9,9 @@
 // fused bucket keeps the ring's 16-byte vector alignment). The segment table lives in device
 // memory (uploaded with one async copy from a pinned staging table). Default mapping: every
 // segment is cut into 1 KiB tiles that restart at the segment start, one 64-lane workgroup per
-// tile, the tile's segment from a one-byte-per-tile index built on the device (k_tile_index,
-// k_seg_tiles).
+// tile, the tile's segment from a one-byte-per-tile index built on the device (k_tile_index).
+// One kernel, k_seg, walks the tiles for every operation; what an operation does to a 16-byte
+// unit and to a single element is its Op struct (CopyOp, DivOp, CvtPackOp, CvtUnpackOp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -32,24 +33,22 @@ struct SegDesc {
     uint64_t ptr;   // segment address (tensor side)
     uint64_t off;   // offset in the flat buffer (256-byte aligned)
     uint64_t len;   // bytes
-    uint32_t vec;   // 1 if ptr is 16-byte aligned (16-byte units), else byte copies
+    uint32_t vec;   // kSegVec: ptr is 16-byte aligned (16-byte units, else elements); kSegAvg
     uint32_t tile0; // segment-aligned tiling: index of the segment's first tile
 };
+constexpr uint32_t kSegVec = 1, kSegAvg = 2;
 
-// Misaligned or partial chunk: byte copy (rare; kept out of line so the unrolled main loop
-// stays small).
-__device__ inline void copy_bytes(char *dst, const char *src, uint32_t m) {
-    for (uint32_t k = 0; k < m; ++k) dst[k] = src[k];
-}
-
-// dir 0: gather segments -> flat; dir 1: scatter flat -> segments.
-// Segment-aligned tiling: every segment is cut into tiles of THREADS * 16 * kIters bytes that
-// restart at the segment start, so a tile never crosses a segment and its workgroup needs no
-// per-chunk search: tile_seg[t] (k_tile_index: one thread per tile, binary search of the
-// tile0 column) names the segment, one scalar descriptor load gives ptr / off / len, and lane l
-// moves bytes [16 l + it * THREADS * 16, ...) of the tile. Small tiles (1 KiB per 64-lane
-// workgroup) keep the chunks in flight a compact window of each stream (tools/copy_tune.hip:
-// 1R+1W copies reach 6.5 TB/s with 1-2 KiB per workgroup vs 5.3 TB/s with 64 KiB).
+// Segment-aligned tiling: every segment is cut into tiles of kSegTile bytes that restart at the
+// segment start, so a tile never crosses a segment and its workgroup needs no per-chunk search:
+// the tile index (k_tile_index: one thread per tile, binary search of the tile0 column) names
+// the segment, one scalar descriptor load gives ptr / off / len, and lane l moves bytes
+// [16 l, 16 l + 16) of the tile. Small tiles keep the chunks in flight a compact window of each
+// stream (tools/copy_tune.hip: 1R+1W copies reach 6.5 TB/s with 1-2 KiB per workgroup vs 5.3 TB/s
+// with 64 KiB). One 1 KiB tile per 64-lane workgroup: the r01 tile-shape measurement (C5 bucket
+// set, pack / unpack) had 6.10 / 6.37 TB/s for it against 6.09 / 6.29 for 2 KiB tiles of 128 lanes
+// and 5.74 / 6.30 for 4 KiB tiles of 128 lanes x 2 chunks; the span kernel with an in-kernel
+// segment search (2-64 KiB spans) 4.5-6.0. Other shapes are tried in tools/copy_tune.hip.
+constexpr uint64_t kSegTile = 1024;
 // Tile -> segment map, compact: the dispatcher deals workgroups round-robin over the 8 XCDs,
 // each with its own L2, so every 128-byte line of a per-tile index is fetched by all 8 (r01: an
 // int32 per tile cost +3.2 % HBM traffic on the C5 set). The map is therefore one byte per tile,
@@ -74,83 +73,82 @@ __global__ void __launch_bounds__(256) k_tile_index(const SegDesc *__restrict__ 
     else static_cast<int *>(map)[t] = lo;
 }
 
-template <int DIR, int kIters, int THREADS, bool NARROW>
-__global__ void __launch_bounds__(THREADS) k_seg_tiles(char *flat, const SegDesc *__restrict__ d,
-                                                       const uint32_t *__restrict__ blk_base,
-                                                       const void *__restrict__ map) {
-    constexpr uint64_t kTile = (uint64_t)THREADS * 16 * kIters;
+// the byte is read as its aligned dword (a scalar load; a byte load would go through the vector
+// memory path and delay the whole tile)
+template <bool NARROW>
+__device__ inline int tile_segment(unsigned tile, const uint32_t *__restrict__ blk_base, const void *__restrict__ map) {
+    return NARROW ? (int)(blk_base[tile / kIdxBlock] +
+                          ((static_cast<const uint32_t *>(map)[tile / 4] >> (8 * (tile % 4))) & 0xffu))
+                  : static_cast<const int *>(map)[tile];
+}
+
+// The tile walk of every operation. An Op says what happens to the data and nothing about where:
+//   kUnit             bytes of SegDesc::len per element
+//   Op(flat, sd, seg, a...)   the segment's addresses; `a` are the launch's extra arguments
+//   vector()          may the lanes move whole 16-byte units (else the tile goes element by element)
+//   vec(b)            the 16-byte unit at byte b of the segment (bytes as SegDesc::len counts them)
+//   elem(e)           element e of the segment
+// Element granular at the edges: a misaligned segment and a segment's last partial unit go element
+// by element (the host guarantees whole, aligned elements), never byte by byte unless kUnit is 1.
+template <class Op, bool NARROW, class... A>
+__global__ void __launch_bounds__(64) k_seg(char *flat, const SegDesc *__restrict__ d,
+                                            const uint32_t *__restrict__ blk_base, const void *__restrict__ map,
+                                            A... a) {
+    constexpr uint64_t kUnit = Op::kUnit;
     const unsigned tile = blockIdx.x;
-    // the byte is read as its aligned dword (a scalar load; a byte load would go through the
-    // vector memory path and delay the whole tile)
-    const int seg = NARROW ? (int)(blk_base[tile / kIdxBlock] +
-                                   ((static_cast<const uint32_t *>(map)[tile / 4] >> (8 * (tile % 4))) & 0xffu))
-                           : static_cast<const int *>(map)[tile];
+    const int seg = tile_segment<NARROW>(tile, blk_base, map);
     const SegDesc sd = d[seg];
-    const uint64_t base = (uint64_t)(tile - sd.tile0) * kTile;  // tile start inside the segment
-    char *fl = flat + sd.off;
-    char *tp = reinterpret_cast<char *>(sd.ptr);
-    if (!sd.vec) {  // misaligned tensor: bytes
-        for (uint64_t b = base + threadIdx.x; b < sd.len && b < base + kTile; b += THREADS) {
-            if (DIR == 0) fl[b] = tp[b];
-            else tp[b] = fl[b];
-        }
+    const Op op(flat, sd, seg, a...);
+    const uint64_t base = (uint64_t)(tile - sd.tile0) * kSegTile;  // tile start inside the segment
+    if (!op.vector()) {
+        const uint64_t end = (sd.len < base + kSegTile ? sd.len : base + kSegTile) / kUnit;
+        for (uint64_t e = base / kUnit + threadIdx.x; e < end; e += 64) op.elem(e);
         return;
     }
-    u32x4 v[kIters];
-#pragma unroll
-    for (int it = 0; it < kIters; ++it) {
-        const uint64_t b = base + (uint64_t)it * THREADS * 16 + threadIdx.x * 16;
-        if (b + 16 <= sd.len)
-            v[it] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>((DIR == 0 ? tp : fl) + b));
-    }
-#pragma unroll
-    for (int it = 0; it < kIters; ++it) {
-        const uint64_t b = base + (uint64_t)it * THREADS * 16 + threadIdx.x * 16;
-        if (b + 16 <= sd.len) {
-            __builtin_nontemporal_store(v[it], reinterpret_cast<u32x4 *>((DIR == 0 ? fl : tp) + b));
-        } else if (b < sd.len) {  // the segment's last partial 16 bytes
-            const uint32_t m = (uint32_t)(sd.len - b);
-            if (DIR == 0) copy_bytes(fl + b, tp + b, m);
-            else copy_bytes(tp + b, fl + b, m);
-        }
+    const uint64_t b = base + threadIdx.x * 16;
+    if (b + 16 <= sd.len) {
+        op.vec(b);
+    } else if (b < sd.len) {  // the segment's last partial 16 bytes
+        for (uint64_t e = b / kUnit; e < sd.len / kUnit; ++e) op.elem(e);
     }
 }
 
-// one 1 KiB tile per 64-lane workgroup (kSegTile): the r01 tile-shape measurement (C5 bucket
-// set, pack / unpack) had 6.10 / 6.37 TB/s for it against 6.09 / 6.29 for 2 KiB tiles of 128 lanes
-// and 5.74 / 6.30 for 4 KiB tiles of 128 lanes x 2 chunks; the span kernel with an in-kernel
-// segment search (2-64 KiB spans) 4.5-6.0
-constexpr uint64_t kSegTile = 1024;
-template <int DIR, bool NARROW>
-void launch_dir(dim3 g, hipStream_t stream, char *fl, const SegDesc *dd, const uint32_t *db, const void *map) {
-    hipLaunchKernelGGL((k_seg_tiles<DIR, 1, 64, NARROW>), g, dim3(64), 0, stream, fl, dd, db, map);
+template <class Op, class... A>
+void launch(bool narrow, dim3 g, hipStream_t stream, char *fl, const SegDesc *dd, const uint32_t *db, const void *map,
+            A... a) {
+    if (narrow) hipLaunchKernelGGL((k_seg<Op, true, A...>), g, dim3(64), 0, stream, fl, dd, db, map, a...);
+    else hipLaunchKernelGGL((k_seg<Op, false, A...>), g, dim3(64), 0, stream, fl, dd, db, map, a...);
 }
 
-void launch_tiles(int dir, bool narrow, dim3 g, hipStream_t stream, char *fl, const SegDesc *dd, const uint32_t *db,
-                  const void *map) {
-    if (dir == 0) {
-        if (narrow) launch_dir<0, true>(g, stream, fl, dd, db, map);
-        else launch_dir<0, false>(g, stream, fl, dd, db, map);
-    } else {
-        if (narrow) launch_dir<1, true>(g, stream, fl, dd, db, map);
-        else launch_dir<1, false>(g, stream, fl, dd, db, map);
+// ---- the plain copies ---------------------------------------------------------------------------
+// DIR 0: gather segments -> flat; DIR 1: scatter flat -> segments. Bytes.
+template <int DIR> struct CopyOp {
+    static constexpr uint32_t kUnit = 1;
+    char *fl, *tp;
+    bool v;
+    __device__ CopyOp(char *flat, const SegDesc &sd, int)
+        : fl(flat + sd.off), tp(reinterpret_cast<char *>(sd.ptr)), v((sd.vec & kSegVec) != 0) {}
+    __device__ bool vector() const { return v; }
+    __device__ void vec(uint64_t b) const {
+        const u32x4 x = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>((DIR == 0 ? tp : fl) + b));
+        __builtin_nontemporal_store(x, reinterpret_cast<u32x4 *>((DIR == 0 ? fl : tp) + b));
     }
-}
+    __device__ void elem(uint64_t e) const {
+        if (DIR == 0) fl[e] = tp[e];
+        else tp[e] = fl[e];
+    }
+};
 
 // ---- the dividing scatter (DDL_ALLREDUCE_OP_AVG) ------------------------------------------------
-// k_seg_div: k_seg_tiles<1>'s mapping (segment-aligned 1 KiB tiles, the same index, 64 lanes) with
-// the mean's quotient in the store: the elements of a segment flagged kSegAvg (bit 1 of
-// SegDesc::vec; bit 0 stays "16-byte aligned") leave as q(x, P), the others unchanged. The source
-// is the flat buffer (the dividing unpack) or, with flat == nullptr, the segment itself (in place:
-// every lane reads and writes its own bytes only). Element granular throughout: a misaligned
-// tensor and a segment's last partial 16 bytes go element by element (the dtype guarantees element
-// alignment), never byte by byte — a quotient needs whole elements.
+// DivOp: the scatter with the mean's quotient in the store: the elements of a segment flagged
+// kSegAvg leave as q(x, P), the others unchanged. The source is the flat buffer (the dividing
+// unpack) or, with flat == nullptr, the segment itself (in place: every lane reads and writes its
+// own bytes only). A quotient needs whole elements, so kUnit is the dtype's size.
 // q: fp32 / fp64 the correctly rounded IEEE quotient by (float)P / (double)P (hipcc's default
 // correctly rounded division; subnormals kept, kernel mode float_denorm_mode_32 = 3); fp16 / bf16
 // widened to fp32, divided, rounded to nearest even into the type — what numpy and torch CPU
 // compute. No reciprocal multiply anywhere: at P = 3, 5, 6, 7 it differs in the last bit for
 // about a third of the values.
-constexpr uint32_t kSegVec = 1, kSegAvg = 2;
 enum DivType : int { kDivF32 = 0, kDivF64 = 1, kDivF16 = 2, kDivBF16 = 3 };
 
 template <int DT> struct DivTraits;
@@ -180,37 +178,24 @@ template <> struct DivTraits<kDivBF16> {
     }
 };
 
-template <int DT, bool NARROW>
-__global__ void __launch_bounds__(64) k_seg_div(const char *flat, const SegDesc *__restrict__ d,
-                                                const uint32_t *__restrict__ blk_base,
-                                                const void *__restrict__ map, double divisor) {
+template <int DT> struct DivOp {
     using Tr = DivTraits<DT>;
     using T = typename Tr::T;
-    constexpr uint32_t kPer = 16 / sizeof(T);
+    static constexpr uint32_t kUnit = sizeof(T);
+    static constexpr uint32_t kPer = 16 / sizeof(T);
     union Vec {
         u32x4 v;
         T e[kPer];
     };
-    const unsigned tile = blockIdx.x;
-    const int seg = NARROW ? (int)(blk_base[tile / kIdxBlock] +
-                                   ((static_cast<const uint32_t *>(map)[tile / 4] >> (8 * (tile % 4))) & 0xffu))
-                           : static_cast<const int *>(map)[tile];
-    const SegDesc sd = d[seg];
-    const typename Tr::D dv = (typename Tr::D)divisor;
-    const bool avg = (sd.vec & kSegAvg) != 0;
-    const uint64_t base = (uint64_t)(tile - sd.tile0) * 1024;  // tile start inside the segment
-    char *tp = reinterpret_cast<char *>(sd.ptr);
-    const char *sp = flat ? flat + sd.off : tp;
-    if (!(sd.vec & kSegVec)) {  // misaligned tensor: elements
-        const uint64_t end = sd.len < base + 1024 ? sd.len : base + 1024;
-        for (uint64_t b = base + threadIdx.x * sizeof(T); b + sizeof(T) <= end; b += 64 * sizeof(T)) {
-            const T x = *reinterpret_cast<const T *>(sp + b);
-            *reinterpret_cast<T *>(tp + b) = avg ? Tr::q(x, dv) : x;
-        }
-        return;
-    }
-    const uint64_t b = base + threadIdx.x * 16;
-    if (b + 16 <= sd.len) {
+    char *tp;
+    const char *sp;
+    typename Tr::D dv;
+    bool avg, v;
+    __device__ DivOp(const char *flat, const SegDesc &sd, int, double divisor)
+        : tp(reinterpret_cast<char *>(sd.ptr)), sp(flat ? flat + sd.off : tp), dv((typename Tr::D)divisor),
+          avg((sd.vec & kSegAvg) != 0), v((sd.vec & kSegVec) != 0) {}
+    __device__ bool vector() const { return v; }
+    __device__ void vec(uint64_t b) const {
         Vec x;
         x.v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(sp + b));
         if (avg) {
@@ -218,46 +203,27 @@ __global__ void __launch_bounds__(64) k_seg_div(const char *flat, const SegDesc 
             for (uint32_t k = 0; k < kPer; ++k) x.e[k] = Tr::q(x.e[k], dv);
         }
         __builtin_nontemporal_store(x.v, reinterpret_cast<u32x4 *>(tp + b));
-    } else if (b < sd.len) {  // the segment's last partial 16 bytes: elements
-        for (uint64_t o = b; o + sizeof(T) <= sd.len; o += sizeof(T)) {
-            const T x = *reinterpret_cast<const T *>(sp + o);
-            *reinterpret_cast<T *>(tp + o) = avg ? Tr::q(x, dv) : x;
-        }
     }
-}
-
-template <int DT>
-void launch_div_dt(bool narrow, dim3 g, hipStream_t stream, const char *fl, const SegDesc *dd, const uint32_t *db,
-                   const void *map, double divisor) {
-    if (narrow) hipLaunchKernelGGL((k_seg_div<DT, true>), g, dim3(64), 0, stream, fl, dd, db, map, divisor);
-    else hipLaunchKernelGGL((k_seg_div<DT, false>), g, dim3(64), 0, stream, fl, dd, db, map, divisor);
-}
-
-void launch_div(int dtype, bool narrow, dim3 g, hipStream_t stream, const char *fl, const SegDesc *dd,
-                const uint32_t *db, const void *map, double divisor) {
-    switch (dtype) {
-        case DDL_FLOAT: launch_div_dt<kDivF32>(narrow, g, stream, fl, dd, db, map, divisor); break;
-        case DDL_DOUBLE: launch_div_dt<kDivF64>(narrow, g, stream, fl, dd, db, map, divisor); break;
-        case DDL_HALF: launch_div_dt<kDivF16>(narrow, g, stream, fl, dd, db, map, divisor); break;
-        case DDL_BFLOAT16: launch_div_dt<kDivBF16>(narrow, g, stream, fl, dd, db, map, divisor); break;
-        default: fail(DDL_STATUS_UNSUPPORTED_DTYPE, std::string("AVG is not defined for ") + dtype_name(dtype));
+    __device__ void elem(uint64_t e) const {
+        const T x = reinterpret_cast<const T *>(sp)[e];
+        reinterpret_cast<T *>(tp)[e] = avg ? Tr::q(x, dv) : x;
     }
-}
+};
 
 // ---- the converting copies (ddl_allreduce_wire: fp32 tensors, 16-bit flat buffer) -----------------
-// k_seg_cvt_pack / k_seg_cvt_unpack: k_seg_tiles' mapping with the tiles defined on the WIRE side.
-// SegDesc::len / off and the 1 KiB tile count wire bytes (512 elements), so the segment table, the
-// tile index and flat_bytes are those of a plain copy of the wire stream; the tensor side of a tile
-// is 2 KiB of fp32. A lane handles 8 elements: two 16-byte fp32 vectors on the tensor side, one
-// 16-byte wire vector on the flat side (6 bytes moved per element against the plain copy's 8).
+// CvtPackOp / CvtUnpackOp: the tiles are defined on the WIRE side. SegDesc::len / off and the 1 KiB
+// tile count wire bytes (512 elements), so the segment table, the tile index and flat_bytes are
+// those of a plain copy of the wire stream; the tensor side of a tile is 2 KiB of fp32. A lane
+// handles 8 elements: two 16-byte fp32 vectors on the tensor side, one 16-byte wire vector on the
+// flat side (6 bytes moved per element against the plain copy's 8); vec(b) takes the wire byte b
+// of the lane's vector, the tensor's byte 2b.
 // Pack: round to nearest even — the plain fptrunc, which hipcc lowers for gfx950 to v_cvt_pk_f16_f32
 // (the kernel's rounding mode, nearest even; NOT the round-toward-zero v_cvt_pkrtz_f16_f32; overflow
 // gives inf, subnormals are kept: the kernel's fp16 denormal mode) and to v_cvt_pk_bf16_f32, the
 // hardware's packed RNE conversion (profiles/wire_compress/kernel_resource_usage.txt); a NaN stays a
-// NaN in both. Unpack: widen (exact) and, for a kSegAvg segment,
-// the correctly rounded fp32 quotient by (float)P — true division, as k_seg_div. Element granular
-// at the edges like k_seg_div: a tensor that is only 4-byte aligned and a segment's last partial
-// vector go element by element.
+// NaN in both. Unpack: widen (exact) and, for a kSegAvg segment, the correctly rounded fp32 quotient
+// by (float)P — true division, as DivOp. A tensor that is only 4-byte aligned and a segment's last
+// partial vector go element by element.
 enum WireType : int { kWireF16 = 0, kWireBF16 = 1 };
 template <int WIRE> struct WireTraits;
 template <> struct WireTraits<kWireF16> {
@@ -270,61 +236,19 @@ template <> struct WireTraits<kWireBF16> {
     static __device__ inline T narrow(float x) { return (T)x; }
     static __device__ inline float widen(T x) { return (float)x; }
 };
-
-template <bool NARROW>
-__device__ inline int tile_segment(unsigned tile, const uint32_t *__restrict__ blk_base, const void *__restrict__ map) {
-    return NARROW ? (int)(blk_base[tile / kIdxBlock] +
-                          ((static_cast<const uint32_t *>(map)[tile / 4] >> (8 * (tile % 4))) & 0xffu))
-                  : static_cast<const int *>(map)[tile];
-}
-
-template <int WIRE, bool NARROW>
-__global__ void __launch_bounds__(64) k_seg_cvt_pack(char *flat, const SegDesc *__restrict__ d,
-                                                     const uint32_t *__restrict__ blk_base,
-                                                     const void *__restrict__ map) {
-    using Tr = WireTraits<WIRE>;
-    using T = typename Tr::T;
-    union In {
-        u32x4 v;
-        float e[4];
-    };
-    union Out {
-        u32x4 v;
-        T e[8];
-    };
-    const unsigned tile = blockIdx.x;
-    const SegDesc sd = d[tile_segment<NARROW>(tile, blk_base, map)];
-    const uint64_t base = (uint64_t)(tile - sd.tile0) * 1024;  // tile start inside the segment, wire bytes
-    T *fl = reinterpret_cast<T *>(flat + sd.off);
-    const float *tp = reinterpret_cast<const float *>(sd.ptr);
-    if (!(sd.vec & kSegVec)) {  // tensor only 4-byte aligned: elements
-        const uint64_t end = (sd.len < base + 1024 ? sd.len : base + 1024) / sizeof(T);
-        for (uint64_t e = base / sizeof(T) + threadIdx.x; e < end; e += 64) fl[e] = Tr::narrow(tp[e]);
-        return;
-    }
-    const uint64_t b = base + threadIdx.x * 16;  // wire byte of the lane's vector; the tensor's byte 2b
-    if (b + 16 <= sd.len) {
-        const u32x4 *src = reinterpret_cast<const u32x4 *>(tp + b / sizeof(T));
-        In lo, hi;
-        lo.v = __builtin_nontemporal_load(src);
-        hi.v = __builtin_nontemporal_load(src + 1);
-        Out o;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            o.e[k] = Tr::narrow(lo.e[k]);
-            o.e[4 + k] = Tr::narrow(hi.e[k]);
-        }
-        __builtin_nontemporal_store(o.v, reinterpret_cast<u32x4 *>(flat + sd.off + b));
-    } else if (b < sd.len) {  // the segment's last partial vector: elements
-        for (uint64_t e = b / sizeof(T); e < sd.len / sizeof(T); ++e) fl[e] = Tr::narrow(tp[e]);
-    }
-}
+union F32x4 {
+    u32x4 v;
+    float e[4];
+};
+template <class T> union Wire8 {
+    u32x4 v;
+    T e[8];
+};
 
 // ---- the converting pack with error feedback (DDL_ALLREDUCE_WIRE_FEEDBACK) -----------------------
-// k_seg_cvt_pack_fb: k_seg_cvt_pack's mapping (the same segment table, tile index, 1 KiB wire tiles,
-// 64 lanes, 8 elements per lane) plus one table of residual addresses, res[seg] (0: the segment is
-// converted as k_seg_cvt_pack converts it). Per element of a segment with a residual r (fp32, the
-// segment's element count, indexed like the tensor):
+// CvtPackOp<WIRE, true>: the converting pack plus one table of residual addresses, res[seg] (0: the
+// segment is converted as CvtPackOp<WIRE, false> converts it). Per element of a segment with a
+// residual r (fp32, the segment's element count, indexed like the tensor):
 //     v = g + r;  w = narrow(v);  r' = isfinite(widen(w)) ? v - widen(w) : 0
 // w goes to the flat buffer, r' replaces r. One fp32 rounding (g + r, nearest even, subnormals kept)
 // beyond the wire's own: v - widen(w) is exact whenever widen(w) is finite. A NaN or inf in v, or
@@ -335,7 +259,7 @@ __global__ void __launch_bounds__(64) k_seg_cvt_pack(char *flat, const SegDesc *
 // next read a whole step later); the residual LOADS are plain: with non-temporal loads of both read
 // streams the C5 set took 1.73 ms against 1.49-1.53 ms (profiles/wire_feedback/feedback_probe_nt_loads.json
 // against feedback_probe.json). Otherwise, and for a segment's last partial vector, element by
-// element.
+// element. FB = false takes no table and stays its own, smaller kernel.
 template <int WIRE>
 __device__ inline typename WireTraits<WIRE>::T feedback(float g, float &r) {
     using Tr = WireTraits<WIRE>;
@@ -346,52 +270,31 @@ __device__ inline typename WireTraits<WIRE>::T feedback(float g, float &r) {
     return w;
 }
 
-template <int WIRE, bool NARROW>
-__global__ void __launch_bounds__(64) k_seg_cvt_pack_fb(char *flat, const SegDesc *__restrict__ d,
-                                                        const uint32_t *__restrict__ blk_base,
-                                                        const void *__restrict__ map,
-                                                        const uint64_t *__restrict__ res) {
+template <int WIRE, bool FB> struct CvtPackOp {
     using Tr = WireTraits<WIRE>;
     using T = typename Tr::T;
-    union In {
-        u32x4 v;
-        float e[4];
-    };
-    union Out {
-        u32x4 v;
-        T e[8];
-    };
-    const unsigned tile = blockIdx.x;
-    const int seg = tile_segment<NARROW>(tile, blk_base, map);
-    const SegDesc sd = d[seg];
-    const uint64_t rp = res[seg];
-    const uint64_t base = (uint64_t)(tile - sd.tile0) * 1024;  // tile start inside the segment, wire bytes
-    T *fl = reinterpret_cast<T *>(flat + sd.off);
-    const float *tp = reinterpret_cast<const float *>(sd.ptr);
-    float *rs = reinterpret_cast<float *>(rp);
-    if (!(sd.vec & kSegVec) || (rp & 15u)) {  // tensor or residual only 4-byte aligned: elements
-        const uint64_t end = (sd.len < base + 1024 ? sd.len : base + 1024) / sizeof(T);
-        for (uint64_t e = base / sizeof(T) + threadIdx.x; e < end; e += 64) {
-            if (rs) {
-                float r = rs[e];
-                fl[e] = feedback<WIRE>(tp[e], r);
-                rs[e] = r;
-            } else {
-                fl[e] = Tr::narrow(tp[e]);
-            }
-        }
-        return;
-    }
-    const uint64_t b = base + threadIdx.x * 16;  // wire byte of the lane's vector; the tensor's byte 2b
-    if (b + 16 <= sd.len) {
+    static constexpr uint32_t kUnit = sizeof(T);
+    T *fl;
+    const float *tp;
+    float *rs;
+    bool v;
+    __device__ CvtPackOp(char *flat, const SegDesc &sd, int)
+        : fl(reinterpret_cast<T *>(flat + sd.off)), tp(reinterpret_cast<const float *>(sd.ptr)), rs(nullptr),
+          v((sd.vec & kSegVec) != 0) {}
+    __device__ CvtPackOp(char *flat, const SegDesc &sd, int seg, const uint64_t *__restrict__ res)
+        : fl(reinterpret_cast<T *>(flat + sd.off)), tp(reinterpret_cast<const float *>(sd.ptr)),
+          rs(reinterpret_cast<float *>(res[seg])),  // tensor or residual only 4-byte aligned: elements
+          v((sd.vec & kSegVec) != 0 && (res[seg] & 15u) == 0) {}
+    __device__ bool vector() const { return v; }
+    __device__ void vec(uint64_t b) const {
         const u32x4 *src = reinterpret_cast<const u32x4 *>(tp + b / sizeof(T));
-        In lo, hi;
+        F32x4 lo, hi;
         lo.v = __builtin_nontemporal_load(src);
         hi.v = __builtin_nontemporal_load(src + 1);
-        Out o;
-        if (rs) {
+        Wire8<T> o;
+        if (FB && rs) {
             u32x4 *rv = reinterpret_cast<u32x4 *>(rs + b / sizeof(T));
-            In rlo, rhi;
+            F32x4 rlo, rhi;
             rlo.v = rv[0];  // plain loads: measured faster than non-temporal ones (above)
             rhi.v = rv[1];
 #pragma unroll
@@ -408,53 +311,35 @@ __global__ void __launch_bounds__(64) k_seg_cvt_pack_fb(char *flat, const SegDes
                 o.e[4 + k] = Tr::narrow(hi.e[k]);
             }
         }
-        __builtin_nontemporal_store(o.v, reinterpret_cast<u32x4 *>(flat + sd.off + b));
-    } else if (b < sd.len) {  // the segment's last partial vector: elements
-        for (uint64_t e = b / sizeof(T); e < sd.len / sizeof(T); ++e) {
-            if (rs) {
-                float r = rs[e];
-                fl[e] = feedback<WIRE>(tp[e], r);
-                rs[e] = r;
-            } else {
-                fl[e] = Tr::narrow(tp[e]);
-            }
+        __builtin_nontemporal_store(o.v, reinterpret_cast<u32x4 *>(reinterpret_cast<char *>(fl) + b));
+    }
+    __device__ void elem(uint64_t e) const {
+        if (FB && rs) {
+            float r = rs[e];
+            fl[e] = feedback<WIRE>(tp[e], r);
+            rs[e] = r;
+        } else {
+            fl[e] = Tr::narrow(tp[e]);
         }
     }
-}
+};
 
-template <int WIRE, bool NARROW>
-__global__ void __launch_bounds__(64) k_seg_cvt_unpack(const char *flat, const SegDesc *__restrict__ d,
-                                                       const uint32_t *__restrict__ blk_base,
-                                                       const void *__restrict__ map, float divisor) {
+template <int WIRE> struct CvtUnpackOp {
     using Tr = WireTraits<WIRE>;
     using T = typename Tr::T;
-    union In {
-        u32x4 v;
-        T e[8];
-    };
-    union Out {
-        u32x4 v;
-        float e[4];
-    };
-    const unsigned tile = blockIdx.x;
-    const SegDesc sd = d[tile_segment<NARROW>(tile, blk_base, map)];
-    const bool avg = (sd.vec & kSegAvg) != 0;
-    const uint64_t base = (uint64_t)(tile - sd.tile0) * 1024;
-    const T *fl = reinterpret_cast<const T *>(flat + sd.off);
-    float *tp = reinterpret_cast<float *>(sd.ptr);
-    if (!(sd.vec & kSegVec)) {
-        const uint64_t end = (sd.len < base + 1024 ? sd.len : base + 1024) / sizeof(T);
-        for (uint64_t e = base / sizeof(T) + threadIdx.x; e < end; e += 64) {
-            const float x = Tr::widen(fl[e]);
-            tp[e] = avg ? x / divisor : x;
-        }
-        return;
-    }
-    const uint64_t b = base + threadIdx.x * 16;
-    if (b + 16 <= sd.len) {
-        In x;
-        x.v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(flat + sd.off + b));
-        Out lo, hi;
+    static constexpr uint32_t kUnit = sizeof(T);
+    const T *fl;
+    float *tp;
+    float divisor;
+    bool avg, v;
+    __device__ CvtUnpackOp(const char *flat, const SegDesc &sd, int, float dv)
+        : fl(reinterpret_cast<const T *>(flat + sd.off)), tp(reinterpret_cast<float *>(sd.ptr)), divisor(dv),
+          avg((sd.vec & kSegAvg) != 0), v((sd.vec & kSegVec) != 0) {}
+    __device__ bool vector() const { return v; }
+    __device__ void vec(uint64_t b) const {
+        Wire8<T> x;
+        x.v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(fl) + b));
+        F32x4 lo, hi;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             lo.e[k] = Tr::widen(x.e[k]);
@@ -470,44 +355,22 @@ __global__ void __launch_bounds__(64) k_seg_cvt_unpack(const char *flat, const S
         u32x4 *dst = reinterpret_cast<u32x4 *>(tp + b / sizeof(T));
         __builtin_nontemporal_store(lo.v, dst);
         __builtin_nontemporal_store(hi.v, dst + 1);
-    } else if (b < sd.len) {
-        for (uint64_t e = b / sizeof(T); e < sd.len / sizeof(T); ++e) {
-            const float x = Tr::widen(fl[e]);
-            tp[e] = avg ? x / divisor : x;
-        }
     }
-}
-
-template <int WIRE>
-void launch_cvt_wire(int dir, bool narrow, dim3 g, hipStream_t stream, char *fl, const SegDesc *dd, const uint32_t *db,
-                     const void *map, float divisor) {
-    if (dir == 0) {
-        if (narrow) hipLaunchKernelGGL((k_seg_cvt_pack<WIRE, true>), g, dim3(64), 0, stream, fl, dd, db, map);
-        else hipLaunchKernelGGL((k_seg_cvt_pack<WIRE, false>), g, dim3(64), 0, stream, fl, dd, db, map);
-    } else {
-        if (narrow) hipLaunchKernelGGL((k_seg_cvt_unpack<WIRE, true>), g, dim3(64), 0, stream, fl, dd, db, map, divisor);
-        else hipLaunchKernelGGL((k_seg_cvt_unpack<WIRE, false>), g, dim3(64), 0, stream, fl, dd, db, map, divisor);
+    __device__ void elem(uint64_t e) const {
+        const float x = Tr::widen(fl[e]);
+        tp[e] = avg ? x / divisor : x;
     }
-}
+};
 
-void launch_cvt(int wire, int dir, bool narrow, dim3 g, hipStream_t stream, char *fl, const SegDesc *dd,
-                const uint32_t *db, const void *map, float divisor) {
-    if (wire == DDL_HALF) launch_cvt_wire<kWireF16>(dir, narrow, g, stream, fl, dd, db, map, divisor);
-    else launch_cvt_wire<kWireBF16>(dir, narrow, g, stream, fl, dd, db, map, divisor);
-}
-
-template <int WIRE>
-void launch_cvt_fb_wire(bool narrow, dim3 g, hipStream_t stream, char *fl, const SegDesc *dd, const uint32_t *db,
-                        const void *map, const uint64_t *res) {
-    if (narrow) hipLaunchKernelGGL((k_seg_cvt_pack_fb<WIRE, true>), g, dim3(64), 0, stream, fl, dd, db, map, res);
-    else hipLaunchKernelGGL((k_seg_cvt_pack_fb<WIRE, false>), g, dim3(64), 0, stream, fl, dd, db, map, res);
-}
-
-void launch_cvt_fb(int wire, bool narrow, dim3 g, hipStream_t stream, char *fl, const SegDesc *dd, const uint32_t *db,
-                   const void *map, const uint64_t *res) {
-    if (wire == DDL_HALF) launch_cvt_fb_wire<kWireF16>(narrow, g, stream, fl, dd, db, map, res);
-    else launch_cvt_fb_wire<kWireBF16>(narrow, g, stream, fl, dd, db, map, res);
-}
+// What one run_ is, decided once: its kernel, its tables, its happens-before spans and its label.
+// kCvtUnpack and kCvtUnpackAvg share a kernel (the AVG segments carry kSegAvg).
+enum SegOp : int { kPack, kUnpack, kUnpackAvg, kDivide, kCvtPack, kCvtPackFb, kCvtUnpack, kCvtUnpackAvg };
+struct SegOpInfo {
+    const char *label;  // of the happens-before trace
+    bool gather;        // segments read, flat buffer written; else the segments written
+};
+constexpr SegOpInfo kSegOps[] = {{"pack", true},     {"unpack", false},     {"unpack avg", false}, {"divide", false},
+                                 {"pack cvt", true}, {"pack cvt fb", true}, {"unpack cvt", false}, {"unpack cvt avg", false}};
 
 }  // namespace
 
@@ -601,8 +464,11 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
         DDL_REQUIRE(!div || dir == 1, DDL_STATUS_INVALID_ARGUMENT, "the quotient belongs to the unpack");
     }
     DDL_REQUIRE((flat || dir == kDivInPlace) && segs && bytes, DDL_STATUS_INVALID_ARGUMENT, "null pack arguments");
+    const SegOp op = dir == kDivInPlace ? kDivide
+                     : wire ? (dir == 0 ? (residuals ? kCvtPackFb : kCvtPack) : div ? kCvtUnpackAvg : kCvtUnpack)
+                     : dir == 0 ? kPack : div ? kUnpackAvg : kUnpack;
     const size_t es = div ? dtype_size(dtype) : 1;
-    if (div && !wire) {
+    if (op == kUnpackAvg || op == kDivide) {
         DDL_REQUIRE(dtype == DDL_FLOAT || dtype == DDL_DOUBLE || dtype == DDL_HALF || dtype == DDL_BFLOAT16,
                     DDL_STATUS_UNSUPPORTED_DTYPE, "AVG is not defined for dtype " << dtype);
         for (int i = 0; i < count; ++i)
@@ -611,7 +477,7 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
     }
     // in place only the AVG segments have tiles (a SUM segment already is its result)
     std::vector<size_t> own;
-    if (dir == kDivInPlace) {
+    if (op == kDivide) {
         own.assign(bytes, bytes + count);
         for (int i = 0; i < count; ++i)
             if (ops[i] != DDL_ALLREDUCE_OP_AVG) own[i] = 0;
@@ -627,7 +493,7 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
     const size_t table = (size_t)count * sizeof(SegDesc);
     // descriptors, then the block bases, then (feedback pack) one residual address per segment
     const size_t rtab = (table + nblk * sizeof(uint32_t) + 7) & ~size_t(7);
-    const size_t need = residuals ? rtab + (size_t)count * sizeof(uint64_t) : table + nblk * sizeof(uint32_t);
+    const size_t need = op == kCvtPackFb ? rtab + (size_t)count * sizeof(uint64_t) : table + nblk * sizeof(uint32_t);
     if (need > sl.cap) {  // outgrown tables kept until ddl_finalize: no hipFree on a data path (engine.h)
         retire_host(sl.host);
         retire_device(sl.dev);
@@ -651,7 +517,7 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
         tl += (bytes[i] + seg_tile - 1) / seg_tile;
     }
     if (off == 0) return;
-    if (residuals) {
+    if (op == kCvtPackFb) {
         uint64_t *rt = reinterpret_cast<uint64_t *>(static_cast<char *>(sl.host) + rtab);
         for (int i = 0; i < count; ++i) rt[i] = bytes[i] ? reinterpret_cast<uint64_t>(residuals[i]) : 0;
     }
@@ -681,31 +547,55 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
         const dim3 ig((unsigned)((tiles + 255) / 256)), g((unsigned)tiles);
         if (narrow) hipLaunchKernelGGL(k_tile_index<true>, ig, dim3(256), 0, stream, dd, count, (uint64_t)tiles, db, sl.idx);
         else hipLaunchKernelGGL(k_tile_index<false>, ig, dim3(256), 0, stream, dd, count, (uint64_t)tiles, db, sl.idx);
-        if (residuals)
-            launch_cvt_fb(wire, narrow, g, stream, fl, dd, db, sl.idx,
-                          reinterpret_cast<const uint64_t *>(static_cast<char *>(sl.dev) + rtab));
-        else if (wire) launch_cvt(wire, dir, narrow, g, stream, fl, dd, db, sl.idx, (float)divisor);
-        else if (div) launch_div(dtype, narrow, g, stream, fl, dd, db, sl.idx, (double)divisor);
-        else launch_tiles(dir, narrow, g, stream, fl, dd, db, sl.idx);
+        const bool f16 = wire == DDL_HALF;  // of the converting copies: else bf16 (run_cvt)
+        switch (op) {
+            case kPack: launch<CopyOp<0>>(narrow, g, stream, fl, dd, db, sl.idx); break;
+            case kUnpack: launch<CopyOp<1>>(narrow, g, stream, fl, dd, db, sl.idx); break;
+            case kUnpackAvg:
+            case kDivide: {
+                const double dv = (double)divisor;
+                switch (dtype) {
+                    case DDL_FLOAT: launch<DivOp<kDivF32>>(narrow, g, stream, fl, dd, db, sl.idx, dv); break;
+                    case DDL_DOUBLE: launch<DivOp<kDivF64>>(narrow, g, stream, fl, dd, db, sl.idx, dv); break;
+                    case DDL_HALF: launch<DivOp<kDivF16>>(narrow, g, stream, fl, dd, db, sl.idx, dv); break;
+                    case DDL_BFLOAT16: launch<DivOp<kDivBF16>>(narrow, g, stream, fl, dd, db, sl.idx, dv); break;
+                    default: fail(DDL_STATUS_UNSUPPORTED_DTYPE, std::string("AVG is not defined for ") + dtype_name(dtype));
+                }
+                break;
+            }
+            case kCvtPack:
+                if (f16) launch<CvtPackOp<kWireF16, false>>(narrow, g, stream, fl, dd, db, sl.idx);
+                else launch<CvtPackOp<kWireBF16, false>>(narrow, g, stream, fl, dd, db, sl.idx);
+                break;
+            case kCvtPackFb: {
+                const uint64_t *res = reinterpret_cast<const uint64_t *>(static_cast<char *>(sl.dev) + rtab);
+                if (f16) launch<CvtPackOp<kWireF16, true>>(narrow, g, stream, fl, dd, db, sl.idx, res);
+                else launch<CvtPackOp<kWireBF16, true>>(narrow, g, stream, fl, dd, db, sl.idx, res);
+                break;
+            }
+            case kCvtUnpack:
+            case kCvtUnpackAvg:
+                if (f16) launch<CvtUnpackOp<kWireF16>>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor);
+                else launch<CvtUnpackOp<kWireBF16>>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor);
+                break;
+        }
     }
     DDL_HIP(hipGetLastError());
     DDL_HIP(hipEventRecord(sl.ready, stream));
     if (dep::on()) {  // happens-before trace (deptrace.h): the segments and the flat buffer
         std::vector<dep::Access> acc;
-        if (flat) acc.push_back(dir == 0 ? dep::wr(flat, off) : dep::rd(flat, off));
+        const bool gather = kSegOps[op].gather;
+        if (op != kDivide) acc.push_back(gather ? dep::wr(flat, off) : dep::rd(flat, off));
         const size_t widen = wire ? dtype_size(dtype) / dtype_size(wire) : 1;  // the tensor side in its own bytes
         for (int i = 0; i < count; ++i)
             if (bytes[i])
-                acc.push_back(dir == 0 ? dep::rd(segs[i], bytes[i] * widen) : dep::wr(segs[i], bytes[i] * widen));
-        for (int i = 0; i < count && residuals; ++i)
+                acc.push_back(gather ? dep::rd(segs[i], bytes[i] * widen) : dep::wr(segs[i], bytes[i] * widen));
+        for (int i = 0; i < count && op == kCvtPackFb; ++i)
             if (bytes[i] && residuals[i]) {  // read and written: both, so the race check sees either side
                 acc.push_back(dep::rd(residuals[i], bytes[i] * widen));
                 acc.push_back(dep::wr(residuals[i], bytes[i] * widen));
             }
-        dep::op(stream,
-                wire ? (dir == 0 ? (residuals ? "pack cvt fb" : "pack cvt") : div ? "unpack cvt avg" : "unpack cvt")
-                     : dir == 0 ? "pack" : dir == 1 ? (div ? "unpack avg" : "unpack") : "divide",
-                std::move(acc));
+        dep::op(stream, kSegOps[op].label, std::move(acc));
     }
 }
 

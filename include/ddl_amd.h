@@ -244,7 +244,7 @@ void py_error(const char *log_str);
  * unpadded WIRE bytes); the 16-bit sum is widened to fp32, which is exact; with AVG the widened sum
  * is divided by (float)P with the correctly rounded fp32 quotient (one rounding fewer than a 16-bit
  * AVG). Every step is what numpy / torch CPU compute. The conversions are part of the fusion pack
- * and unpack kernels (csrc/pack.hip k_seg_cvt_pack / k_seg_cvt_unpack): no extra pass over the
+ * and unpack kernels (csrc/pack.hip k_seg<CvtPackOp> / k_seg<CvtUnpackOp>): no extra pass over the
  * tensors; the fusion threshold and the pipeline cuts count wire bytes, and a compressed request
  * always goes through the fusion buffer, also alone in its plan.
  * Unlike SUM / AVG the wire IS communicated: it is a property of a key that every rank must agree
@@ -275,7 +275,7 @@ void py_error(const char *log_str);
  * quotient). v - widen(w) is exact in fp32 whenever widen(w) is finite, so the rule has one rounding
  * (g + r) beyond the wire's own. A NaN or inf in v, or an overflow of the narrowing, clears the
  * residual: it can never poison later steps. The rule is part of the fusion pack
- * (csrc/pack.hip k_seg_cvt_pack_fb): no extra pass, 14 bytes moved per element against 6.
+ * (csrc/pack.hip k_seg<CvtPackOp<WIRE, true>>): no extra pass, 14 bytes moved per element against 6.
  * The residual is owned by the engine: fp32, the request's element count, in device memory,
  * found by the request's key, kept by the communicator until the communicator is destroyed.
  * EVERY DISTINCT KEY THAT EVER CARRIED THE BIT HOLDS 4 BYTES PER ELEMENT UNTIL THEN: a caller that

@@ -116,14 +116,14 @@ int ddl_reduce_fold_batch(int count, void *const *outs, const void *const *as, c
 int ddl_pack(void *dst, const void *const *srcs, const size_t *bytes, int count, void *hip_stream);
 int ddl_unpack(void *const *dsts, const void *src, const size_t *bytes, int count,
                void *hip_stream);
-/* The dividing unpack (DDL_ALLREDUCE_OP_AVG's kernel, csrc/pack.hip k_seg_div): as ddl_unpack, but
+/* The dividing unpack (DDL_ALLREDUCE_OP_AVG's kernel, csrc/pack.hip k_seg<DivOp>): as ddl_unpack, but
  * the elements (of `dtype`, a float type) of every segment with ops[i] == DDL_ALLREDUCE_OP_AVG are
  * stored as their quotient by `divisor`; the other segments are copied. src == NULL: in place —
  * every AVG segment is divided where it is, the others are not touched. */
 int ddl_unpack_ops(void *const *dsts, const void *src, const size_t *bytes, const int *ops, int count, int dtype,
                    int divisor, void *hip_stream);
 /* The converting pack / unpack of the wire compression (ddl_allreduce_wire; csrc/pack.hip
- * k_seg_cvt_pack / k_seg_cvt_unpack). wire_dtype = DDL_HALF or DDL_BFLOAT16; the tensors hold
+ * k_seg<CvtPackOp> / k_seg<CvtUnpackOp>). wire_dtype = DDL_HALF or DDL_BFLOAT16; the tensors hold
  * elements[i] fp32 values (4-byte aligned), segment i of the flat buffer its elements[i] wire values
  * at the running sum of the 256-byte-rounded wire lengths. _pack_cvt rounds to nearest even;
  * _unpack_cvt widens and, where ops[i] == DDL_ALLREDUCE_OP_AVG, divides by (float)divisor
@@ -132,7 +132,7 @@ int ddl_pack_cvt(void *dst, const void *const *srcs, const size_t *elements, int
                  void *hip_stream);
 int ddl_unpack_cvt(void *const *dsts, const void *src, const size_t *elements, const int *ops, int count,
                    int wire_dtype, int divisor, void *hip_stream);
-/* ddl_pack_cvt with error feedback (DDL_ALLREDUCE_WIRE_FEEDBACK; k_seg_cvt_pack_fb) on caller-owned
+/* ddl_pack_cvt with error feedback (DDL_ALLREDUCE_WIRE_FEEDBACK; k_seg<CvtPackOp<WIRE, true>>) on caller-owned
  * residuals: residuals[i] = elements[i] fp32 values (4-byte aligned), added to segment i before the
  * rounding and overwritten with what the rounding removed; NULL = segment i is converted as
  * ddl_pack_cvt converts it. With every residual NULL the launch is ddl_pack_cvt's. */

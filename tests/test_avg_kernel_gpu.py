@@ -1,4 +1,4 @@
-"""The dividing unpack kernel (csrc/pack.hip k_seg_div) on its own, through ddl_unpack_ops: the
+"""The dividing unpack kernel (csrc/pack.hip k_seg<DivOp>) on its own, through ddl_unpack_ops: the
 quotient of DDL_ALLREDUCE_OP_AVG in the store of the fusion scatter, flat -> tensors and in place.
 
 Expected values are the inputs divided on the CPU (numpy; torch CPU for bf16, _avg_helpers.quotient):

@@ -1,5 +1,5 @@
 """Every 16-bit pattern through the two-input reduce, the N-input folds and the converting pack
-(csrc/reduce_kernels.hip, csrc/pack.hip k_seg_cvt_pack), in all their forms, plus an edge table for
+(csrc/reduce_kernels.hip, csrc/pack.hip k_seg<CvtPackOp>), in all their forms, plus an edge table for
 fp32 / fp64 and one schedule-level check per 16-bit type.
 
 The inputs are the sets of tests/_edge_helpers.py (every pattern against 26 partners: subnormals,

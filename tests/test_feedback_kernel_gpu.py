@@ -1,4 +1,4 @@
-"""The converting pack with error feedback (csrc/pack.hip k_seg_cvt_pack_fb) on its own, through
+"""The converting pack with error feedback (csrc/pack.hip k_seg<CvtPackOp<WIRE, true>>) on its own, through
 ddl_pack_cvt_fb with caller-owned residuals, for both wire types.
 
 Expected values are the CPU model's (_feedback_helpers.step: v = g + r in fp32, the CPU's cast,

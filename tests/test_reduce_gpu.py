@@ -164,7 +164,8 @@ def test_pack_unpack_layouts(lib, gpu, case):
         offs.append(o)
         o += s + (int(rng.integers(1, 16)) if case == 'unaligned' else 0)
     total = sum((s + 255) // 256 * 256 for s in sizes)
-    fused = torch.zeros(max(total, 1), dtype=torch.uint8, device=gpu)
+    guard = 0xA5  # the flat buffer's padding between segments must stay as it was
+    fused = torch.full((max(total, 1),), guard, dtype=torch.uint8, device=gpu)
     P = ctypes.c_void_p * len(sizes)
     S = ctypes.c_size_t * len(sizes)
     stream = torch.cuda.current_stream().cuda_stream
@@ -175,12 +176,15 @@ def test_pack_unpack_layouts(lib, gpu, case):
     f, src, dst = fused.cpu().numpy(), pool.cpu().numpy(), outpool.cpu().numpy()
     off = 0
     covered = np.zeros(dst.size, dtype=bool)
+    packed = np.zeros(f.size, dtype=bool)
     for s, x in zip(sizes, offs):
         assert np.array_equal(f[off:off + s], src[x:x + s])
         assert np.array_equal(dst[x:x + s], src[x:x + s])
         covered[x:x + s] = True
+        packed[off:off + s] = True
         off += (s + 255) // 256 * 256
     assert not dst[~covered].any()  # unpack writes nothing between or past the segments
+    assert (f[~packed] == guard).all()  # pack writes nothing into the padding between the segments
 
 
 @pytest.mark.parametrize('dt', [1, 2, 3, 9, 14, 19, 23])

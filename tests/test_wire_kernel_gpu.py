@@ -1,4 +1,4 @@
-"""The converting fusion kernels (csrc/pack.hip k_seg_cvt_pack / k_seg_cvt_unpack) on their own,
+"""The converting fusion kernels (csrc/pack.hip k_seg<CvtPackOp> / k_seg<CvtUnpackOp>) on their own,
 through ddl_pack_cvt / ddl_unpack_cvt, for both wire types.
 
 Expected values are the CPU's casts (_wire_helpers.narrow / widen: numpy for fp16, torch CPU for

@@ -2,8 +2,8 @@
 
   python tools/avg_probe.py [--repeats 7] [--legs kernel,device,pinned]
 
-1. kernel: the plain unpack (ddl_unpack, k_seg_tiles) against the all-AVG dividing unpack
-   (ddl_unpack_ops, k_seg_div, divisor 3) on bench.py's C5 segment set (the same seed and size
+1. kernel: the plain unpack (ddl_unpack, k_seg<CopyOp<1>>) against the all-AVG dividing unpack
+   (ddl_unpack_ops, k_seg<DivOp>, divisor 3) on bench.py's C5 segment set (the same seed and size
    rule as bench.fusion_c5: 4096 sizes log-uniform in 4 KiB .. 4 MiB, 256-byte multiples), every
    segment fp32, fp16 or fp64. Bytes moved over time, and the ratio to plain.
 2. device: a one-rank world with one_rank_shortcut 0, 4096 fp32 device tensors of the C5 sizes

@@ -3,8 +3,8 @@
 
   python tools/feedback_probe.py [--repeats 9] [--out profiles/wire_feedback/feedback_probe.json]
 
-The converting pack (ddl_pack_cvt: k_seg_cvt_pack, 6 bytes moved per element) against the feedback
-pack (ddl_pack_cvt_fb: k_seg_cvt_pack_fb with a residual for every segment, 14 bytes per element:
+The converting pack (ddl_pack_cvt: k_seg<CvtPackOp<WIRE, false>>, 6 bytes moved per element) against the feedback
+pack (ddl_pack_cvt_fb: k_seg<CvtPackOp<WIRE, true>> with a residual for every segment, 14 bytes per element:
 the tensor and the residual read, the wire value and the residual written) of the SAME fp32 tensors,
 bench.py's C5 segment set (tools/wire_probe.py's c5_sizes: 4096 sizes log-uniform in 4 KiB .. 4 MiB,
 256-byte multiples; 2.4 GB of tensors and as much of residuals, so every launch streams its

@@ -3,9 +3,9 @@ profiles/wire_compress/).
 
   python tools/wire_probe.py [--repeats 9] [--legs kernel,step]
 
-1. kernel: the converting pack and unpack (ddl_pack_cvt / ddl_unpack_cvt: k_seg_cvt_pack,
-   k_seg_cvt_unpack with every segment AVG, divisor 3) against the plain pack and unpack
-   (ddl_pack / ddl_unpack: k_seg_tiles) of the SAME fp32 tensors, bench.py's C5 segment set (the same
+1. kernel: the converting pack and unpack (ddl_pack_cvt / ddl_unpack_cvt: k_seg<CvtPackOp>,
+   k_seg<CvtUnpackOp> with every segment AVG, divisor 3) against the plain pack and unpack
+   (ddl_pack / ddl_unpack: k_seg<CopyOp>) of the SAME fp32 tensors, bench.py's C5 segment set (the same
    seed and size rule as bench.fusion_c5: 4096 sizes log-uniform in 4 KiB .. 4 MiB, 256-byte
    multiples; 2.4 GB of tensors, so every launch streams its operands from HBM, far beyond the
    caches). Rates in algorithmic bytes: 8 per element for the plain copies, 6 for the converting

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Probe for the keyed host path over pinned host tensors: what HIP reports for
-torch's pinned CPU tensors, and how fast the fusion pack / unpack kernels (k_seg_tiles) move the
+torch's pinned CPU tensors, and how fast the fusion pack / unpack kernels (k_seg<CopyOp>) move the
 C5 bucket set when they read and write those tensors directly over PCIe (no host memcpy),
 next to the DMA engines' rate for one large pinned buffer.
 
