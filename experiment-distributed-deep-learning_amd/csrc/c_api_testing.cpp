@@ -360,6 +360,51 @@ int ddl_reduce_fold_batch(int count, void *const *outs, const void *const *as, c
     });
 }
 
+namespace {
+void check_kernel_op(int op) {
+    DDL_REQUIRE(op == DDL_ALLREDUCE_OP_SUM || op_is_minmax(op), DDL_STATUS_INVALID_ARGUMENT,
+                "reduce kernel op " << op << " (SUM = 0, MIN = 3, MAX = 4)");
+}
+}  // namespace
+
+int ddl_reduce_op2(void *out, const void *a, const void *b, size_t elements, int dtype, int op, void *hip_stream) {
+    return guarded([&] {
+        check_kernel_op(op);
+        SegTable t;
+        t.count = 1;
+        t.a[0] = a;
+        t.b[0] = b;
+        t.out[0] = out;
+        t.n[0] = elements;
+        launch_sum2(t, dtype, as_stream(hip_stream), -1, op);
+    });
+}
+
+int ddl_reduce_fold_batch_op(int count, void *const *outs, const void *const *as, const void *const *ins, int nb,
+                             const size_t *elements, int dtype, int op, void *hip_stream) {
+    return guarded([&] {
+        check_kernel_op(op);
+        DDL_REQUIRE(count >= 1 && count <= kMaxFoldBatch && outs && as && ins && elements, DDL_STATUS_INVALID_ARGUMENT,
+                    "fold batch of " << count << " (1.." << kMaxFoldBatch << ")");
+        DDL_REQUIRE(nb >= 1 && nb <= kMaxInputs, DDL_STATUS_INVALID_ARGUMENT, "fold inputs " << nb);
+        std::vector<SegTableN> t(count);
+        for (int p = 0; p < count; ++p) {
+            t[p].a = as[p];
+            t[p].out = outs[p];
+            t[p].n = elements[p];
+            t[p].nb = nb;
+            for (int i = 0; i < nb; ++i) t[p].b[i] = ins[(size_t)p * nb + i];
+        }
+        launch_sumN_batch(t.data(), count, dtype, as_stream(hip_stream), op);
+    });
+}
+
+int ddl_reduce_fold_op(void *out, const void *a, const void *const *ins, int nb, size_t elements, int dtype, int op,
+                       void *hip_stream) {
+    const size_t n = elements;
+    return ddl_reduce_fold_batch_op(1, &out, &a, ins, nb, &n, dtype, op, hip_stream);
+}
+
 int ddl_reduce_fold(void *out, const void *a, const void *const *ins, int nb, size_t elements, int dtype,
                     void *hip_stream) {
     return ddl_reduce_fold_ordered(out, a, ins, nb, elements, dtype, kFoldLeft, hip_stream);
@@ -429,7 +474,10 @@ int ddl_unpack_cvt(void *const *dsts, const void *src, const size_t *elements, c
     return guarded([&] {
         DDL_REQUIRE(count >= 0 && (count == 0 || (src && dsts && elements)) && divisor >= 1, DDL_STATUS_INVALID_ARGUMENT,
                     "bad unpack_cvt args");
-        for (int i = 0; ops && i < count; ++i) check_allreduce_op(ops[i], DDL_FLOAT);
+        for (int i = 0; ops && i < count; ++i) {
+            check_allreduce_op(ops[i], DDL_FLOAT);
+            DDL_REQUIRE(!op_is_minmax(ops[i]), DDL_STATUS_INVALID_ARGUMENT, "MIN / MAX take no wire");
+        }
         const std::vector<size_t> b = wire_bytes(elements, count, wire_dtype);
         std::lock_guard<std::mutex> g(abi_copier_mu());
         abi_copier().run_cvt(1, const_cast<void *>(src), dsts, b.data(), count, as_stream(hip_stream), DDL_FLOAT,
@@ -444,7 +492,8 @@ int ddl_local_ring_allreduce(int nranks, const void *const *sends, void *const *
         check_allreduce_op(op, dtype);
         DDL_REQUIRE(sends && recvs, DDL_STATUS_INVALID_ARGUMENT, "null buffer arrays");
         (void)current_device();
-        local_world(nranks).allreduce(sends, recvs, elements, dtype, as_stream(hip_stream), config().ring());
+        local_world(nranks).allreduce(sends, recvs, elements, dtype, as_stream(hip_stream), config().ring(),
+                                      reduce_kind(op));
         if (op == DDL_ALLREDUCE_OP_AVG && nranks > 1 && elements) {  // every rank's result, one launch
             const std::vector<size_t> bytes(nranks, elements * dtype_size(dtype));
             const std::vector<int> ops(nranks, op);
@@ -564,7 +613,10 @@ int ddl_testing_thread_fused_allreduce_wire(int nranks, int count, const void *c
     return guarded([&] {
         DDL_REQUIRE(nranks >= 1 && nranks <= 64 && count >= 1 && srcs && dsts && elements, DDL_STATUS_INVALID_ARGUMENT,
                     "bad thread fused allreduce");
-        for (int i = 0; ops && i < count; ++i) check_allreduce_op(ops[i], DDL_FLOAT);
+        for (int i = 0; ops && i < count; ++i) {
+            check_allreduce_op(ops[i], DDL_FLOAT);
+            DDL_REQUIRE(!op_is_minmax(ops[i]), DDL_STATUS_INVALID_ARGUMENT, "MIN / MAX take no wire");
+        }
         const std::vector<size_t> b = wire_bytes(elements, count, wire_dtype);
         const size_t j = thread_world(nranks).fused_allreduce(srcs, dsts, b.data(), count, wire_dtype,
                                                               as_stream(hip_stream), config().ring(),
@@ -580,7 +632,10 @@ int ddl_testing_thread_fused_allreduce_wire_fb(int nranks, int count, const void
     return guarded([&] {
         DDL_REQUIRE(nranks >= 1 && nranks <= 64 && count >= 1 && srcs && dsts && residuals && elements,
                     DDL_STATUS_INVALID_ARGUMENT, "bad thread fused allreduce");
-        for (int i = 0; ops && i < count; ++i) check_allreduce_op(ops[i], DDL_FLOAT);
+        for (int i = 0; ops && i < count; ++i) {
+            check_allreduce_op(ops[i], DDL_FLOAT);
+            DDL_REQUIRE(!op_is_minmax(ops[i]), DDL_STATUS_INVALID_ARGUMENT, "MIN / MAX take no wire");
+        }
         const std::vector<size_t> b = wire_bytes(elements, count, wire_dtype);
         const size_t j = thread_world(nranks).fused_allreduce(srcs, dsts, b.data(), count, wire_dtype,
                                                               as_stream(hip_stream), config().ring(),

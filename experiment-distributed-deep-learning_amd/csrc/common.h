@@ -77,28 +77,36 @@ struct Error {
         }                                                 \
     } while (0)
 
-// The op of every allreduce entry point: SUM or AVG, AVG on float types only. Refused before
+inline bool op_is_minmax(int op) { return op == DDL_ALLREDUCE_OP_MIN || op == DDL_ALLREDUCE_OP_MAX; }
+// What the reduce and fold kernels of an allreduce with `op` compute (launch_sum2 / launch_sumN's
+// `op`): AVG is a SUM whose result is divided afterwards, MIN / MAX are themselves.
+inline int reduce_kind(int op) { return op_is_minmax(op) ? op : DDL_ALLREDUCE_OP_SUM; }
+
+// The op of every allreduce entry point: SUM, AVG (float types only), MIN or MAX. Refused before
 // anything is posted; the dtype is the same on every rank, so all ranks refuse together.
 inline void check_allreduce_op(int op, int dtype) {
-    DDL_REQUIRE(op == DDL_ALLREDUCE_OP_SUM || op == DDL_ALLREDUCE_OP_AVG, DDL_STATUS_INVALID_ARGUMENT,
-                "unknown allreduce op " << op << " (SUM = 0, AVG = 1)");
+    DDL_REQUIRE(op == DDL_ALLREDUCE_OP_SUM || op == DDL_ALLREDUCE_OP_AVG || op_is_minmax(op),
+                DDL_STATUS_INVALID_ARGUMENT, "unknown allreduce op " << op << " (SUM = 0, AVG = 1, MIN = 3, MAX = 4)");
     DDL_REQUIRE(op != DDL_ALLREDUCE_OP_AVG || dtype_size(dtype) == 0 || dtype_is_float(dtype),
                 DDL_STATUS_UNSUPPORTED_DTYPE, "AVG is not defined for " << dtype_name(dtype));
 }
 
-// The `op` of a keyed allreduce request: SUM / AVG in the low bits, optionally one
-// ddl_allreduce_wire format flag, optionally DDL_ALLREDUCE_WIRE_FEEDBACK with it. Returns the wire
-// dtype (DDL_HALF / DDL_BFLOAT16; 0 = uncompressed), leaves SUM / AVG in *base and the feedback bit
-// in *feedback. Refusals as ddl_amd.h lists them, before anything is registered.
+// The `op` of a keyed allreduce request: SUM / AVG / MIN / MAX in the low bits, with SUM / AVG
+// optionally one ddl_allreduce_wire format flag, optionally DDL_ALLREDUCE_WIRE_FEEDBACK with it.
+// Returns the wire dtype (DDL_HALF / DDL_BFLOAT16; 0 = uncompressed), leaves the op in *base and
+// the feedback bit in *feedback. Refusals as ddl_amd.h lists them, before anything is registered.
 inline int decode_keyed_op(int op, int dtype, bool host, int *base, bool *feedback) {
     constexpr int kWire = DDL_ALLREDUCE_WIRE_FP16 | DDL_ALLREDUCE_WIRE_BF16;
     *base = op & ~(kWire | DDL_ALLREDUCE_WIRE_FEEDBACK);
     *feedback = (op & DDL_ALLREDUCE_WIRE_FEEDBACK) != 0;
     const int w = op & kWire;
     DDL_REQUIRE(w != kWire, DDL_STATUS_INVALID_ARGUMENT, "both wire flags in allreduce op " << op);
-    DDL_REQUIRE(*base == DDL_ALLREDUCE_OP_SUM || *base == DDL_ALLREDUCE_OP_AVG, DDL_STATUS_INVALID_ARGUMENT,
+    DDL_REQUIRE(*base == DDL_ALLREDUCE_OP_SUM || *base == DDL_ALLREDUCE_OP_AVG || op_is_minmax(*base),
+                DDL_STATUS_INVALID_ARGUMENT,
                 "unknown allreduce op " << op << " (SUM = 0, AVG = 1, | WIRE_FP16 = 0x100 or WIRE_BF16 = 0x200, "
-                                                 "| WIRE_FEEDBACK = 0x1000 with one of them)");
+                                                 "| WIRE_FEEDBACK = 0x1000 with one of them; MIN = 3, MAX = 4)");
+    DDL_REQUIRE(!op_is_minmax(*base) || (!w && !*feedback), DDL_STATUS_INVALID_ARGUMENT,
+                "MIN / MAX take no wire flag (allreduce op " << op << ")");
     DDL_REQUIRE(w || !*feedback, DDL_STATUS_INVALID_ARGUMENT,
                 "WIRE_FEEDBACK without WIRE_FP16 or WIRE_BF16 in allreduce op " << op);
     if (!w) return 0;
@@ -177,7 +185,9 @@ struct SegTableN {
 };
 // fp32/fp64/int: one rounding per add in `order`; fp16/bf16 (no reference order: the reference
 // rejects them): accumulate in fp32 and round once at the end, whatever the order.
-void launch_sumN(const SegTableN &t, int dtype, hipStream_t stream);
+// `op`: DDL_ALLREDUCE_OP_SUM, or _MIN / _MAX (the element-wise IEEE 754-2019 minimum / maximum, the
+// integer order; associative, so `order` is not used).
+void launch_sumN(const SegTableN &t, int dtype, hipStream_t stream, int op = DDL_ALLREDUCE_OP_SUM);
 // Up to kMaxFoldBatch independent folds with the same input count and order in ONE launch
 // (blockIdx.y = problem): the grouped allreduce folds every bucket's slice of a tick together, so
 // 64 back-to-back 2 MiB fp16 chunks (C4) become 8 launches of 8 chunks instead of 64 latency-bound
@@ -187,7 +197,7 @@ struct FoldBatch {
     SegTableN t[kMaxFoldBatch];
     int count;
 };
-void launch_sumN_batch(const SegTableN *t, int count, int dtype, hipStream_t stream);
+void launch_sumN_batch(const SegTableN *t, int count, int dtype, hipStream_t stream, int op = DDL_ALLREDUCE_OP_SUM);
 
 // Reduce-kernel cache-policy / staging flags (bit set). kVariantDefault is what the engine uses;
 // the others exist for measurement (ddl_reduce_sum2_variant, bench.py, tools/reduce_tune.hip).
@@ -216,8 +226,9 @@ void set_testing_fold_variant(int v);  // ddl_testing_fold_variant: 4 / 5 forced
 int get_fold_form();
 
 // out = a + b for each segment; dtype-generic. Returns via fail() on bad arguments.
-// variant < 0 selects default_variant().
-void launch_sum2(const SegTable &t, int dtype, hipStream_t stream, int variant = -1);
+// variant < 0 selects default_variant(). `op` as launch_sumN's; MIN / MAX take the variants
+// default_variant and ring_variant choose, not the measurement-only ones.
+void launch_sum2(const SegTable &t, int dtype, hipStream_t stream, int variant = -1, int op = DDL_ALLREDUCE_OP_SUM);
 int device_cu_count();
 
 // Chunk boundaries [cut[i], cut[i + 1]) of a host-staged transfer of `total` bytes through

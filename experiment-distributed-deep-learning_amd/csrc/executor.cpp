@@ -143,7 +143,7 @@ void *RankResources::ensure_staging(size_t bytes, bool capturing) {
     return staging_;
 }
 
-double launch_tick_reduce(const Tick &tk, int dtype, hipStream_t stream) {
+double launch_tick_reduce(const Tick &tk, int dtype, hipStream_t stream, int kind) {
     const double es = (double)dtype_size(dtype);
     if (tk.multi) {
         // fold steps in order on the compute stream; consecutive independent steps of one shape
@@ -151,7 +151,7 @@ double launch_tick_reduce(const Tick &tk, int dtype, hipStream_t stream) {
         double bytes = 0;
         std::vector<SegTableN> batch;
         auto flush = [&] {
-            if (!batch.empty()) launch_sumN_batch(batch.data(), (int)batch.size(), dtype, stream);
+            if (!batch.empty()) launch_sumN_batch(batch.data(), (int)batch.size(), dtype, stream, kind);
             batch.clear();
         };
         auto meets = [es](const void *p, uint64_t pn, const void *q, uint64_t qn) {
@@ -174,7 +174,7 @@ double launch_tick_reduce(const Tick &tk, int dtype, hipStream_t stream) {
         flush();
         return bytes;
     }
-    launch_sum2(tk.reduce, dtype, stream, ring_variant());
+    launch_sum2(tk.reduce, dtype, stream, ring_variant(), kind);
     double elems = 0;
     for (int s = 0; s < tk.reduce.count; ++s) elems += (double)tk.reduce.n[s];
     return 3.0 * elems * es;
@@ -256,7 +256,7 @@ void RingExecutor::allreduce(const void *in, void *out, size_t n, int dtype, hip
     }
     void *staging = res_.ensure_staging(program_staging_elems(n, es, size_, cfg) * es, stream_capturing(user));
     build_program(prog_, rank_, size_, in, out, staging, n, dtype, cfg);
-    run_(dtype, user);
+    run_(dtype, user, reduce_kind(op));
     if (avg) {
         const size_t bytes = n * es;
         divider_.run(SegmentCopier::kDivInPlace, nullptr, &out, &bytes, 1, user, dtype, size_, &op);
@@ -279,7 +279,7 @@ void RingExecutor::allreduce_batch(const void *const *in, void *const *out, cons
     void *staging = res_.ensure_staging(std::max<size_t>(1, batch_staging_elems(n, count, es, size_, cfg)) * es,
                                         stream_capturing(user));
     build_batch_program(prog_, rank_, size_, in, out, n, count, staging, dtype, cfg);
-    run_(dtype, user);
+    run_(dtype, user, reduce_kind(op));
     if (avg && count > 0) {  // one launch over every bucket's result
         std::vector<size_t> bytes(count);
         for (int b = 0; b < count; ++b) bytes[b] = n[b] * es;
@@ -370,7 +370,7 @@ void Poster::finish() {
                                                hipStreamSetCaptureDependencies));
 }
 
-void RingExecutor::run_(int dtype, hipStream_t user) {
+void RingExecutor::run_(int dtype, hipStream_t user, int kind) {
     if (prog_.ticks.empty()) return;
     DDL_TRACE("executor rank " << rank_ << "/" << size_ << " run: " << prog_.ticks.size() << " ticks, user " << (void *)user);
     // Eagerly the program forks from the caller's stream onto the comm / compute streams and joins
@@ -427,7 +427,7 @@ void RingExecutor::run_(int dtype, hipStream_t user) {
                 DDL_HIP(hipEventRecord(tp.first, compute));
             }
             const hipStream_t cs = p.on(compute);
-            const double bytes = launch_tick_reduce(tk, dtype, cs);
+            const double bytes = launch_tick_reduce(tk, dtype, cs, kind);
             p.posted(compute);
             if (dep::on()) dep::op(cs, dep_label(tk.multi ? "fold" : "reduce", rank_, t), tick_reduce_access(tk, dtype));
             if (timing) {

@@ -186,7 +186,9 @@ public:
     // `op` DDL_ALLREDUCE_OP_AVG: once the program has joined `user`, one in-place launch of the
     // dividing kernel (SegmentCopier::kDivInPlace) over the result on `user` alone — one segment,
     // or one per bucket for the batch; nothing at size 1. Refused while `user` is captured (the
-    // copier's table upload and slot events are not capturable).
+    // copier's table upload and slot events are not capturable). DDL_ALLREDUCE_OP_MIN / _MAX: every
+    // reduce and fold launch of the program combines with the minimum / maximum (reduce_kind); the
+    // program, its bytes and its launches are SUM's, so it is capturable like SUM.
     void allreduce(const void *in, void *out, size_t n, int dtype, hipStream_t user,
                    const RingConfig &cfg, int op = DDL_ALLREDUCE_OP_SUM);
     // `count` buckets of one dtype as one grouped program (build_batch_program): one group and
@@ -204,7 +206,8 @@ public:
 
 private:
     // posts prog_ on the streams, forked from / joined to user (graph-safe when user is captured)
-    void run_(int dtype, hipStream_t user);
+    // (`kind`: what the program's reduce / fold launches compute, reduce_kind(op))
+    void run_(int dtype, hipStream_t user, int kind = DDL_ALLREDUCE_OP_SUM);
 
     int rank_, size_;
     std::unique_ptr<Transport> transport_;
@@ -221,8 +224,8 @@ private:
 int last_reduce_at_or_before(const RingProgram &p, int w);
 
 // Launches a tick's reduce (2-input ring step or N-input direct fold) on `stream`; returns its
-// algorithmic HBM bytes.
-double launch_tick_reduce(const Tick &tk, int dtype, hipStream_t stream);
+// algorithmic HBM bytes. `kind`: DDL_ALLREDUCE_OP_SUM, _MIN or _MAX (reduce_kind).
+double launch_tick_reduce(const Tick &tk, int dtype, hipStream_t stream, int kind = DDL_ALLREDUCE_OP_SUM);
 // The byte ranges a tick's reduce reads and writes, and a trace label (deptrace.h).
 std::vector<dep::Access> tick_reduce_access(const Tick &tk, int dtype);
 std::string dep_label(const char *what, int rank, size_t tick);

@@ -44,7 +44,8 @@ public:
     // sub-plans above `cap` bytes (0: never). `ops` (one ddl_allreduce_op per segment, or null =
     // all SUM) with `divisor` = the communicator's size: the unpack of every (sub-)plan holding an
     // AVG segment is the dividing unpack (pack.hip k_seg<DivOp>), which stores the quotients of those
-    // segments; the cuts, the packs and the allreduces do not depend on the ops.
+    // segments; the cuts, the packs and the allreduces do not depend on the ops. (A MIN / MAX plan
+    // holds one kind only; its caller's `ar` reduces with that kind and the unpack copies.)
     // `src_dtype` != 0 and != dtype (DDL_FLOAT over a 16-bit `dtype`: wire compression): the tensors
     // hold src_dtype elements, `bytes`, `cap`, the cuts and the allreduce are those of the WIRE stream
     // in `dtype` (a tensor's offset at a cut is the wire offset scaled by the element sizes), and

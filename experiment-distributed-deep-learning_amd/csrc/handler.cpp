@@ -470,7 +470,7 @@ void plan_slices(const Plan &p, const std::vector<Request> &reqs, const std::vec
 }
 // The op of every slice plan_slices visits, in its order: a request's SUM / AVG is rank-local and
 // applied where its segment is written out; it never enters the group key or the plan cuts (the wire
-// dtype of a compressed request, Request::wire, does: it is communicated).
+// dtype of a compressed request, Request::wire, and MIN / MAX do: they are communicated).
 std::vector<int> plan_ops(const Plan &p, const std::vector<Request> &reqs, const std::vector<size_t> &group) {
     std::vector<int> ops;
     for (size_t q = p.req_begin; q <= p.req_end; ++q) ops.push_back(reqs[group[q]].op);
@@ -527,13 +527,17 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
     // device ones. The wire dtype is the request's own dtype unless it is an fp32 request with a
     // wire flag (Request::wire), whose group comes right after the native group of that 16-bit
     // dtype — the same order on every rank, the wire being a property of the key. Groups of
-    // uncompressed requests are formed and ordered as without the flag.
-    std::map<std::tuple<int, int, int>, std::vector<size_t>> groups;
+    // uncompressed requests are formed and ordered as without the flag. The reduction kind (0 SUM /
+    // AVG, 1 MIN, 2 MAX) is communicated too — it is what the plan's allreduce computes — so MIN and
+    // MAX requests form groups of their own after the SUM / AVG group of the same dtype and memory;
+    // a round without them forms exactly the groups it formed before.
+    auto kind_rank = [](int op) { return op == DDL_ALLREDUCE_OP_MIN ? 1 : op == DDL_ALLREDUCE_OP_MAX ? 2 : 0; };
+    std::map<std::tuple<int, int, int, int>, std::vector<size_t>> groups;
     for (size_t i = 0; i < reqs.size(); ++i) {
         if (reqs[i].n == 0) dones.push_back(Done{kNoPlan, i, DDL_STATUS_OK});  // nothing to reduce
         else
             groups[std::make_tuple(reqs[i].wire ? reqs[i].wire : reqs[i].dtype, reqs[i].wire ? 1 : 0,
-                                   reqs[i].host ? 1 : 0)]
+                                   reqs[i].host ? 1 : 0, kind_rank(reqs[i].op))]
                 .push_back(i);
     }
     std::vector<hipEvent_t> waited;
@@ -541,6 +545,7 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
         const int dt = std::get<0>(g.first);  // what is communicated and summed
         const bool comp = std::get<1>(g.first) != 0;
         const bool host = std::get<2>(g.first) != 0;
+        const int kind = reduce_kind(reqs[g.second[0]].op);  // of the whole group: SUM, MIN or MAX
         const int sdt = comp ? DDL_FLOAT : dt;  // what the tensors hold
         // plans, the fusion threshold and the message size count wire bytes (es); the tensors'
         // slices their own (ses)
@@ -586,7 +591,7 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
                     // chunks of the padded stream either way, so ranks that differ in which
                     // outputs are pinned still issue the same collectives
                     auto coll = [&](void *d, size_t elems) {
-                        data_->allreduce(d, d, elems, dt, DDL_ALLREDUCE_OP_SUM, stream_, message);
+                        data_->allreduce(d, d, elems, dt, kind, stream_, message);
                     };
                     const auto t_check = std::chrono::steady_clock::now();
                     const bool mapped = config().host_zero_copy.load() && host_->mapped_dsts(segs);
@@ -629,7 +634,7 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
                                            : nullptr);
                 fp_.run(srcs, dsts, bytes, dt, (size_t)config().fusion_pipeline_bytes.load(), stream_,
                         [&](void *buf, size_t elems, size_t message) {
-                            data_->allreduce(buf, buf, elems, dt, DDL_ALLREDUCE_OP_SUM, stream_, message);
+                            data_->allreduce(buf, buf, elems, dt, kind, stream_, message);
                         },
                         &ops, data_->size(), sdt, resid.empty() ? nullptr : &res);
             }

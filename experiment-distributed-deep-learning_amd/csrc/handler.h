@@ -54,7 +54,7 @@ struct Request {
     void *out = nullptr;
     size_t n = 0;  // elements of `in`
     int dtype = 0;
-    int op = 0;                       // allreduce: SUM / AVG (the wire flag decoded into `wire`)
+    int op = 0;                       // allreduce: SUM / AVG / MIN / MAX (the wire flag decoded into `wire`)
     int wire = 0;                     // allreduce: wire dtype of a compressed fp32 request (0: its own dtype)
     bool feedback = false;            // allreduce: DDL_ALLREDUCE_WIRE_FEEDBACK (only with `wire`; rank-local)
     int root = 0;                     // broadcast: TensorBroadcastRequest::rootRank()

@@ -29,6 +29,7 @@
 
 #include <atomic>
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -108,6 +109,128 @@ struct Add<DDL_BFLOAT16> {
     }
     __device__ static S one(S a, S b) { return (__bf16)((float)a + (float)b); }
 };
+
+// ---- MIN / MAX (DDL_ALLREDUCE_OP_MIN / _MAX) -------------------------------------------------
+// The kernels below are instantiated on a combine id: the dtype alone for SUM (so every SUM
+// instance is the one it was), dtype | op << kOpShift for MIN / MAX, whose Add<> is the
+// element-wise IEEE 754-2019 minimum / maximum (NaN propagates and comes out quiet, -0 < +0,
+// subnormals kept, nothing rounded) or the integer order. Same tiles, descriptors, cache bits
+// and tails: only the combine differs.
+constexpr int kOpShift = 8;
+constexpr int cid(int dtype, int op) { return dtype | (op << kOpShift); }
+constexpr int cid_op(int id) { return id >> kOpShift; }
+
+using i32x4 = int __attribute__((ext_vector_type(4)));
+using i64x2 = long long __attribute__((ext_vector_type(2)));
+
+template <bool MAX, class T>
+__device__ __forceinline__ T fext(T a, T b) {  // v_maximum3_f32 / v_pk_maximum3_f16 (a, b, b) on gfx950
+    if constexpr (MAX) return __builtin_elementwise_maximum(a, b);
+    else return __builtin_elementwise_minimum(a, b);
+}
+template <bool MAX, class T>
+__device__ __forceinline__ T iext(T a, T b) {
+    if constexpr (MAX) return __builtin_elementwise_max(a, b);
+    else return __builtin_elementwise_min(a, b);
+}
+// fp64 has no v_maximum_f64 on gfx950: compare integer sort keys (the bits, the magnitude
+// inverted below zero, compared signed — numeric order with -0 < +0), a NaN on either side
+// gives the canonical quiet NaN.
+template <bool MAX>
+__device__ __forceinline__ double dext(double a, double b) {
+    const long long x = __builtin_bit_cast(long long, a), y = __builtin_bit_cast(long long, b);
+    constexpr long long kMag = 0x7fffffffffffffffll, kInf = 0x7ff0000000000000ll;
+    const long long kx = x ^ ((x >> 63) & kMag), ky = y ^ ((y >> 63) & kMag);
+    const long long r = (MAX ? kx > ky : kx < ky) ? x : y;
+    const bool nan = (x & kMag) > kInf || (y & kMag) > kInf;
+    return __builtin_bit_cast(double, nan ? 0x7ff8000000000000ll : r);
+}
+// two bf16 per dword, each widened exactly to fp32 (its bits in the high half): the result is one
+// of the inputs, or a quiet fp32 NaN whose high half is a quiet bf16 NaN, so the high half is exact
+template <bool MAX>
+__device__ __forceinline__ unsigned int bext_pair(unsigned int a, unsigned int b) {
+    const float lo = fext<MAX>(__builtin_bit_cast(float, a << 16), __builtin_bit_cast(float, b << 16));
+    const float hi = fext<MAX>(__builtin_bit_cast(float, a & 0xffff0000u), __builtin_bit_cast(float, b & 0xffff0000u));
+    return (__builtin_bit_cast(unsigned int, lo) >> 16) | (__builtin_bit_cast(unsigned int, hi) & 0xffff0000u);
+}
+
+template <int DT, bool MAX>
+struct MinMax;
+template <bool MAX>
+struct MinMax<DDL_FLOAT, MAX> {
+    using S = float;
+    __device__ static u32x4 vec(u32x4 a, u32x4 b) {
+        return __builtin_bit_cast(u32x4, fext<MAX>(__builtin_bit_cast(f32x4, a), __builtin_bit_cast(f32x4, b)));
+    }
+    __device__ static S one(S a, S b) { return fext<MAX>(a, b); }
+};
+template <bool MAX>
+struct MinMax<DDL_DOUBLE, MAX> {
+    using S = double;
+    __device__ static u32x4 vec(u32x4 a, u32x4 b) {
+        const f64x2 x = __builtin_bit_cast(f64x2, a), y = __builtin_bit_cast(f64x2, b);
+        return __builtin_bit_cast(u32x4, f64x2{dext<MAX>(x.x, y.x), dext<MAX>(x.y, y.y)});
+    }
+    __device__ static S one(S a, S b) { return dext<MAX>(a, b); }
+};
+template <bool MAX>
+struct MinMax<DDL_INT32, MAX> {
+    using S = int;
+    __device__ static u32x4 vec(u32x4 a, u32x4 b) {
+        return __builtin_bit_cast(u32x4, iext<MAX>(__builtin_bit_cast(i32x4, a), __builtin_bit_cast(i32x4, b)));
+    }
+    __device__ static S one(S a, S b) { return iext<MAX>(a, b); }
+};
+template <bool MAX>
+struct MinMax<DDL_INT64, MAX> {
+    using S = long long;
+    __device__ static u32x4 vec(u32x4 a, u32x4 b) {
+        return __builtin_bit_cast(u32x4, iext<MAX>(__builtin_bit_cast(i64x2, a), __builtin_bit_cast(i64x2, b)));
+    }
+    __device__ static S one(S a, S b) { return iext<MAX>(a, b); }
+};
+template <bool MAX>
+struct MinMax<DDL_UINT64, MAX> {
+    using S = unsigned long long;
+    __device__ static u32x4 vec(u32x4 a, u32x4 b) {
+        return __builtin_bit_cast(u32x4, iext<MAX>(__builtin_bit_cast(u64x2, a), __builtin_bit_cast(u64x2, b)));
+    }
+    __device__ static S one(S a, S b) { return iext<MAX>(a, b); }
+};
+template <bool MAX>
+struct MinMax<DDL_HALF, MAX> {
+    using S = _Float16;
+    __device__ static u32x4 vec(u32x4 a, u32x4 b) {
+        return __builtin_bit_cast(u32x4, fext<MAX>(__builtin_bit_cast(h16x8, a), __builtin_bit_cast(h16x8, b)));
+    }
+    __device__ static S one(S a, S b) { return fext<MAX>(a, b); }
+};
+template <bool MAX>
+struct MinMax<DDL_BFLOAT16, MAX> {
+    using S = unsigned short;  // the bits: nothing is ever rounded
+    __device__ static u32x4 vec(u32x4 a, u32x4 b) {
+        return u32x4{bext_pair<MAX>(a.x, b.x), bext_pair<MAX>(a.y, b.y), bext_pair<MAX>(a.z, b.z),
+                     bext_pair<MAX>(a.w, b.w)};
+    }
+    __device__ static S one(S a, S b) {
+        const float r = fext<MAX>(__builtin_bit_cast(float, (unsigned int)a << 16),
+                                  __builtin_bit_cast(float, (unsigned int)b << 16));
+        return (S)(__builtin_bit_cast(unsigned int, r) >> 16);
+    }
+};
+#define DDL_MINMAX_ADD(DT)                                                     \
+    template <>                                                                \
+    struct Add<cid(DT, DDL_ALLREDUCE_OP_MIN)> : MinMax<DT, false> {};          \
+    template <>                                                                \
+    struct Add<cid(DT, DDL_ALLREDUCE_OP_MAX)> : MinMax<DT, true> {};
+DDL_MINMAX_ADD(DDL_FLOAT)
+DDL_MINMAX_ADD(DDL_DOUBLE)
+DDL_MINMAX_ADD(DDL_INT32)
+DDL_MINMAX_ADD(DDL_INT64)
+DDL_MINMAX_ADD(DDL_UINT64)
+DDL_MINMAX_ADD(DDL_HALF)
+DDL_MINMAX_ADD(DDL_BFLOAT16)
+#undef DDL_MINMAX_ADD
 
 typedef __attribute__((address_space(1))) void *gptr_t;
 typedef __attribute__((address_space(3))) void *lptr_t;
@@ -499,9 +622,10 @@ bool fold_run_form(size_t chunk_bytes, int order, int inputs) {
     return chunk_bytes >= kFoldRunMinBytes && inputs >= kFoldRunMinInputs;
 }
 
-// Half types fold left in fp32 whatever the order: only kFoldLeft is instantiated for them.
+// Half types fold left in fp32 whatever the order, and MIN / MAX are associative (any order gives
+// the same bits): only kFoldLeft is instantiated for them.
 template <int DT>
-constexpr bool kHalfType = DT == DDL_HALF || DT == DDL_BFLOAT16;
+constexpr bool kOneOrder = DT == DDL_HALF || DT == DDL_BFLOAT16 || cid_op(DT) != 0;
 
 template <int DT, int NB, int FV>
 void launch_sumN_order(const FoldBatch &b, hipStream_t stream) {
@@ -511,7 +635,7 @@ void launch_sumN_order(const FoldBatch &b, hipStream_t stream) {
     for (int i = 0; i < b.count; ++i) max_n = b.t[i].n > max_n ? b.t[i].n : max_n;
     if (fold_run_form((size_t)max_n * sizeof(typename Add<DT>::S), t.order, NB + 1)) {
         const dim3 grid((unsigned)((max_n / V + kRunVec) / kRunVec), (unsigned)b.count);  // +1 vector for the tail
-        if constexpr (!kHalfType<DT>) {
+        if constexpr (!kOneOrder<DT>) {
             if (t.order == kFoldMpichTree) {
                 hipLaunchKernelGGL((k_sumN_run<DT, NB, FV, kFoldMpichTree>), grid, dim3(kFoldThreads), 0, stream, b);
                 return;
@@ -523,7 +647,7 @@ void launch_sumN_order(const FoldBatch &b, hipStream_t stream) {
     const uint64_t tiles = (max_n / V + kFoldThreads) / kFoldThreads;
     DDL_REQUIRE(tiles < (1ull << 31), DDL_STATUS_INVALID_ARGUMENT, "segment too large: " << max_n << " elements");
     const dim3 grid((unsigned)tiles, (unsigned)b.count);
-    if constexpr (!kHalfType<DT>) {
+    if constexpr (!kOneOrder<DT>) {
         if (t.order == kFoldMpichTree) {
             hipLaunchKernelGGL((k_sumN_tile<DT, NB, FV, kFoldMpichTree>), grid, dim3(kFoldThreads), 0, stream, b);
             return;
@@ -582,7 +706,7 @@ void launch_sumN_scalar_nb(const SegTableN &t, hipStream_t stream, unsigned bloc
             launch_sumN_scalar_nb<DT, NB + 1>(t, stream, blocks);
             return;
         }
-        if constexpr (!kHalfType<DT>) {
+        if constexpr (!kOneOrder<DT>) {
             if (t.order == kFoldMpichTree) {
                 hipLaunchKernelGGL((k_sumN_scalar<DT, NB, kFoldMpichTree>), dim3(blocks), dim3(kThreads), 0, stream, t);
                 return;
@@ -643,25 +767,78 @@ void launch_run(const SegTable &t, hipStream_t stream, int policy, uint64_t max_
     }
 }
 
+// MIN / MAX: the forms and cache policies default_variant and ring_variant choose (the SUM bands),
+// and none of the measurement-only variants.
+template <int DT>
+void launch_minmax(const SegTable &t, hipStream_t stream, int variant, uint64_t max_n) {
+    constexpr uint64_t V = 16 / sizeof(typename Add<DT>::S);
+    constexpr int kNtWt = kNtLoadA | kNtLoadB | kWtStore, kNtNt = kNtLoadA | kNtLoadB | kNtStore;
+    const uint64_t wg_vec = variant & kRunForm ? 128ull * 4 : (uint64_t)kReduceThreads;
+    const uint64_t wgs = (max_n / V + wg_vec) / wg_vec;  // +1 vector of room for the tail
+    DDL_REQUIRE(wgs < (1ull << 31), DDL_STATUS_INVALID_ARGUMENT, "segment too large: " << max_n << " elements");
+    const dim3 grid((unsigned)wgs, t.count), block(kReduceThreads);
+    static_assert(kReduceThreads == 128, "k_sum2_run's workgroup");
+    switch (variant) {
+        case kNtLoadA: hipLaunchKernelGGL((k_sum2_tile<DT, kNtLoadA, kReduceThreads>), grid, block, 0, stream, t); break;
+        case kWtStore: hipLaunchKernelGGL((k_sum2_tile<DT, kWtStore, kReduceThreads>), grid, block, 0, stream, t); break;
+        case kNtWt: hipLaunchKernelGGL((k_sum2_tile<DT, kNtWt, kReduceThreads>), grid, block, 0, stream, t); break;
+        case kNtNt: hipLaunchKernelGGL((k_sum2_tile<DT, kNtNt, kReduceThreads>), grid, block, 0, stream, t); break;
+        case kRunForm | kRun4 | kWtStore: hipLaunchKernelGGL((k_sum2_run<DT, kWtStore, 4>), grid, block, 0, stream, t); break;
+        case kRunForm | kRun4 | kNtWt: hipLaunchKernelGGL((k_sum2_run<DT, kNtWt, 4>), grid, block, 0, stream, t); break;
+        default: fail(DDL_STATUS_INVALID_ARGUMENT, "MIN / MAX reduce: variant " + std::to_string(variant));
+    }
+}
+
 template <int DT>
 void launch_dt(const SegTable &t, hipStream_t stream, int variant, bool aligned, uint64_t max_n) {
-    if (aligned && (variant & kRunForm)) {
+    if constexpr (cid_op(DT) != 0) {
+        if (aligned) {
+            launch_minmax<DT>(t, stream, variant, max_n);
+            return;
+        }
+    } else if (aligned && (variant & kRunForm)) {
         if (variant & kRun4) launch_run<DT, 4>(t, stream, variant & kVariantMask, max_n);
         else launch_run<DT, 8>(t, stream, variant & kVariantMask, max_n);
         return;
     }
-    if (!aligned) {
+    if (!aligned) {  // (MIN / MAX too)
         uint64_t blocks = (max_n + kThreads * 4 - 1) / (kThreads * 4);
         const uint64_t cap = (uint64_t)device_cu_count() * 8;
         blocks = blocks > cap ? cap : (blocks < 1 ? 1 : blocks);
         hipLaunchKernelGGL(k_sum2_scalar<DT>, dim3((unsigned)blocks, t.count), dim3(kThreads), 0, stream, t);
         return;
     }
-    constexpr uint64_t V = 16 / sizeof(typename Add<DT>::S);
-    constexpr uint64_t tv = kReduceThreads;
-    const uint64_t tiles = (max_n / V + tv) / tv;  // +1 vector of room for the tail
-    DDL_REQUIRE(tiles < (1ull << 31), DDL_STATUS_INVALID_ARGUMENT, "segment too large: " << max_n << " elements");
-    launch_variant<DT, 0>(t, stream, variant, dim3((unsigned)tiles, t.count));
+    if constexpr (cid_op(DT) == 0) {
+        constexpr uint64_t V = 16 / sizeof(typename Add<DT>::S);
+        constexpr uint64_t tv = kReduceThreads;
+        const uint64_t tiles = (max_n / V + tv) / tv;  // +1 vector of room for the tail
+        DDL_REQUIRE(tiles < (1ull << 31), DDL_STATUS_INVALID_ARGUMENT, "segment too large: " << max_n << " elements");
+        launch_variant<DT, 0>(t, stream, variant, dim3((unsigned)tiles, t.count));
+    }
+}
+
+// Calls f(std::integral_constant<int, combine id>) for (dtype, op), op SUM / MIN / MAX.
+template <int DT, class F>
+void with_op(int op, F &&f) {
+    switch (op) {
+        case DDL_ALLREDUCE_OP_SUM: f(std::integral_constant<int, DT>{}); break;
+        case DDL_ALLREDUCE_OP_MIN: f(std::integral_constant<int, cid(DT, DDL_ALLREDUCE_OP_MIN)>{}); break;
+        case DDL_ALLREDUCE_OP_MAX: f(std::integral_constant<int, cid(DT, DDL_ALLREDUCE_OP_MAX)>{}); break;
+        default: fail(DDL_STATUS_INVALID_ARGUMENT, "reduce kernels: op " + std::to_string(op));
+    }
+}
+template <class F>
+void with_combine(int dtype, int op, F &&f) {
+    switch (dtype) {
+        case DDL_FLOAT: with_op<DDL_FLOAT>(op, f); break;
+        case DDL_DOUBLE: with_op<DDL_DOUBLE>(op, f); break;
+        case DDL_INT32: with_op<DDL_INT32>(op, f); break;
+        case DDL_INT64: with_op<DDL_INT64>(op, f); break;
+        case DDL_UINT64: with_op<DDL_UINT64>(op, f); break;
+        case DDL_HALF: with_op<DDL_HALF>(op, f); break;
+        case DDL_BFLOAT16: with_op<DDL_BFLOAT16>(op, f); break;
+        default: fail(DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported dtype");
+    }
 }
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -720,7 +897,7 @@ void check_fold(const SegTableN &t) {
 }
 }  // namespace
 
-void launch_sumN_batch(const SegTableN *t, int count, int dtype, hipStream_t stream) {
+void launch_sumN_batch(const SegTableN *t, int count, int dtype, hipStream_t stream, int op) {
     DDL_REQUIRE(count >= 0 && count <= kMaxFoldBatch, DDL_STATUS_INVALID_ARGUMENT, "fold batch of " << count);
     FoldBatch b;
     b.count = 0;
@@ -732,20 +909,15 @@ void launch_sumN_batch(const SegTableN *t, int count, int dtype, hipStream_t str
         b.t[b.count++] = t[i];
     }
     if (b.count == 0) return;
-    switch (dtype) {
-        case DDL_FLOAT: launch_sumN_dt<DDL_FLOAT>(b, stream); break;
-        case DDL_DOUBLE: launch_sumN_dt<DDL_DOUBLE>(b, stream); break;
-        case DDL_INT32: launch_sumN_dt<DDL_INT32>(b, stream); break;
-        case DDL_INT64: launch_sumN_dt<DDL_INT64>(b, stream); break;
-        case DDL_UINT64: launch_sumN_dt<DDL_UINT64>(b, stream); break;
-        case DDL_HALF: launch_sumN_dt<DDL_HALF>(b, stream); break;
-        case DDL_BFLOAT16: launch_sumN_dt<DDL_BFLOAT16>(b, stream); break;
-        default: fail(DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported dtype");
-    }
+    if (op != DDL_ALLREDUCE_OP_SUM)  // associative: every order is the left fold's instance
+        for (int i = 0; i < b.count; ++i) b.t[i].order = kFoldLeft;
+    with_combine(dtype, op, [&](auto id) { launch_sumN_dt<decltype(id)::value>(b, stream); });
     DDL_HIP(hipGetLastError());
 }
 
-void launch_sumN(const SegTableN &t, int dtype, hipStream_t stream) { launch_sumN_batch(&t, 1, dtype, stream); }
+void launch_sumN(const SegTableN &t, int dtype, hipStream_t stream, int op) {
+    launch_sumN_batch(&t, 1, dtype, stream, op);
+}
 
 // Standalone reduce (acc += in over whole buckets) of `bytes` per operand, by bucket size
 // (3 rotating buffer sets per size, interleaved A/Bs: profiles/r02/reduce_policy/, profiles/r05/s6/,
@@ -787,7 +959,7 @@ int default_variant(size_t bytes) {
 // step's send (keep it cache-resident: plain store).
 int ring_variant() { return kNtLoadA; }
 
-void launch_sum2(const SegTable &t, int dtype, hipStream_t stream, int variant) {
+void launch_sum2(const SegTable &t, int dtype, hipStream_t stream, int variant, int op) {
     DDL_REQUIRE(t.count >= 1 && t.count <= kMaxSegments, DDL_STATUS_INVALID_ARGUMENT,
                 "segment count " << t.count << " outside [1, " << kMaxSegments << "]");
     const size_t es = dtype_size(dtype);
@@ -804,16 +976,7 @@ void launch_sum2(const SegTable &t, int dtype, hipStream_t stream, int variant) 
     if (max_n == 0) return;
     if (variant < 0) variant = default_variant((size_t)total_n * es);
     DDL_REQUIRE(variant <= (kVariantMask | kRunForm | kRun4), DDL_STATUS_INVALID_ARGUMENT, "bad reduce variant " << variant);
-    switch (dtype) {
-        case DDL_FLOAT: launch_dt<DDL_FLOAT>(t, stream, variant, aligned, max_n); break;
-        case DDL_DOUBLE: launch_dt<DDL_DOUBLE>(t, stream, variant, aligned, max_n); break;
-        case DDL_INT32: launch_dt<DDL_INT32>(t, stream, variant, aligned, max_n); break;
-        case DDL_INT64: launch_dt<DDL_INT64>(t, stream, variant, aligned, max_n); break;
-        case DDL_UINT64: launch_dt<DDL_UINT64>(t, stream, variant, aligned, max_n); break;
-        case DDL_HALF: launch_dt<DDL_HALF>(t, stream, variant, aligned, max_n); break;
-        case DDL_BFLOAT16: launch_dt<DDL_BFLOAT16>(t, stream, variant, aligned, max_n); break;
-        default: fail(DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported dtype");
-    }
+    with_combine(dtype, op, [&](auto id) { launch_dt<decltype(id)::value>(t, stream, variant, aligned, max_n); });
     DDL_HIP(hipGetLastError());
 }
 

@@ -285,6 +285,12 @@ void ThreadWorld::allreduce_batch(const void *const *in, void *const *out, const
 size_t ThreadWorld::fused_allreduce(const void *const *srcs, void *const *dsts, const size_t *bytes, int count,
                                     int dtype, hipStream_t user, const RingConfig &cfg, size_t cap, const int *ops,
                                     int src_dtype, void *const *residuals) {
+    // the plan's kind: MIN / MAX plans hold one kind only (the keyed handler's groups)
+    const int kind = ops && count > 0 ? reduce_kind(ops[0]) : DDL_ALLREDUCE_OP_SUM;
+    for (int i = 0; ops && i < count; ++i)
+        DDL_REQUIRE(reduce_kind(ops[i]) == kind, DDL_STATUS_INVALID_ARGUMENT,
+                    "a fusion plan holds one reduction kind: segment " << i << " has op " << ops[i] << ", segment 0 op "
+                                                                       << ops[0]);
     while (pipes_.size() < (size_t)P_) pipes_.emplace_back(new FusionPipe);
     const std::vector<size_t> b(bytes, bytes + count);
     const std::vector<int> o(ops ? ops : nullptr, ops ? ops + count : nullptr);
@@ -296,7 +302,7 @@ size_t ThreadWorld::fused_allreduce(const void *const *srcs, void *const *dsts, 
         pipes_[r]->run(src, dst, b, dtype, cap, s, [&](void *buf, size_t elems, size_t message) {
             RingConfig c = cfg;
             c.order_bytes = message;
-            ex_[r]->allreduce(buf, buf, elems, dtype, s, c);
+            ex_[r]->allreduce(buf, buf, elems, dtype, s, c, kind);
         }, ops ? &o : nullptr, P_, src_dtype, residuals ? &res : nullptr);
     });
     return pipes_[0]->subplans();
@@ -331,7 +337,7 @@ const P2POp &LocalWorld::match_(int r, size_t t, const P2POp &op, std::map<std::
 }
 
 void LocalWorld::allreduce(const void *const *in, void *const *out, size_t n, int dtype,
-                           hipStream_t user, const RingConfig &cfg) {
+                           hipStream_t user, const RingConfig &cfg, int kind) {
     const size_t es = dtype_size(dtype);
     DDL_REQUIRE(es != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported dtype " << dtype);
     if (n == 0) return;
@@ -344,7 +350,7 @@ void LocalWorld::allreduce(const void *const *in, void *const *out, size_t n, in
         void *st = res_[r]->ensure_staging(program_staging_elems(n, es, P_, cfg) * es, capture);
         build_program(progs_[r], r, P_, in[r], out[r], st, n, dtype, cfg);
     }
-    run_(dtype, user);
+    run_(dtype, user, kind);
 }
 
 void LocalWorld::allreduce_batch(const void *const *in, void *const *out, const size_t *n, int count, int dtype,
@@ -379,7 +385,7 @@ void LocalWorld::allgatherv(const void *const *sends, void *const *recvs, const 
     run_(dtype, user);
 }
 
-void LocalWorld::run_(int dtype, hipStream_t user) {
+void LocalWorld::run_(int dtype, hipStream_t user, int kind) {
     const size_t T = progs_[0].ticks.size();
     if (T == 0) return;
     for (int r = 0; r < P_; ++r) {
@@ -516,7 +522,7 @@ void LocalWorld::run_(int dtype, hipStream_t user) {
             wait(compute(r), rr.comm_ev[t]);
             DDL_TRACE("reduce launch on " << (void *)compute(r));
             const hipStream_t cs = p.on(compute(r));
-            launch_tick_reduce(tk, dtype, cs);
+            launch_tick_reduce(tk, dtype, cs, kind);
             p.posted(compute(r));
             if (dep::on()) dep::op(cs, dep_label(tk.multi ? "fold" : "reduce", r, t), tick_reduce_access(tk, dtype));
             record(rr.red_ev[t], compute(r));

@@ -125,8 +125,9 @@ class LocalWorld {
 public:
     LocalWorld(int nranks, int device, ncclComm_t loopback = nullptr);
     ~LocalWorld();
+    // `kind`: what the reduce / fold launches compute (reduce_kind: SUM, MIN or MAX)
     void allreduce(const void *const *in, void *const *out, size_t n, int dtype, hipStream_t user,
-                   const RingConfig &cfg);
+                   const RingConfig &cfg, int kind = DDL_ALLREDUCE_OP_SUM);
     // in[r * count + b] / out[r * count + b]: rank r's bucket b (RingExecutor::allreduce_batch)
     void allreduce_batch(const void *const *in, void *const *out, const size_t *n, int count, int dtype,
                          hipStream_t user, const RingConfig &cfg);
@@ -137,7 +138,7 @@ public:
     long long loopback_pairs() const { return loop_pairs_; }
 
 private:
-    void run_(int dtype, hipStream_t user);
+    void run_(int dtype, hipStream_t user, int kind = DDL_ALLREDUCE_OP_SUM);
     // the matching send of rank r's recv `op` at tick t (k-th recv from a (peer, tag) pairs with
     // the peer's k-th send to r with that tag)
     const P2POp &match_(int r, size_t t, const P2POp &op, std::map<std::pair<int, int>, int> &seen) const;
@@ -171,7 +172,8 @@ public:
     // pack -> allreduce -> unpack, sub-plans above `cap` bytes), each sub-plan's allreduce through
     // the rank's RingExecutor with the whole plan's message size. srcs[r * count + i] /
     // dsts[r * count + i]: rank r's segment i of bytes[i] bytes; ops[i] (optional) segment i's
-    // ddl_allreduce_op. Returns the sub-plans per rank.
+    // ddl_allreduce_op; the allreduces run with the segments' one reduction kind (SUM / AVG, MIN or
+    // MAX: a plan that mixes kinds is refused). Returns the sub-plans per rank.
     size_t fused_allreduce(const void *const *srcs, void *const *dsts, const size_t *bytes, int count, int dtype,
                            hipStream_t user, const RingConfig &cfg, size_t cap, const int *ops = nullptr,
                            int src_dtype = 0,  // != 0: a compressed plan (FusionPipe::run), bytes on the wire

@@ -40,6 +40,7 @@ STATUS_NAMES = {0: 'OK', 1: 'COMM_ERROR', 2: 'ERROR_UNKNOWN', 3: 'INVALID_ARGUME
                 8: 'CONFIG_MISMATCH'}
 STATUS_CONFIG_MISMATCH = 8
 OP_SUM, OP_AVG = 0, 1  # enum ddl_allreduce_op
+OP_MIN, OP_MAX = 3, 4  # element-wise IEEE 754-2019 minimum / maximum (integers: their order); 2 is not an op
 WIRE_FP16, WIRE_BF16 = 0x100, 0x200  # enum ddl_allreduce_wire: OR-ed into a keyed fp32 device request's op
 WIRE_FEEDBACK = 0x1000  # error feedback: only together with exactly one of the two wire flags
 MEMORY_DEVICE, MEMORY_HOST = 0, 1  # enum ddl_memory
@@ -167,6 +168,10 @@ class CPPBackend:
         sig('ddl_reduce_fold', ci, vp, vp, ctypes.POINTER(vp), ci, sz, ci, vp)
         sig('ddl_reduce_fold_ordered', ci, vp, vp, ctypes.POINTER(vp), ci, sz, ci, ci, vp)
         sig('ddl_reduce_fold_batch', ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ci,
+            ctypes.POINTER(sz), ci, ci, vp)
+        sig('ddl_reduce_op2', ci, vp, vp, vp, sz, ci, ci, vp)
+        sig('ddl_reduce_fold_op', ci, vp, vp, ctypes.POINTER(vp), ci, sz, ci, ci, vp)
+        sig('ddl_reduce_fold_batch_op', ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ci,
             ctypes.POINTER(sz), ci, ci, vp)
         sig('ddl_pack', ci, vp, ctypes.POINTER(vp), ctypes.POINTER(sz), ci, vp)
         sig('ddl_unpack', ci, ctypes.POINTER(vp), vp, ctypes.POINTER(sz), ci, vp)

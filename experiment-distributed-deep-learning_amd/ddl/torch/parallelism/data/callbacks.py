@@ -15,6 +15,7 @@ The first two go through the engine's keyed requests (one negotiated, fused roun
 """
 import torch
 
+from ddl.torch import cpp_backend as cb
 from ddl.torch.communicator import Communicator
 from ddl.torch.tensor_communicate import allreduce_async, broadcast_parameters
 
@@ -48,20 +49,30 @@ class InitialParametersBroadcast:
 
 
 class MetricAverage:
-    """`on_epoch_end(epoch, logs)` replaces every value in `logs` by its mean over the ranks."""
+    """`on_epoch_end(epoch, logs)` replaces every value in `logs` by its mean over the ranks.
+    `ops` (optional): metric name -> cb.OP_SUM / OP_AVG / OP_MIN / OP_MAX for the metrics that are
+    not averaged (the best / worst value over the ranks, the slowest rank's step time, a count); a
+    metric not named in it is averaged as ever, so with the default every metric is. The same `ops`
+    on every rank: MIN / MAX are a property of the request's name."""
 
-    def __init__(self, communicator: Communicator = None, device=None):
+    def __init__(self, communicator: Communicator = None, device=None, ops: dict = None):
         self._comm = Communicator.world() if communicator is None else communicator
         self._device = torch.device('cuda', torch.cuda.current_device()) if device is None else device
+        self._ops = dict(ops or {})
+        for k, op in self._ops.items():
+            if op not in (cb.OP_SUM, cb.OP_AVG, cb.OP_MIN, cb.OP_MAX):
+                raise ValueError(f'MetricAverage: unknown op {op!r} for metric {k!r}')
 
     def average(self, logs: dict) -> dict:
         if not logs:
             return logs
         names = sorted(logs)
         vals = [torch.as_tensor(logs[k], dtype=torch.float64).reshape(1).to(self._device) for k in names]
-        handles = [allreduce_async(v, f'MetricAverage.{k}', self._comm) for k, v in zip(names, vals)]
+        # a metric without an op of its own: the sum, divided here (as before there were ops)
+        handles = [allreduce_async(v, f'MetricAverage.{k}', self._comm, op=self._ops[k]) if k in self._ops else
+                   allreduce_async(v, f'MetricAverage.{k}', self._comm) for k, v in zip(names, vals)]
         for k, h in zip(names, handles):
-            logs[k] = h.wait().item() / self._comm.size
+            logs[k] = h.wait().item() if k in self._ops else h.wait().item() / self._comm.size
         return logs
 
     def on_epoch_end(self, epoch=None, logs=None):

@@ -4,7 +4,9 @@
 communicator's ranks — as the reference's `Allreduce` op does (AllreduceOp.cc:32-66, output
 allocated like the input). `allreduce_gradient` divides by the size; every allreduce also takes
 `op=cb.OP_AVG` for the mean, which the engine divides on the GPU in the kernel that writes the
-result (the IEEE quotient, as numpy and torch CPU compute it). `allreduce_async` is the
+result (the IEEE quotient, as numpy and torch CPU compute it), and `op=cb.OP_MIN` / `cb.OP_MAX` for
+the element-wise minimum / maximum over the ranks (IEEE 754-2019: a NaN on any rank gives a NaN,
+-0 < +0; integers in their own order; never with a `compression`). `allreduce_async` is the
 keyed request path (the TF op's asynchronous `handleRequest`): requests registered under
 a key are negotiated across ranks, fused by dtype in key order and completed through a
 callback.
@@ -34,6 +36,12 @@ def _comm(communicator):
     return Communicator.world() if communicator is None else communicator
 
 
+def _check_op_compression(op, compression) -> None:
+    """MIN / MAX never travel over a 16-bit wire: refused here, before any library call."""
+    if int(op) in (cb.OP_MIN, cb.OP_MAX) and wire_flag(compression):
+        raise ValueError(f'op {int(op)} (MIN / MAX) takes no compression, got {compression!r}')
+
+
 def _allreduce_device(src: torch.Tensor, dst: torch.Tensor, communicator: Communicator,
                       op: int = cb.OP_SUM) -> None:
     require_device_tensor(src, 'allreduce input')
@@ -45,7 +53,8 @@ def _allreduce_device(src: torch.Tensor, dst: torch.Tensor, communicator: Commun
 
 def allreduce(tensor: torch.Tensor, communicator: Communicator = None, op: int = cb.OP_SUM) -> torch.Tensor:
     """Sum of `tensor` over all ranks of `communicator` (`op=cb.OP_AVG`: the mean, divided by the
-    engine on the GPU); returns a new tensor."""
+    engine on the GPU; `cb.OP_MIN` / `cb.OP_MAX`: the element-wise minimum / maximum); returns a new
+    tensor."""
     communicator = _comm(communicator)
     if tensor.is_cuda:
         src = tensor.contiguous()
@@ -69,7 +78,7 @@ def allreduce_(tensor: torch.Tensor, communicator: Communicator = None, op: int 
 
 
 def allreduce_batch_(tensors, communicator: Communicator = None, op: int = cb.OP_SUM):
-    """In-place SUM (`op=cb.OP_AVG`: mean) of every device tensor in `tensors` (one dtype) over the ranks, as ONE grouped
+    """In-place SUM (`op=cb.OP_AVG`: mean, `cb.OP_MIN` / `cb.OP_MAX`: minimum / maximum) of every device tensor in `tensors` (one dtype) over the ranks, as ONE grouped
     collective (ddl_allreduce_batch): a DDP-style bucket list reduced with one RCCL group per tick
     and the folds of up to 8 buckets per kernel launch. With reference_order 1 (the default) each
     result is bit for bit what `allreduce_` gives that tensor alone (MPICH's order for its own
@@ -444,7 +453,9 @@ def _same_memory(a: torch.Tensor, b: torch.Tensor, what: str) -> int:
 
 def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator = None,
                     output: torch.Tensor = None, op: int = cb.OP_SUM, compression=Compression.none) -> Handle:
-    """Register a keyed allreduce (`op`: cb.OP_SUM, or cb.OP_AVG for the mean); returns a Handle.
+    """Register a keyed allreduce (`op`: cb.OP_SUM, cb.OP_AVG for the mean, cb.OP_MIN / cb.OP_MAX for
+    the element-wise minimum / maximum — like a compression, the same on every rank for a name, and
+    never together with one: ValueError); returns a Handle.
     `compression` (Compression.fp16 / .bf16): a dense fp32 device tensor at size > 1 is sent and
     summed as 16-bit values and comes back as fp32 (ddl.torch.compression; every rank must pass the
     same compression for a name); any other tensor is submitted as without it. With
@@ -459,6 +470,7 @@ def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator 
     Device tensors stay in HBM; host (CPU) tensors — the reference's only kind, its op is
     DEVICE_CPU (AllreduceOp.cc:68) — are fused through pinned staging to the GPU and back.
     """
+    _check_op_compression(op, compression)
     communicator = _comm(communicator)
     out = torch.empty_like(tensor) if output is None else output
     mem = _same_memory(tensor, out, 'allreduce_async')
@@ -482,13 +494,14 @@ def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator 
 def allreduce_async_batch(tensors, names, communicator: Communicator = None, outputs=None, op: int = cb.OP_SUM,
                           compression=Compression.none):
     """Register several keyed allreduces at once (one engine wake-up, one input-ready event), all
-    with `op` (cb.OP_SUM, or cb.OP_AVG for the mean); returns one Handle per tensor. Same key rules as `allreduce_async`; device and host tensors
+    with `op` (cb.OP_SUM, cb.OP_AVG for the mean, cb.OP_MIN / cb.OP_MAX); returns one Handle per tensor. Same key rules as `allreduce_async`; device and host tensors
     may be mixed (one submission per memory kind). `compression` (Compression.fp16 / .bf16) applies
     to the dense fp32 device tensors at size > 1 (ddl.torch.compression); the others are submitted
     uncompressed, so a mixed batch goes as one compressed and one plain submission. The handles
     come back in the caller's order either way. The error-feedback kinds as in `allreduce_async`:
     one residual per name, so stable names."""
     import ctypes
+    _check_op_compression(op, compression)
     communicator = _comm(communicator)
     tensors = list(tensors)
     names = list(names)

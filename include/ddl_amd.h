@@ -77,8 +77,10 @@ enum ddl_memory { DDL_MEMORY_DEVICE = 0, DDL_MEMORY_HOST = 1 };
 
 /* Communicator::AllreduceOperation (reference Communicator.h:22-24 has SUM only). AVG (MI355X
  * extension) is the SUM result divided by the communicator's size, the quotient taken on the GPU
- * by the kernel that writes the result (see the data-plane section). */
-enum ddl_allreduce_op { DDL_ALLREDUCE_OP_SUM = 0, DDL_ALLREDUCE_OP_AVG = 1 };
+ * by the kernel that writes the result (see the data-plane section). MIN / MAX (MI355X extension,
+ * Horovod's numbers; 2 is not an op) are the element-wise minimum / maximum over the ranks. */
+enum ddl_allreduce_op { DDL_ALLREDUCE_OP_SUM = 0, DDL_ALLREDUCE_OP_AVG = 1, DDL_ALLREDUCE_OP_MIN = 3,
+                        DDL_ALLREDUCE_OP_MAX = 4 };
 /* Wire format of a keyed device allreduce of DDL_FLOAT tensors (MI355X extension, Horovod's
  * Compression.fp16): at most one flag, OR-ed into `op`. The gradients travel and are summed as
  * 16-bit values and come back as fp32 (see the data-plane section). */
@@ -292,7 +294,27 @@ void py_error(const char *log_str);
  * returns DDL_STATUS_INVALID_ARGUMENT; with host memory or another dtype than DDL_FLOAT the wire
  * flag's own refusals apply.
  * P = 1: with "one_rank_shortcut" 1 nothing is touched and no residual is made; with 0 the data
- * plane runs and the feedback applies. */
+ * plane runs and the feedback applies.
+ *
+ * MIN / MAX: DDL_ALLREDUCE_OP_MIN = 3 and DDL_ALLREDUCE_OP_MAX = 4, on every dtype and every
+ * allreduce entry point. Per element over the P inputs: DDL_INT32 / DDL_INT64 in signed order,
+ * DDL_UINT64 in unsigned order; DDL_FLOAT / DDL_DOUBLE / DDL_HALF / DDL_BFLOAT16 are IEEE 754-2019
+ * `minimum` / `maximum`: if any input is a NaN the result is a quiet NaN (sign and payload not
+ * pinned), otherwise it is bit for bit the input that is least / greatest in numeric order with
+ * -0 < +0. Subnormals are kept, nothing is rounded (the 16-bit types may be widened internally: the
+ * result is the same). This is deliberately not MPICH's `a > b ? a : b`, whose result depends on
+ * the order once a NaN or +-0 is present and which lets a NaN hide behind a MAX. The operation is
+ * associative and commutative, so the result does not depend on the schedule, the slicing, the fold
+ * order, "reference_order" or P, and for non-NaN results every rank holds the same bits. The
+ * reduce and fold kernels (csrc/reduce_kernels.hip) take the combine in place of the addition:
+ * the same schedules, bytes and launches as SUM, no trailing launch, so MIN / MAX direct
+ * collectives can be captured into a hipGraph exactly like SUM. P = 1: the result is the input.
+ * Unlike SUM against AVG the reduction kind IS communicated: like the wire flag it is a property of
+ * a key that every rank must agree on (MIN and MAX requests form fusion groups of their own, after
+ * the SUM / AVG group of the same dtype and memory, MIN before MAX). Ranks that disagree about a
+ * key's kind post different collectives.
+ * Refusals, before anything is registered: MIN / MAX with a wire flag or DDL_ALLREDUCE_WIRE_FEEDBACK
+ * returns DDL_STATUS_INVALID_ARGUMENT; op values 2 and above 4 stay DDL_STATUS_INVALID_ARGUMENT. */
 /* recv = SUM over ranks of send (elementwise), bit for bit the reference's MPI_Allreduce (MPICH
  * 3.3.2's order) with reference_order 1. The schedule is the tuned one for the bucket's size
  * class: by default at P > 2 the direct reduce-scatter (slices of every chunk to every peer over

@@ -111,6 +111,16 @@ int ddl_reduce_fold_ordered(void *out, const void *a, const void *const *ins, in
 int ddl_reduce_fold_batch(int count, void *const *outs, const void *const *as, const void *const *ins, int nb,
                           const size_t *elements, int dtype, int order, void *hip_stream);
 
+/* The reduce and the folds above with the combine of `op`: DDL_ALLREDUCE_OP_SUM (the left fold),
+ * DDL_ALLREDUCE_OP_MIN or DDL_ALLREDUCE_OP_MAX (ddl_amd.h: IEEE 754-2019 minimum / maximum, the
+ * integer order; associative, so there is no order argument). The forms, tiles and cache policies
+ * are the engine's for the size (config "fold_form" is honoured); out may alias an input. */
+int ddl_reduce_op2(void *out, const void *a, const void *b, size_t elements, int dtype, int op, void *hip_stream);
+int ddl_reduce_fold_op(void *out, const void *a, const void *const *ins, int nb, size_t elements, int dtype, int op,
+                       void *hip_stream);
+int ddl_reduce_fold_batch_op(int count, void *const *outs, const void *const *as, const void *const *ins, int nb,
+                             const size_t *elements, int dtype, int op, void *hip_stream);
+
 /* Fusion pack/unpack (device): gathers `count` segments into one contiguous buffer and
  * scatters it back (executeCommunicatePlan_'s memcpy in/out, MPIRingTokenCommunication.cc:548-733). */
 int ddl_pack(void *dst, const void *const *srcs, const size_t *bytes, int count, void *hip_stream);
@@ -187,7 +197,9 @@ int ddl_testing_thread_allgatherv(int nranks, const void *const *sends, void *co
 int ddl_testing_thread_fused_allreduce(int nranks, int count, const void *const *srcs, void *const *dsts,
                                        const size_t *bytes, int dtype, void *hip_stream, size_t *subplans);
 /* The same with ops[i] = segment i's ddl_allreduce_op, as the keyed handler passes the requests'
- * ops to FusionPipe::run (AVG segments are divided by nranks in the unpack of their sub-plans). */
+ * ops to FusionPipe::run (AVG segments are divided by nranks in the unpack of their sub-plans). The
+ * sub-plans' allreduces run with the segments' reduction kind; a plan that mixes SUM / AVG, MIN and
+ * MAX segments returns DDL_STATUS_INVALID_ARGUMENT (the handler never forms one). */
 int ddl_testing_thread_fused_allreduce_ops(int nranks, int count, const void *const *srcs, void *const *dsts,
                                            const size_t *bytes, const int *ops, int dtype, void *hip_stream,
                                            size_t *subplans);
