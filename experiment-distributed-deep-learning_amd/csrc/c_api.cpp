@@ -320,6 +320,29 @@ int ddl_tune_result(ddl_communicator_id id, size_t bucket_bytes, int *chosen, in
     });
 }
 
+namespace {
+// DDL_ALLREDUCE_SUMSQ (ddl_amd.h): with the bit `user` is a ddl_sumsq_arg, read here and now. Takes the
+// bit out of `op`, leaves what done() receives in *user and where the value goes in *sumsq (null: not
+// wanted, also without the bit).
+static void take_sumsq(int *op, void **user, double **sumsq) {
+    *sumsq = nullptr;
+    if (!(*op & DDL_ALLREDUCE_SUMSQ)) return;
+    DDL_REQUIRE(*user, DDL_STATUS_INVALID_ARGUMENT, "DDL_ALLREDUCE_SUMSQ needs a ddl_sumsq_arg as the user pointer");
+    const ddl_sumsq_arg arg = *static_cast<const ddl_sumsq_arg *>(*user);
+    *op &= ~DDL_ALLREDUCE_SUMSQ;
+    *user = arg.user;
+    *sumsq = arg.sumsq;
+}
+// the refusals of a wanted sum of squares, before anything is registered or recorded
+static void check_sumsq(const double *sumsq, int dtype, int op, bool host) {
+    if (!sumsq) return;
+    DDL_REQUIRE(dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
+                "the sum of squares is defined for float32 requests, not " << dtype_name(dtype));
+    DDL_REQUIRE(!op_is_minmax(op), DDL_STATUS_INVALID_ARGUMENT, "the sum of squares takes SUM or AVG, not MIN / MAX");
+    DDL_REQUIRE(!host, DDL_STATUS_INVALID_ARGUMENT, "the sum of squares takes device memory");
+}
+}  // namespace
+
 int ddl_allreduce_submit_mem(ddl_communicator_id id, const char *key, const void *in, void *out, size_t elements,
                              int dtype, int op, int memory, void *hip_stream, ddl_done_fn done, void *user) {
     return guarded([&] {
@@ -333,7 +356,9 @@ int ddl_allreduce_submit_mem(ddl_communicator_id id, const char *key, const void
         r.n = elements;
         r.dtype = dtype;
         r.host = memory == DDL_MEMORY_HOST;
+        take_sumsq(&op, &user, &r.sumsq);
         r.wire = decode_keyed_op(op, dtype, r.host, &r.op, &r.feedback);  // refusals before anything is posted
+        check_sumsq(r.sumsq, dtype, r.op, r.host);
         r.done = done;
         r.user = user;
         r.ready = ready_event(memory, hip_stream);
@@ -413,6 +438,8 @@ int ddl_allreduce_submit_batch_mem(ddl_communicator_id id, int count, const char
         if (count == 0) return;
         auto c = Registry::get().find(id);
         DeviceGuard g(c->device());
+        DDL_REQUIRE(!(op & DDL_ALLREDUCE_SUMSQ) || users, DDL_STATUS_INVALID_ARGUMENT,
+                    "DDL_ALLREDUCE_SUMSQ needs one ddl_sumsq_arg per request in users");
         // one op for the batch: with a wire flag every entry must be fp32 (all-or-nothing, decided
         // before the ready event is recorded)
         std::vector<Request> rs(count);
@@ -424,9 +451,12 @@ int ddl_allreduce_submit_batch_mem(ddl_communicator_id id, int count, const char
             rs[i].n = elements[i];
             rs[i].dtype = dtypes[i];
             rs[i].host = memory == DDL_MEMORY_HOST;
-            rs[i].wire = decode_keyed_op(op, dtypes[i], rs[i].host, &rs[i].op, &rs[i].feedback);
-            rs[i].done = done;
+            int opi = op;
             rs[i].user = users ? users[i] : nullptr;
+            take_sumsq(&opi, &rs[i].user, &rs[i].sumsq);  // (the args' sumsq entries may be NULL)
+            rs[i].wire = decode_keyed_op(opi, dtypes[i], rs[i].host, &rs[i].op, &rs[i].feedback);
+            check_sumsq(rs[i].sumsq, dtypes[i], rs[i].op, rs[i].host);
+            rs[i].done = done;
         }
         auto ready = ready_event(memory, hip_stream);
         for (Request &r : rs) r.ready = ready;

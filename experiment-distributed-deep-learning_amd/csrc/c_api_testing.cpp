@@ -162,6 +162,37 @@ std::vector<size_t> wire_bytes(const size_t *elements, int count, int wire_dtype
     for (int i = 0; i < count; ++i) b[i] = elements[i] * dtype_size(wire_dtype);
     return b;
 }
+
+// ddl_unpack_ops_sumsq / ddl_unpack_cvt_sumsq: the piece values through pinned memory, waited for here.
+// One grow-only pinned buffer (under abi_copier_mu, as the copier): no allocation per call, so the
+// entries can be timed (tools/sumsq_probe.py).
+double *sumsq_buffer(size_t count) {
+    static double *buf = nullptr;
+    static size_t cap = 0;
+    if (count > cap) {
+        if (buf) (void)hipHostFree(buf);
+        buf = nullptr;
+        cap = 0;
+        void *m = nullptr;
+        DDL_HIP(hipHostMalloc(&m, count * 2 * sizeof(double), hipHostMallocDefault));
+        buf = static_cast<double *>(m);
+        cap = count * 2;
+    }
+    return buf;
+}
+
+template <class Run>
+void unpack_sumsq(int count, void *hip_stream, double *sumsq_out, const Run &run) {
+    double *buf = sumsq_buffer((size_t)count);
+    try {
+        run(buf);
+    } catch (...) {
+        (void)hipStreamSynchronize(as_stream(hip_stream));  // a copy into buf may have been posted
+        throw;
+    }
+    DDL_HIP(hipStreamSynchronize(as_stream(hip_stream)));
+    std::copy(buf, buf + count, sumsq_out);
+}
 }  // namespace
 
 extern "C" {
@@ -445,6 +476,39 @@ int ddl_unpack_ops(void *const *dsts, const void *src, const size_t *bytes, cons
     });
 }
 
+int ddl_unpack_ops_sumsq(void *const *dsts, const void *src, const size_t *bytes, const int *ops, int count, int dtype,
+                         int divisor, void *hip_stream, const unsigned char *want, double *sumsq_out) {
+    return guarded([&] {
+        DDL_REQUIRE(count >= 0 && (count == 0 || (dsts && bytes && ops && want && sumsq_out)) && divisor >= 1,
+                    DDL_STATUS_INVALID_ARGUMENT, "bad unpack_ops_sumsq args");
+        if (count == 0) return;
+        std::lock_guard<std::mutex> g(abi_copier_mu());
+        unpack_sumsq(count, hip_stream, sumsq_out, [&](double *sq) {
+            abi_copier().run(src ? 1 : SegmentCopier::kSumsqInPlace, const_cast<void *>(src), dsts, bytes, count,
+                             as_stream(hip_stream), dtype, divisor, ops, want, sq);
+        });
+    });
+}
+
+int ddl_unpack_cvt_sumsq(void *const *dsts, const void *src, const size_t *elements, const int *ops, int count,
+                         int wire_dtype, int divisor, void *hip_stream, const unsigned char *want, double *sumsq_out) {
+    return guarded([&] {
+        DDL_REQUIRE(count >= 0 && (count == 0 || (dsts && elements && want && sumsq_out)) && divisor >= 1,
+                    DDL_STATUS_INVALID_ARGUMENT, "bad unpack_cvt_sumsq args");
+        if (count == 0) return;
+        for (int i = 0; ops && i < count; ++i) {
+            check_allreduce_op(ops[i], DDL_FLOAT);
+            DDL_REQUIRE(!op_is_minmax(ops[i]), DDL_STATUS_INVALID_ARGUMENT, "MIN / MAX take no wire");
+        }
+        const std::vector<size_t> b = wire_bytes(elements, count, wire_dtype);
+        std::lock_guard<std::mutex> g(abi_copier_mu());
+        unpack_sumsq(count, hip_stream, sumsq_out, [&](double *sq) {
+            abi_copier().run_cvt(src ? 1 : SegmentCopier::kSumsqInPlace, const_cast<void *>(src), dsts, b.data(), count,
+                                 as_stream(hip_stream), DDL_FLOAT, wire_dtype, divisor, ops, nullptr, want, sq);
+        });
+    });
+}
+
 int ddl_pack_cvt(void *dst, const void *const *srcs, const size_t *elements, int count, int wire_dtype,
                  void *hip_stream) {
     return guarded([&] {
@@ -643,6 +707,59 @@ int ddl_testing_thread_fused_allreduce_wire_fb(int nranks, int count, const void
                                                               DDL_FLOAT, residuals);
         if (subplans) *subplans = j;
     });
+}
+
+int ddl_testing_thread_fused_allreduce_sumsq(int nranks, int count, const void *const *srcs, void *const *dsts,
+                                             const size_t *elements, const int *ops, int wire_dtype, void *hip_stream,
+                                             size_t *subplans, const unsigned char *want, double *sumsq_out,
+                                             size_t *cut_segs, size_t *cut_elems, int max_cuts, int *ncuts) {
+    return guarded([&] {
+        DDL_REQUIRE(nranks >= 1 && nranks <= 64 && count >= 1 && srcs && dsts && elements && want && sumsq_out,
+                    DDL_STATUS_INVALID_ARGUMENT, "bad thread fused allreduce");
+        for (int i = 0; ops && i < count; ++i) {
+            check_allreduce_op(ops[i], DDL_FLOAT);
+            DDL_REQUIRE(!op_is_minmax(ops[i]), DDL_STATUS_INVALID_ARGUMENT, "the sum of squares takes SUM or AVG");
+        }
+        std::vector<size_t> b(count);
+        if (wire_dtype) b = wire_bytes(elements, count, wire_dtype);
+        else
+            for (int i = 0; i < count; ++i) b[i] = elements[i] * sizeof(float);
+        std::vector<std::pair<size_t, size_t>> cuts;
+        const size_t j = thread_world(nranks).fused_allreduce(
+            srcs, dsts, b.data(), count, wire_dtype ? wire_dtype : DDL_FLOAT, as_stream(hip_stream), config().ring(),
+            (size_t)config().fusion_pipeline_bytes.load(), ops, wire_dtype ? DDL_FLOAT : 0, nullptr, want, sumsq_out, &cuts);
+        if (subplans) *subplans = j;
+        if (ncuts) *ncuts = (int)cuts.size();
+        for (int k = 0; k < max_cuts && k < (int)cuts.size() && cut_segs && cut_elems; ++k) {
+            cut_segs[k] = cuts[k].first;
+            cut_elems[k] = cuts[k].second;
+        }
+    });
+}
+
+// DDL_ALLREDUCE_SUMSQ with the value's address as an argument (ddl_amd_testing.h): the deployment entry
+// points with the bit and a ddl_sumsq_arg per request, nothing else.
+int ddl_allreduce_submit_sumsq(ddl_communicator_id id, const char *key, const void *in, void *out, size_t elements,
+                               int dtype, int op, void *hip_stream, ddl_done_fn done, void *user, double *sumsq) {
+    if (!sumsq) return ddl_allreduce_submit(id, key, in, out, elements, dtype, op, hip_stream, done, user);
+    ddl_sumsq_arg arg{user, sumsq};
+    return ddl_allreduce_submit(id, key, in, out, elements, dtype, op | DDL_ALLREDUCE_SUMSQ, hip_stream, done, &arg);
+}
+
+int ddl_allreduce_submit_batch_sumsq(ddl_communicator_id id, int count, const char *const *keys,
+                                     const void *const *ins, void *const *outs, const size_t *elements,
+                                     const int *dtypes, int op, void *hip_stream, ddl_done_fn done,
+                                     void *const *users, double *const *sumsqs) {
+    if (!sumsqs || count <= 0)
+        return ddl_allreduce_submit_batch(id, count, keys, ins, outs, elements, dtypes, op, hip_stream, done, users);
+    std::vector<ddl_sumsq_arg> args((size_t)count);
+    std::vector<void *> ptrs((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        args[(size_t)i] = ddl_sumsq_arg{users ? users[i] : nullptr, sumsqs[i]};
+        ptrs[(size_t)i] = &args[(size_t)i];
+    }
+    return ddl_allreduce_submit_batch(id, count, keys, ins, outs, elements, dtypes, op | DDL_ALLREDUCE_SUMSQ, hip_stream,
+                                      done, ptrs.data());
 }
 
 int ddl_testing_thread_transport(int rccl, long long *loopback_pairs) {

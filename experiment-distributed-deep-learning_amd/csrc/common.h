@@ -258,8 +258,20 @@ public:
     // segments where they are (`flat` unused, the other segments untouched). Without an AVG
     // segment, or with divisor 1, dir 0 / 1 are the plain copies and kDivInPlace posts nothing.
     static constexpr int kDivInPlace = 2;
+    // The sum of squares (DDL_ALLREDUCE_SUMSQ; `want` one byte per segment, null = none;
+    // `sumsq` `count` doubles of PINNED host memory that stay valid until the work posted here has
+    // run): a scatter (dir 1) of DDL_FLOAT segments with want[i] != 0 for some non-empty segment is one
+    // launch of k_seg_sumsq in place of k_seg — it stores what k_seg would and leaves one fp64
+    // partial per 1 KiB tile of the wanted segments — followed by the finishing kernel and an async
+    // copy of the `count` results into `sumsq` on `stream` (+0.0 for unwanted and empty segments).
+    // Every other launch is the kernel it was; its `sumsq` entries are +0.0 at return. The order of
+    // the additions: include/ddl_amd.h. dir kSumsqInPlace: the same reduction, read-only, over
+    // segments that already hold their results (`flat` and `ops` unused; nothing posted if nothing
+    // is wanted).
+    static constexpr int kSumsqInPlace = 3;
     void run(int dir, void *flat, void *const *segs, const size_t *bytes, int count, hipStream_t stream,
-             int dtype = 0, int divisor = 1, const int *ops = nullptr);
+             int dtype = 0, int divisor = 1, const int *ops = nullptr, const unsigned char *want = nullptr,
+             double *sumsq = nullptr);
     // The converting copies of the wire compression (ddl_allreduce_wire): the tensors hold `src_dtype`
     // (DDL_FLOAT) elements, the flat buffer `wire_dtype` (DDL_HALF / DDL_BFLOAT16) ones. `wire_bytes[i]`
     // = segment i's bytes on the FLAT side (elements x 2), so offsets, tiles and flat_bytes are those
@@ -272,17 +284,22 @@ public:
     // segment the launch is the feedback-free CvtPackOp<WIRE, false>, unchanged.
     void run_cvt(int dir, void *flat, void *const *segs, const size_t *wire_bytes, int count, hipStream_t stream,
                  int src_dtype, int wire_dtype, int divisor = 1, const int *ops = nullptr,
-                 void *const *residuals = nullptr);
+                 void *const *residuals = nullptr,
+                 // dir 1 / kSumsqInPlace: the sums of squares as in run(), in the compressed order
+                 // (512 elements per tile, 8 per lane)
+                 const unsigned char *want = nullptr, double *sumsq = nullptr);
     static size_t flat_bytes(const size_t *bytes, int count);
 
 private:
     void run_(int dir, void *flat, void *const *segs, const size_t *bytes, int count, hipStream_t stream, int dtype,
-              int divisor, const int *ops, int wire, void *const *residuals);
+              int divisor, const int *ops, int wire, void *const *residuals, const unsigned char *want, double *sumsq);
     struct Slot {
         void *host = nullptr, *dev = nullptr;
         size_t cap = 0;
         void *idx = nullptr;  // device tile -> segment map (k_tile_index): a byte or an int32 per tile
         size_t idx_cap = 0;
+        void *stat = nullptr;  // device: the tiles' partial sums of squares, then one result per segment
+        size_t stat_cap = 0;
         hipEvent_t ready = nullptr;
     };
     Slot &free_slot_();  // a slot whose last table copy has been consumed (grows the pool)

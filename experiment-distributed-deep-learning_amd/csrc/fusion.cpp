@@ -41,7 +41,8 @@ hipEvent_t FusionPipe::event_(size_t i) {
 
 void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<void *> &dsts,
                      const std::vector<size_t> &bytes, int dt, size_t cap, hipStream_t stream, const Allreduce &ar,
-                     const std::vector<int> *ops, int divisor, int src_dt, const std::vector<void *> *residuals) {
+                     const std::vector<int> *ops, int divisor, int src_dt, const std::vector<void *> *residuals,
+                     PlanSumsq *sumsq) {
     const size_t es = dtype_size(dt);
     DDL_REQUIRE(es != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported dtype " << dt);
     const bool cvt = src_dt != 0 && src_dt != dt;
@@ -49,12 +50,17 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
     DDL_REQUIRE(ses != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported source dtype " << src_dt);
     // gather (dir 0) / scatter (dir 1) of one (sub-)plan: the converting kernels with a wire dtype
     // (`res`: the pack's residuals of a plan with error feedback)
+    // (`want`, `sq`: the unpack's sums of squares, SegmentCopier::run)
     auto copy = [&](int dir, void *fb, void *const *segs, const size_t *b, int n, hipStream_t s, const int *o,
-                    void *const *res = nullptr) {
-        if (cvt) copier.run_cvt(dir, fb, segs, b, n, s, src_dt, dt, divisor, o, dir == 0 ? res : nullptr);
+                    void *const *res = nullptr, const unsigned char *want = nullptr, double *sq = nullptr) {
+        if (cvt) copier.run_cvt(dir, fb, segs, b, n, s, src_dt, dt, divisor, o, dir == 0 ? res : nullptr, want, sq);
         else if (dir == 0) copier.run(0, fb, segs, b, n, s);
-        else copier.run(1, fb, segs, b, n, s, dt, divisor, o);
+        else copier.run(1, fb, segs, b, n, s, dt, divisor, o, want, sq);
     };
+    // the statistic only where some segment asks for it: otherwise every launch below is as without it
+    bool stat = false;
+    for (size_t i = 0; sumsq && sumsq->want && i < bytes.size(); ++i) stat = stat || sumsq->want[i];
+    if (sumsq) sumsq->pieces.clear();
     DDL_REQUIRE(!ops || ops->size() == bytes.size(), DDL_STATUS_INVALID_ARGUMENT, "fusion plan: one op per segment");
     DDL_REQUIRE(!residuals || (cvt && residuals->size() == bytes.size()), DDL_STATUS_INVALID_ARGUMENT,
                 "fusion plan: one residual per segment of a compressed plan");
@@ -73,7 +79,11 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
         copy(0, fb, const_cast<void *const *>(reinterpret_cast<const void *const *>(srcs.data())), bytes.data(),
              (int)srcs.size(), stream, nullptr, residuals ? residuals->data() : nullptr);
         ar(fb, total / es, message);
-        copy(1, fb, dsts.data(), bytes.data(), (int)dsts.size(), stream, ops ? ops->data() : nullptr);
+        double *sq = stat ? sumsq->pinned(bytes.size()) : nullptr;
+        copy(1, fb, dsts.data(), bytes.data(), (int)dsts.size(), stream, ops ? ops->data() : nullptr, nullptr,
+             stat ? sumsq->want : nullptr, sq);
+        for (size_t i = 0; stat && i < bytes.size(); ++i)
+            if (sumsq->want[i]) sumsq->pieces.push_back(PlanSumsq::Piece{i, 0, sq + i});
         return;
     }
     struct Sub {
@@ -82,6 +92,9 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
         std::vector<size_t> bytes;
         std::vector<int> ops;  // of each piece: its segment's (only with `ops`)
         std::vector<void *> res;  // of each piece: its slice of the segment's residual (only with `residuals`)
+        std::vector<unsigned char> want;  // of each piece: its segment's (only with a wanted statistic)
+        std::vector<size_t> seg, elem;    //   and the piece's segment and first element in it
+        bool stat = false;
         size_t flat = 0;
     };
     std::vector<Sub> subs(1);
@@ -104,6 +117,12 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
             // the residual is indexed like the tensor: the same fp32 element offset at a cut
             if (residuals)
                 cur->res.push_back((*residuals)[i] ? static_cast<char *>((*residuals)[i]) + off / es * ses : nullptr);
+            if (stat) {
+                cur->want.push_back(sumsq->want[i]);
+                cur->seg.push_back(i);
+                cur->elem.push_back(off / es);
+                cur->stat = cur->stat || (sumsq->want[i] && len);
+            }
             cur->flat += (len + 255) & ~size_t(255);
             off += len;
         } while (off < bytes[i]);
@@ -123,8 +142,13 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
     auto unpack = [&](size_t j) {
         DDL_HIP(hipStreamWaitEvent(side_, events_[2 + 2 * j], 0));
         dep::wait(side_, events_[2 + 2 * j]);
-        copy(1, buf[j % 2], subs[j].dst.data(), subs[j].bytes.data(), (int)subs[j].dst.size(), side_,
-             ops ? subs[j].ops.data() : nullptr);
+        const Sub &sb = subs[j];
+        double *sq = sb.stat ? sumsq->pinned(sb.bytes.size()) : nullptr;
+        copy(1, buf[j % 2], sb.dst.data(), sb.bytes.data(), (int)sb.dst.size(), side_, ops ? sb.ops.data() : nullptr,
+             nullptr, sb.stat ? sb.want.data() : nullptr, sq);
+        // the pieces of a segment in increasing offset: the sub-plans are unpacked in order
+        for (size_t k = 0; sb.stat && k < sb.bytes.size(); ++k)
+            if (sb.want[k] && sb.bytes[k]) sumsq->pieces.push_back(PlanSumsq::Piece{sb.seg[k], sb.elem[k], sq + k});
     };
     for (size_t j = 0; j < J; ++j) {
         Sub &sb = subs[j];

@@ -27,6 +27,22 @@
 
 namespace ddl {
 
+// The sums of squares of a plan's results (DDL_ALLREDUCE_SUMSQ). A segment is cut into pieces by
+// the sub-plans (tiles restart at every piece); every piece's value — the canonical sum of
+// include/ddl_amd.h over the piece — lands in pinned host memory by an async copy behind the unpack
+// that computed it, on that unpack's stream. The segment's value is its pieces' values added in
+// increasing offset, starting from the first piece's: `pieces` lists them in that order per segment,
+// readable once the plan's work has run.
+struct PlanSumsq {
+    const unsigned char *want = nullptr;     // one per segment: 0 = not wanted
+    std::function<double *(size_t)> pinned;  // n doubles of pinned host memory that outlive the plan's work
+    struct Piece {
+        size_t seg, elem;     // the segment and the piece's first element in it
+        const double *value;  // in the pinned memory
+    };
+    std::vector<Piece> pieces;  // out: the wanted, non-empty pieces
+};
+
 class FusionPipe {
 public:
     FusionPipe() = default;
@@ -54,10 +70,13 @@ public:
     // feedback residuals of DDL_ALLREDUCE_WIRE_FEEDBACK, fp32 arrays indexed like the tensors — a
     // sub-plan's piece takes its residual at the tensor's own element offset. The pack adds them in
     // and rewrites them (k_seg<CvtPackOp<WIRE, true>>); cuts, allreduces and unpacks do not depend on them.
+    // `sumsq` (fp32 tensors only; null or no wanted segment: every launch as without it): the unpack of
+    // every (sub-)plan holding a wanted piece is k_seg_sumsq (pack.hip); cuts, packs and allreduces do
+    // not depend on it.
     void run(const std::vector<const void *> &srcs, const std::vector<void *> &dsts,
              const std::vector<size_t> &bytes, int dtype, size_t cap, hipStream_t stream, const Allreduce &ar,
              const std::vector<int> *ops = nullptr, int divisor = 1, int src_dtype = 0,
-             const std::vector<void *> *residuals = nullptr);
+             const std::vector<void *> *residuals = nullptr, PlanSumsq *sumsq = nullptr);
     size_t subplans() const { return last_subplans_; }  // of the last run
 
     SegmentCopier copier;

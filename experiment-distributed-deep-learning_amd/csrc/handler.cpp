@@ -108,6 +108,7 @@ RequestHandler::~RequestHandler() {
     if (done_thread_.joinable()) done_thread_.join();
     fail_all_(DDL_STATUS_COMM_ERROR);
     for (hipEvent_t e : free_events_) (void)hipEventDestroy(e);
+    for (StatBlock &b : free_stat_) (void)hipHostFree(b.p);
     if (gather_) (void)hipFree(gather_);
     if (dims_) (void)hipFree(dims_);
     for (auto &kv : residuals_)  // the error-feedback residuals live as long as the handler
@@ -126,6 +127,10 @@ void validate(const Request &r, int size) {
                         DDL_STATUS_INVALID_ARGUMENT, "wire dtype " << r.wire << " on a " << dtype_name(r.dtype) << " request");
             DDL_REQUIRE(!r.feedback || r.wire != 0, DDL_STATUS_INVALID_ARGUMENT, "error feedback without a wire dtype");
             DDL_REQUIRE(r.n == 0 || (r.in && r.out), DDL_STATUS_INVALID_ARGUMENT, "null buffer");
+            DDL_REQUIRE(!r.sumsq || r.dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
+                        "the sum of squares is defined for float32 requests, not " << dtype_name(r.dtype));
+            DDL_REQUIRE(!r.sumsq || (!r.host && !op_is_minmax(r.op)), DDL_STATUS_INVALID_ARGUMENT,
+                        "the sum of squares takes a SUM or AVG request in device memory");
             break;
         case kReqBroadcast:
             DDL_REQUIRE(r.root >= 0 && r.root < size, DDL_STATUS_INVALID_ARGUMENT,
@@ -497,6 +502,40 @@ void *RequestHandler::residual_(const Request &r) {
     return res.ptr;
 }
 
+double *RequestHandler::stat_take_(size_t n) {
+    if (round_stat_blocks_.empty() || round_stat_blocks_.back().cap - round_stat_blocks_.back().used < n) {
+        StatBlock b;
+        {
+            std::lock_guard<std::mutex> g(done_mu_);
+            for (size_t k = 0; k < free_stat_.size() && !b.p; ++k)
+                if (free_stat_[k].cap >= n) {
+                    b = free_stat_[k];
+                    free_stat_[k] = free_stat_.back();
+                    free_stat_.pop_back();
+                }
+        }
+        if (!b.p) {
+            b.cap = std::max<size_t>(n, 4096);
+            void *m = nullptr;
+            DDL_HIP(hipHostMalloc(&m, b.cap * sizeof(double), hipHostMallocDefault));
+            b.p = static_cast<double *>(m);
+        }
+        b.used = 0;
+        round_stat_blocks_.push_back(b);
+    }
+    StatBlock &b = round_stat_blocks_.back();
+    double *p = b.p + b.used;
+    b.used += n;
+    return p;
+}
+
+void RequestHandler::stat_in_place_(size_t req, void *out, size_t bytes) {
+    const unsigned char want = 1;
+    double *sq = stat_take_(1);
+    fp_.copier.run(SegmentCopier::kSumsqInPlace, nullptr, &out, &bytes, 1, stream_, DDL_FLOAT, 1, nullptr, &want, sq);
+    round_stat_.emplace_back(req, sq);
+}
+
 std::unique_lock<std::mutex> RequestHandler::lock_host_group_(const std::vector<Request> &reqs,
                                                               const std::vector<size_t> &group, size_t es, bool host) {
     if (!host) return {};
@@ -605,15 +644,21 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
                 }
             } else if (data_->size() == 1 && config().one_rank_shortcut.load()) {
                 // a one-rank world: the sum is the input; move bytes only where out != in (nothing
-                // is communicated, so nothing is compressed either)
+                // is communicated, so nothing is compressed either — and a sum of squares is taken in
+                // the uncompressed order, in place)
+                size_t q = p.req_begin;
                 plan_slices(p, reqs, g.second, ses, [&](const char *s, char *d, size_t n) {
                     if (s != d && n) DDL_HIP(hipMemcpyAsync(d, s, n, hipMemcpyDeviceToDevice, stream_));
+                    if (reqs[g.second[q]].sumsq && n) stat_in_place_(g.second[q], d, n);
+                    ++q;
                 });
             } else if (p.req_begin == p.req_end && !comp) {
                 const Request &r = reqs[g.second[p.req_begin]];
                 const size_t cnt = p.elem_end - p.elem_begin;
                 data_->allreduce(static_cast<const char *>(r.in) + p.elem_begin * es,
                                  static_cast<char *>(r.out) + p.elem_begin * es, cnt, dt, r.op, stream_);
+                // no unpack to take it from: one read-only pass over the finished slice
+                if (r.sumsq && cnt) stat_in_place_(g.second[p.req_begin], static_cast<char *>(r.out) + p.elem_begin * es, cnt * es);
             } else {
                 std::vector<const void *> srcs;
                 std::vector<void *> dsts;
@@ -632,11 +677,21 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
                 for (size_t q = p.req_begin; q <= p.req_end && !resid.empty(); ++q)
                     res.push_back(resid[q] ? static_cast<char *>(resid[q]) + (q == p.req_begin ? p.elem_begin : 0) * ses
                                            : nullptr);
+                // the sums of squares (Request::sumsq, rank-local like the op): taken by the unpack
+                std::vector<unsigned char> want;
+                PlanSumsq ps;
+                for (size_t q = p.req_begin; q <= p.req_end; ++q) want.push_back(reqs[g.second[q]].sumsq ? 1 : 0);
+                const bool stat = std::find(want.begin(), want.end(), 1) != want.end();
+                if (stat) {
+                    ps.want = want.data();
+                    ps.pinned = [this](size_t n) { return stat_take_(n); };
+                }
                 fp_.run(srcs, dsts, bytes, dt, (size_t)config().fusion_pipeline_bytes.load(), stream_,
                         [&](void *buf, size_t elems, size_t message) {
                             data_->allreduce(buf, buf, elems, dt, kind, stream_, message);
                         },
-                        &ops, data_->size(), sdt, resid.empty() ? nullptr : &res);
+                        &ops, data_->size(), sdt, resid.empty() ? nullptr : &res, stat ? &ps : nullptr);
+                for (const PlanSumsq::Piece &pc : ps.pieces) round_stat_.emplace_back(g.second[p.req_begin + pc.seg], pc.value);
             }
             finish_plan_(p, reqs, g.second, dones, nplans);
         }
@@ -863,6 +918,8 @@ void RequestHandler::execute_(const std::vector<ReqId> &ids, int forced) {
     int status = forced;
     const clk::time_point t1 = timed ? clk::now() : clk::time_point();
     round_events_.clear();
+    round_stat_.clear();
+    round_stat_blocks_.clear();
     if (forced == DDL_STATUS_OK) try {
         for (const Request &r : reqs)
             DDL_REQUIRE(r.type == reqs[0].type, DDL_STATUS_COMM_ERROR, "agreed requests of mixed types");
@@ -880,6 +937,8 @@ void RequestHandler::execute_(const std::vector<ReqId> &ids, int forced) {
     rd.reqs = std::move(reqs);
     rd.dones = std::move(dones);
     rd.events.swap(round_events_);
+    rd.stat.swap(round_stat_);
+    rd.stat_blocks.swap(round_stat_blocks_);
     rd.status = status;
     rd.nplans = nplans;
     rd.t0 = t0;
@@ -923,6 +982,22 @@ void RequestHandler::complete_(Round &rd) {
     int status = rd.status;
     std::vector<char> fired(rd.reqs.size(), 0);
     size_t synced = kNoPlan;  // dones are in plan order: wait for each plan's event once
+    // a request's sum of squares: its pieces' values added in increasing element offset, from the
+    // first piece's value (+0.0 without a piece). The values were copied to pinned memory on the
+    // plans' streams ahead of the plan events waited for below, the last piece's plan last.
+    std::vector<std::vector<const double *>> pieces;
+    if (!rd.stat.empty()) {
+        pieces.resize(rd.reqs.size());
+        for (const auto &sp : rd.stat) pieces[sp.first].push_back(sp.second);
+    }
+    auto write_sumsq = [&](size_t req) {
+        const Request &r = rd.reqs[req];
+        if (!r.sumsq) return;
+        double v = 0.0;
+        if (req < pieces.size())
+            for (size_t k = 0; k < pieces[req].size(); ++k) v = k == 0 ? *pieces[req][k] : v + *pieces[req][k];
+        *r.sumsq = v;
+    };
     for (const Done &d : rd.dones) {
         if (status == DDL_STATUS_OK && d.plan != kNoPlan && d.plan != synced) {
             hipError_t he = wait_plan(rd.events[d.plan]);
@@ -931,6 +1006,7 @@ void RequestHandler::complete_(Round &rd) {
         }
         const Request &r = rd.reqs[d.req];
         fired[d.req] = 1;
+        if (status == DDL_STATUS_OK) write_sumsq(d.req);
         if (r.done) r.done(status == DDL_STATUS_OK ? d.status : status, r.user);
     }
     for (size_t i = 0; i < rd.reqs.size(); ++i)
@@ -939,8 +1015,10 @@ void RequestHandler::complete_(Round &rd) {
     if (status == DDL_STATUS_OK) {  // waited for: safe to record again
         std::lock_guard<std::mutex> g(done_mu_);
         free_events_.insert(free_events_.end(), rd.events.begin(), rd.events.end());
+        free_stat_.insert(free_stat_.end(), rd.stat_blocks.begin(), rd.stat_blocks.end());
     } else {
         for (hipEvent_t e : rd.events) (void)hipEventDestroy(e);
+        for (StatBlock &b : rd.stat_blocks) retire_host(b.p);  // a copy into it may still be pending
         if (rd.status == DDL_STATUS_OK) {  // a device failure the engine thread has not seen
             {
                 std::lock_guard<std::mutex> g(mu_);
@@ -951,6 +1029,8 @@ void RequestHandler::complete_(Round &rd) {
         }
     }
     rd.events.clear();
+    rd.stat.clear();
+    rd.stat_blocks.clear();
     const size_t n = rd.reqs.size();
     rd.reqs.clear();  // the requests' input-ready events go with them
     {

@@ -57,6 +57,7 @@ struct Request {
     int op = 0;                       // allreduce: SUM / AVG / MIN / MAX (the wire flag decoded into `wire`)
     int wire = 0;                     // allreduce: wire dtype of a compressed fp32 request (0: its own dtype)
     bool feedback = false;            // allreduce: DDL_ALLREDUCE_WIRE_FEEDBACK (only with `wire`; rank-local)
+    double *sumsq = nullptr;          // allreduce: where the sum of squares of `out` goes before done() (host; rank-local)
     int root = 0;                     // broadcast: TensorBroadcastRequest::rootRank()
     size_t first_dim = 0;             // allgather: rows of `in` (n = first_dim * row_elems)
     size_t row_elems = 1;             //   elements per row (the shape without its first dim)
@@ -109,6 +110,17 @@ private:
     std::vector<ReqId> agreed_ids_(const Agreed &a);  // learns new ids (string rounds)
     void forget_ids_();                                 // the id table was cleared
     void mark_cached_(const ReqId &id, Request &r);
+    // Pinned host memory for the piece values of the sums of squares (DDL_ALLREDUCE_SUMSQ): the
+    // engine thread hands out doubles of the round it is enqueuing (stat_take_), the round carries its
+    // blocks to the completion, which returns them to free_stat_ (done_mu_) once the round's events
+    // have been waited for. No allocation in steady state; blocks are freed with the handler.
+    struct StatBlock {
+        double *p = nullptr;
+        size_t cap = 0, used = 0;
+    };
+    double *stat_take_(size_t n);
+    // the in-place, read-only sum of squares (SegmentCopier::kSumsqInPlace) of reqs[req]'s slice on stream_
+    void stat_in_place_(size_t req, void *out, size_t bytes);
     struct Done {
         size_t plan;  // index into the round's plan events (kNoPlan: nothing to wait for)
         size_t req;
@@ -125,6 +137,10 @@ private:
         std::vector<Request> reqs;
         std::vector<Done> dones;
         std::vector<hipEvent_t> events;
+        // the sums of squares asked for: (request, its piece's value in pinned memory), a request's
+        // pieces in increasing element offset; the pinned blocks the values live in
+        std::vector<std::pair<size_t, const double *>> stat;
+        std::vector<StatBlock> stat_blocks;
         int status = 0;
         size_t nplans = 0;
         std::chrono::steady_clock::time_point t0, t1, t2;  // take / enqueue phase bounds (log)
@@ -179,6 +195,8 @@ private:
     void *dims_ = nullptr;    // allgather first-dim exchange
     size_t dims_bytes_ = 0;
     std::vector<hipEvent_t> round_events_;  // plan events of the round being enqueued (engine thread)
+    std::vector<std::pair<size_t, const double *>> round_stat_;  // and its sums of squares (Round::stat)
+    std::vector<StatBlock> round_stat_blocks_;
 
     std::mutex mu_;
     std::condition_variable cv_;       // new registrations / stop
@@ -203,6 +221,7 @@ private:
     std::condition_variable done_cv_;
     std::deque<Round> rounds_;
     std::vector<hipEvent_t> free_events_;
+    std::vector<StatBlock> free_stat_;
     unsigned long long rounds_queued_ = 0, rounds_done_ = 0;
     bool done_stop_ = false;
     std::thread done_thread_;

@@ -33,10 +33,11 @@ struct SegDesc {
     uint64_t ptr;   // segment address (tensor side)
     uint64_t off;   // offset in the flat buffer (256-byte aligned)
     uint64_t len;   // bytes
-    uint32_t vec;   // kSegVec: ptr is 16-byte aligned (16-byte units, else elements); kSegAvg
+    uint32_t vec;   // kSegVec: ptr is 16-byte aligned (16-byte units, else elements); kSegAvg; kSegStat
     uint32_t tile0; // segment-aligned tiling: index of the segment's first tile
 };
-constexpr uint32_t kSegVec = 1, kSegAvg = 2;
+// kSegStat: the segment's sum of squares is wanted (k_seg_sumsq only; the other kernels never see it)
+constexpr uint32_t kSegVec = 1, kSegAvg = 2, kSegStat = 4;
 
 // Segment-aligned tiling: every segment is cut into tiles of kSegTile bytes that restart at the
 // segment start, so a tile never crosses a segment and its workgroup needs no per-chunk search:
@@ -362,15 +363,168 @@ template <int WIRE> struct CvtUnpackOp {
     }
 };
 
+// ---- the unpacks with the sum of squares (DDL_ALLREDUCE_SUMSQ) -----------------------------
+// k_seg_sumsq: the plain, the dividing (WIRE < 0: fp32 flat buffer, DivOp<kDivF32>'s quotient) and the
+// converting scatter (WIRE = kWireF16 / kWireBF16: CvtUnpackOp's widening and quotient) of fp32
+// tensors that also leave, for every tile of a segment flagged kSegStat, the fp64 sum of the squares
+// of the fp32 values the tile stored in partials[tile]. Launched only when some segment of the launch
+// carries the flag; a segment without it is stored as k_seg stores it and writes no partial.
+// The order of the additions (include/ddl_amd.h, tests/_sumsq_helpers.py): T = 256 elements per tile
+// and E = 4 per lane (WIRE < 0), or T = 512 and E = 8. Lane l of tile t owns elements
+// t*T + l*E .. + E-1 of the segment WHATEVER the tensor's alignment: acc = +0.0, acc += x*x left to
+// right in fp64 (x*x is exact in fp64 for every fp32 x, so an fma contraction of acc + x*x changes no
+// bit), elements past the segment's end count as +0.0; then the butterfly s[l] += s[l ^ d] for
+// d = 32, 16, 8, 4, 2, 1 (every lane ends with the same bits: each step adds the same two numbers on
+// both sides); lane 0 writes the tile's partial. The finishing kernels below combine the partials in
+// groups of 4096. No atomic anywhere.
+// The flat side of a lane's E elements is one aligned 16-byte unit inside the segment's 256-byte
+// padded slot, so it is always one vector load; the tensor side is vector stores where the tensor is
+// 16-byte aligned and the lane holds E whole elements, else element by element.
+// flat == nullptr: in place and read-only — the same reduction over tensors that already hold their
+// results (nothing is divided or stored), the same lanes owning the same elements.
+__device__ inline double wave_sum(double s) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+    return s;
+}
+
+template <int WIRE, bool NARROW>
+__global__ void __launch_bounds__(64) k_seg_sumsq(const char *flat, const SegDesc *__restrict__ d,
+                                                  const uint32_t *__restrict__ blk_base, const void *__restrict__ map,
+                                                  float divisor, double *__restrict__ partials) {
+    constexpr int E = WIRE < 0 ? 4 : 8;
+    constexpr uint64_t kUnit = WIRE < 0 ? 4 : 2;  // bytes of SegDesc::len per element
+    const unsigned tile = blockIdx.x;
+    const int seg = tile_segment<NARROW>(tile, blk_base, map);
+    const SegDesc sd = d[seg];
+    const uint64_t n = sd.len / kUnit;
+    const uint64_t e0 = (uint64_t)(tile - sd.tile0) * (kSegTile / kUnit) + threadIdx.x * E;
+    const int nv = e0 >= n ? 0 : n - e0 < (uint64_t)E ? (int)(n - e0) : E;  // the lane's elements inside the segment
+    float *tp = reinterpret_cast<float *>(sd.ptr) + e0;
+    const bool whole = (sd.vec & kSegVec) != 0 && nv == E;
+    float x[E];
+#pragma unroll
+    for (int k = 0; k < E; ++k) x[k] = 0.0f;
+    if (flat) {
+        if (nv > 0) {
+            const u32x4 raw = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(flat + sd.off + e0 * kUnit));
+            if constexpr (WIRE < 0) {
+                F32x4 v;
+                v.v = raw;
+#pragma unroll
+                for (int k = 0; k < E; ++k) x[k] = v.e[k];
+            } else {
+                Wire8<typename WireTraits<WIRE>::T> w;
+                w.v = raw;
+#pragma unroll
+                for (int k = 0; k < E; ++k) x[k] = WireTraits<WIRE>::widen(w.e[k]);
+            }
+            if (sd.vec & kSegAvg) {
+#pragma unroll
+                for (int k = 0; k < E; ++k) x[k] = x[k] / divisor;
+            }
+            if (whole) {
+#pragma unroll
+                for (int h = 0; h < E / 4; ++h) {
+                    F32x4 o;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) o.e[k] = x[4 * h + k];
+                    __builtin_nontemporal_store(o.v, reinterpret_cast<u32x4 *>(tp) + h);
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < E; ++k)
+                    if (k < nv) tp[k] = x[k];
+            }
+        }
+    } else if (whole) {
+#pragma unroll
+        for (int h = 0; h < E / 4; ++h) {
+            F32x4 v;
+            v.v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(tp) + h);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) x[4 * h + k] = v.e[k];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < E; ++k)
+            if (k < nv) x[k] = tp[k];
+    }
+    if (!(sd.vec & kSegStat)) return;  // (the whole workgroup: one segment per tile)
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < E; ++k) {
+        const double v = (double)x[k];
+        acc += k < nv ? v * v : 0.0;
+    }
+    acc = wave_sum(acc);
+    if (threadIdx.x == 0) partials[tile] = acc;
+}
+
+// The finishing kernels: a segment's tile partials (nt of them, contiguous from tile0) into out[seg], in a
+// fixed order that only nt decides. A GROUP is up to kFinGroup = 4096 consecutive values: lane l adds
+// values l, l + 64, l + 128, ... of the group to +0.0 in that order (at most 64 additions), then the
+// butterfly of k_seg_sumsq gives the group's value. k_sumsq_finish reduces every group of the
+// partials (one workgroup per (segment, group): a 256 MiB segment is 64 independent groups, not one
+// lane chain of 4096 dependent loads); a segment of one group is finished by it. k_sumsq_finish2
+// reduces the group values of a longer segment, themselves one group (nt <= 4096^2: pieces up to
+// 16 GiB, checked on the host). A segment without kSegStat gets +0.0.
+// Group values of segment seg sit at lvl[tile0 / 4096 + seg + g]: distinct for distinct (seg, g).
+constexpr uint64_t kFinGroup = 4096;
+
+__device__ inline double group_sum(const double *__restrict__ v, uint64_t m) {
+    double acc = 0.0;
+#pragma unroll 8
+    for (uint64_t t = threadIdx.x; t < m; t += 64) acc += v[t];
+    return wave_sum(acc);
+}
+
+__global__ void __launch_bounds__(64) k_sumsq_finish(const SegDesc *__restrict__ d, const double *__restrict__ partials,
+                                                     double *__restrict__ lvl, double *__restrict__ out) {
+    const unsigned seg = blockIdx.x;
+    const uint64_t g = blockIdx.y;
+    const SegDesc sd = d[seg];
+    if (!(sd.vec & kSegStat)) {
+        if (g == 0 && threadIdx.x == 0) out[seg] = 0.0;
+        return;
+    }
+    const uint64_t nt = (sd.len + kSegTile - 1) / kSegTile, groups = (nt + kFinGroup - 1) / kFinGroup;
+    if (g >= groups) return;
+    const uint64_t left = nt - g * kFinGroup;
+    const double acc = group_sum(partials + sd.tile0 + g * kFinGroup, left < kFinGroup ? left : kFinGroup);
+    if (threadIdx.x == 0) (groups == 1 ? out[seg] : lvl[sd.tile0 / kFinGroup + seg + g]) = acc;
+}
+
+__global__ void __launch_bounds__(64) k_sumsq_finish2(const SegDesc *__restrict__ d, const double *__restrict__ lvl,
+                                                      double *__restrict__ out) {
+    const unsigned seg = blockIdx.x;
+    const SegDesc sd = d[seg];
+    const uint64_t nt = (sd.len + kSegTile - 1) / kSegTile, groups = (nt + kFinGroup - 1) / kFinGroup;
+    if (!(sd.vec & kSegStat) || groups <= 1) return;  // finished by k_sumsq_finish
+    const double acc = group_sum(lvl + sd.tile0 / kFinGroup + seg, groups);
+    if (threadIdx.x == 0) out[seg] = acc;
+}
+
+template <int WIRE>
+void launch_sumsq(bool narrow, dim3 g, hipStream_t stream, const char *fl, const SegDesc *dd, const uint32_t *db,
+                  const void *map, float divisor, double *partials) {
+    if (narrow) hipLaunchKernelGGL((k_seg_sumsq<WIRE, true>), g, dim3(64), 0, stream, fl, dd, db, map, divisor, partials);
+    else hipLaunchKernelGGL((k_seg_sumsq<WIRE, false>), g, dim3(64), 0, stream, fl, dd, db, map, divisor, partials);
+}
+
 // What one run_ is, decided once: its kernel, its tables, its happens-before spans and its label.
 // kCvtUnpack and kCvtUnpackAvg share a kernel (the AVG segments carry kSegAvg).
-enum SegOp : int { kPack, kUnpack, kUnpackAvg, kDivide, kCvtPack, kCvtPackFb, kCvtUnpack, kCvtUnpackAvg };
+// kUnpackStat / kCvtUnpackStat / kSumsq: k_seg_sumsq (fp32 flat, wire flat, in place) and its finishing kernel.
+enum SegOp : int {
+    kPack, kUnpack, kUnpackAvg, kDivide, kCvtPack, kCvtPackFb, kCvtUnpack, kCvtUnpackAvg, kUnpackStat, kCvtUnpackStat, kSumsq
+};
 struct SegOpInfo {
     const char *label;  // of the happens-before trace
     bool gather;        // segments read, flat buffer written; else the segments written
 };
 constexpr SegOpInfo kSegOps[] = {{"pack", true},     {"unpack", false},     {"unpack avg", false}, {"divide", false},
-                                 {"pack cvt", true}, {"pack cvt fb", true}, {"unpack cvt", false}, {"unpack cvt avg", false}};
+                                 {"pack cvt", true}, {"pack cvt fb", true}, {"unpack cvt", false}, {"unpack cvt avg", false},
+                                 {"unpack sumsq", false}, {"unpack cvt sumsq", false}, {"sumsq", true}};
 
 }  // namespace
 
@@ -381,6 +535,7 @@ SegmentCopier::~SegmentCopier() {
         if (sl.host) (void)hipHostFree(sl.host);
         if (sl.dev) (void)hipFree(sl.dev);
         if (sl.idx) (void)hipFree(sl.idx);
+        if (sl.stat) (void)hipFree(sl.stat);
     }
 }
 
@@ -417,18 +572,19 @@ size_t SegmentCopier::flat_bytes(const size_t *bytes, int count) {
 }
 
 void SegmentCopier::run(int dir, void *flat, void *const *segs, const size_t *bytes, int count,
-                        hipStream_t stream, int dtype, int divisor, const int *ops) {
-    run_(dir, flat, segs, bytes, count, stream, dtype, divisor, ops, 0, nullptr);
+                        hipStream_t stream, int dtype, int divisor, const int *ops, const unsigned char *want,
+                        double *sumsq) {
+    run_(dir, flat, segs, bytes, count, stream, dtype, divisor, ops, 0, nullptr, want, sumsq);
 }
 
 void SegmentCopier::run_cvt(int dir, void *flat, void *const *segs, const size_t *wire_bytes, int count,
                             hipStream_t stream, int src_dtype, int wire_dtype, int divisor, const int *ops,
-                            void *const *residuals) {
+                            void *const *residuals, const unsigned char *want, double *sumsq) {
     DDL_REQUIRE(src_dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
                 "wire compression is defined for float32 sources, not " << dtype_name(src_dtype));
     DDL_REQUIRE(wire_dtype == DDL_HALF || wire_dtype == DDL_BFLOAT16, DDL_STATUS_UNSUPPORTED_DTYPE,
                 "wire dtype " << wire_dtype << " is neither float16 nor bfloat16");
-    DDL_REQUIRE(dir == 0 || dir == 1, DDL_STATUS_INVALID_ARGUMENT, "copier direction " << dir);
+    DDL_REQUIRE(dir == 0 || dir == 1 || dir == kSumsqInPlace, DDL_STATUS_INVALID_ARGUMENT, "copier direction " << dir);
     DDL_REQUIRE(divisor >= 1, DDL_STATUS_INVALID_ARGUMENT, "divisor " << divisor);
     for (int i = 0; i < count && segs && wire_bytes; ++i)
         DDL_REQUIRE(wire_bytes[i] % 2 == 0 && reinterpret_cast<uintptr_t>(segs[i]) % 4 == 0, DDL_STATUS_INVALID_ARGUMENT,
@@ -443,14 +599,38 @@ void SegmentCopier::run_cvt(int dir, void *flat, void *const *segs, const size_t
         fb = true;
     }
     run_(dir, flat, segs, wire_bytes, count, stream, src_dtype, divisor, dir == 1 ? ops : nullptr, wire_dtype,
-         fb ? residuals : nullptr);
+         fb ? residuals : nullptr, dir == 0 ? nullptr : want, sumsq);
 }
 
 // wire == 0: the plain copies and the dividing scatter over `bytes` of `dtype`; else the converting
-// copies, `bytes` the wire-side lengths; `residuals` (a converting pack only): the feedback pack
+// copies, `bytes` the wire-side lengths; `residuals` (a converting pack only): the feedback pack;
+// `want` / `sumsq` (a scatter or kSumsqInPlace): the sums of squares (common.h)
 void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *bytes, int count, hipStream_t stream,
-                         int dtype, int divisor, const int *ops, int wire, void *const *residuals) {
+                         int dtype, int divisor, const int *ops, int wire, void *const *residuals,
+                         const unsigned char *want, double *sumsq) {
     if (count <= 0) return;
+    // the statistic only where some non-empty segment of a scatter asks for it: every other launch
+    // is the kernel it was, its tables exactly as before
+    bool stat = false;
+    if (want && bytes && (dir == 1 || dir == kSumsqInPlace)) {
+        DDL_REQUIRE(sumsq, DDL_STATUS_INVALID_ARGUMENT, "sum of squares without an output");
+        for (int i = 0; i < count; ++i) {
+            sumsq[i] = 0.0;  // a launch that leaves the statistic out, an empty segment (host memory: ours until posted)
+            stat = stat || (want[i] && bytes[i] != 0);
+        }
+    }
+    if (dir == kSumsqInPlace) {
+        if (!stat) return;  // nothing wanted: the zeros above are the answer
+        ops = nullptr;      // the segments hold their results: nothing is divided
+    }
+    if (stat) {
+        DDL_REQUIRE(dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
+                    "the sum of squares is defined for float32 tensors, not " << dtype_name(dtype));
+        const size_t unit = wire ? 2 : 4;
+        for (int i = 0; i < count; ++i)
+            DDL_REQUIRE(bytes[i] % unit == 0 && reinterpret_cast<uintptr_t>(segs[i]) % 4 == 0, DDL_STATUS_INVALID_ARGUMENT,
+                        "segment " << i << " is not whole, aligned float32 elements");
+    }
     // the quotient only where some segment asks for it and it is not the identity: every other
     // launch is the plain copy, its kernels and tables exactly as before
     bool div = false;
@@ -459,12 +639,17 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
     if (dir == kDivInPlace) {
         if (!div) return;  // nothing to divide: the segments already hold their results
         flat = nullptr;
+    } else if (dir == kSumsqInPlace) {
+        flat = nullptr;
     } else {
         DDL_REQUIRE(dir == 0 || dir == 1, DDL_STATUS_INVALID_ARGUMENT, "copier direction " << dir);
         DDL_REQUIRE(!div || dir == 1, DDL_STATUS_INVALID_ARGUMENT, "the quotient belongs to the unpack");
     }
-    DDL_REQUIRE((flat || dir == kDivInPlace) && segs && bytes, DDL_STATUS_INVALID_ARGUMENT, "null pack arguments");
+    DDL_REQUIRE((flat || dir == kDivInPlace || dir == kSumsqInPlace) && segs && bytes, DDL_STATUS_INVALID_ARGUMENT,
+                "null pack arguments");
     const SegOp op = dir == kDivInPlace ? kDivide
+                     : dir == kSumsqInPlace ? kSumsq
+                     : stat ? (wire ? kCvtUnpackStat : kUnpackStat)
                      : wire ? (dir == 0 ? (residuals ? kCvtPackFb : kCvtPack) : div ? kCvtUnpackAvg : kCvtUnpack)
                      : dir == 0 ? kPack : div ? kUnpackAvg : kUnpack;
     const size_t es = div ? dtype_size(dtype) : 1;
@@ -481,6 +666,12 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
         own.assign(bytes, bytes + count);
         for (int i = 0; i < count; ++i)
             if (ops[i] != DDL_ALLREDUCE_OP_AVG) own[i] = 0;
+        bytes = own.data();
+    }
+    if (op == kSumsq) {  // in place only the wanted segments have tiles (nothing else is read)
+        own.assign(bytes, bytes + count);
+        for (int i = 0; i < count; ++i)
+            if (!want[i]) own[i] = 0;
         bytes = own.data();
     }
     Slot &sl = free_slot_();
@@ -512,6 +703,7 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
         t[i].len = bytes[i];
         t[i].vec = (reinterpret_cast<uintptr_t>(segs[i]) & 15u) == 0 ? kSegVec : 0;
         if (div && ops[i] == DDL_ALLREDUCE_OP_AVG) t[i].vec |= kSegAvg;
+        if (stat && want[i] && bytes[i]) t[i].vec |= kSegStat;
         t[i].tile0 = (uint32_t)tl;
         off += (bytes[i] + 255) & ~uint64_t(255);
         tl += (bytes[i] + seg_tile - 1) / seg_tile;
@@ -548,6 +740,25 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
         if (narrow) hipLaunchKernelGGL(k_tile_index<true>, ig, dim3(256), 0, stream, dd, count, (uint64_t)tiles, db, sl.idx);
         else hipLaunchKernelGGL(k_tile_index<false>, ig, dim3(256), 0, stream, dd, count, (uint64_t)tiles, db, sl.idx);
         const bool f16 = wire == DDL_HALF;  // of the converting copies: else bf16 (run_cvt)
+        // the statistic's scratch: one partial per tile, the group values, then one result per segment
+        double *partials = nullptr;
+        uint64_t fin_groups = 0;  // of the longest wanted segment
+        const uint64_t lvl_n = tiles / kFinGroup + (uint64_t)count + 1;
+        if (stat) {
+            for (int i = 0; i < count; ++i)
+                if (t[i].vec & kSegStat)
+                    fin_groups = std::max(fin_groups, ((bytes[i] + seg_tile - 1) / seg_tile + kFinGroup - 1) / kFinGroup);
+            DDL_REQUIRE(fin_groups <= kFinGroup, DDL_STATUS_INVALID_ARGUMENT,
+                        "the sum of squares takes pieces of at most " << kFinGroup * kFinGroup << " tiles");
+            const size_t sb = (tiles + lvl_n + (size_t)count) * sizeof(double);
+            if (sb > sl.stat_cap) {
+                retire_device(sl.stat);
+                sl.stat = nullptr;
+                sl.stat_cap = sb + sb / 2;
+                DDL_HIP(hipMalloc(&sl.stat, sl.stat_cap));
+            }
+            partials = static_cast<double *>(sl.stat);
+        }
         switch (op) {
             case kPack: launch<CopyOp<0>>(narrow, g, stream, fl, dd, db, sl.idx); break;
             case kUnpack: launch<CopyOp<1>>(narrow, g, stream, fl, dd, db, sl.idx); break;
@@ -578,6 +789,20 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
                 if (f16) launch<CvtUnpackOp<kWireF16>>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor);
                 else launch<CvtUnpackOp<kWireBF16>>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor);
                 break;
+            case kUnpackStat:
+            case kCvtUnpackStat:
+            case kSumsq:
+                if (!wire) launch_sumsq<-1>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor, partials);
+                else if (f16) launch_sumsq<kWireF16>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor, partials);
+                else launch_sumsq<kWireBF16>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor, partials);
+                break;
+        }
+        if (stat) {  // the segments' values, then to the caller's host memory ahead of whatever it records next
+            double *lvl = partials + tiles, *res = lvl + lvl_n;
+            hipLaunchKernelGGL(k_sumsq_finish, dim3((unsigned)count, (unsigned)fin_groups), dim3(64), 0, stream, dd, partials,
+                               lvl, res);
+            if (fin_groups > 1) hipLaunchKernelGGL(k_sumsq_finish2, dim3((unsigned)count), dim3(64), 0, stream, dd, lvl, res);
+            DDL_HIP(hipMemcpyAsync(sumsq, res, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, stream));
         }
     }
     DDL_HIP(hipGetLastError());
@@ -585,7 +810,7 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
     if (dep::on()) {  // happens-before trace (deptrace.h): the segments and the flat buffer
         std::vector<dep::Access> acc;
         const bool gather = kSegOps[op].gather;
-        if (op != kDivide) acc.push_back(gather ? dep::wr(flat, off) : dep::rd(flat, off));
+        if (op != kDivide && op != kSumsq) acc.push_back(gather ? dep::wr(flat, off) : dep::rd(flat, off));
         const size_t widen = wire ? dtype_size(dtype) / dtype_size(wire) : 1;  // the tensor side in its own bytes
         for (int i = 0; i < count; ++i)
             if (bytes[i])

@@ -284,7 +284,8 @@ void ThreadWorld::allreduce_batch(const void *const *in, void *const *out, const
 
 size_t ThreadWorld::fused_allreduce(const void *const *srcs, void *const *dsts, const size_t *bytes, int count,
                                     int dtype, hipStream_t user, const RingConfig &cfg, size_t cap, const int *ops,
-                                    int src_dtype, void *const *residuals) {
+                                    int src_dtype, void *const *residuals, const unsigned char *want,
+                                    double *sumsq_out, std::vector<std::pair<size_t, size_t>> *cuts) {
     // the plan's kind: MIN / MAX plans hold one kind only (the keyed handler's groups)
     const int kind = ops && count > 0 ? reduce_kind(ops[0]) : DDL_ALLREDUCE_OP_SUM;
     for (int i = 0; ops && i < count; ++i)
@@ -294,6 +295,26 @@ size_t ThreadWorld::fused_allreduce(const void *const *srcs, void *const *dsts, 
     while (pipes_.size() < (size_t)P_) pipes_.emplace_back(new FusionPipe);
     const std::vector<size_t> b(bytes, bytes + count);
     const std::vector<int> o(ops ? ops : nullptr, ops ? ops + count : nullptr);
+    // the piece values: pinned blocks made as the pipes ask for them, freed once `user` has been waited for
+    std::vector<PlanSumsq> stats(want && sumsq_out ? P_ : 0);
+    std::vector<void *> pinned;
+    std::mutex pmu;
+    struct FreePinned {
+        std::vector<void *> &v;
+        ~FreePinned() {
+            for (void *p : v) (void)hipHostFree(p);
+        }
+    } free_pinned{pinned};
+    for (PlanSumsq &ps : stats) {
+        ps.want = want;
+        ps.pinned = [&](size_t n) {
+            void *m = nullptr;
+            DDL_HIP(hipHostMalloc(&m, std::max<size_t>(n, 1) * sizeof(double), hipHostMallocDefault));
+            std::lock_guard<std::mutex> g(pmu);
+            pinned.push_back(m);
+            return static_cast<double *>(m);
+        };
+    }
     run_(user, [&](int r, hipStream_t s) {
         const std::vector<const void *> src(srcs + (size_t)r * count, srcs + (size_t)(r + 1) * count);
         const std::vector<void *> dst(dsts + (size_t)r * count, dsts + (size_t)(r + 1) * count);
@@ -303,8 +324,21 @@ size_t ThreadWorld::fused_allreduce(const void *const *srcs, void *const *dsts, 
             RingConfig c = cfg;
             c.order_bytes = message;
             ex_[r]->allreduce(buf, buf, elems, dtype, s, c, kind);
-        }, ops ? &o : nullptr, P_, src_dtype, residuals ? &res : nullptr);
+        }, ops ? &o : nullptr, P_, src_dtype, residuals ? &res : nullptr, stats.empty() ? nullptr : &stats[r]);
     });
+    if (!stats.empty()) {
+        DDL_HIP(hipStreamSynchronize(user));
+        for (int r = 0; r < P_; ++r) {
+            std::vector<char> first(count, 1);
+            for (int i = 0; i < count; ++i) sumsq_out[(size_t)r * count + i] = 0.0;
+            for (const PlanSumsq::Piece &pc : stats[r].pieces) {
+                double &v = sumsq_out[(size_t)r * count + pc.seg];
+                v = first[pc.seg] ? *pc.value : v + *pc.value;
+                first[pc.seg] = 0;
+                if (r == 0 && cuts && pc.elem) cuts->emplace_back(pc.seg, pc.elem);
+            }
+        }
+    }
     return pipes_[0]->subplans();
 }
 

@@ -177,7 +177,14 @@ public:
     size_t fused_allreduce(const void *const *srcs, void *const *dsts, const size_t *bytes, int count, int dtype,
                            hipStream_t user, const RingConfig &cfg, size_t cap, const int *ops = nullptr,
                            int src_dtype = 0,  // != 0: a compressed plan (FusionPipe::run), bytes on the wire
-                           void *const *residuals = nullptr);  // [r * count + i]: error feedback of a compressed plan
+                           void *const *residuals = nullptr,  // [r * count + i]: error feedback of a compressed plan
+                           // the sums of squares (FusionPipe's PlanSumsq on every rank; fp32 tensors):
+                           // want[i] per segment, sumsq_out[r * count + i] = rank r's pieces of segment i
+                           // added in increasing offset as the keyed handler adds them (+0.0 where not
+                           // wanted); *cuts = rank 0's (segment, first element) of every wanted piece that
+                           // starts inside a segment. Waits for `user` before it returns.
+                           const unsigned char *want = nullptr, double *sumsq_out = nullptr,
+                           std::vector<std::pair<size_t, size_t>> *cuts = nullptr);
 
 private:
     void run_(hipStream_t user, const std::function<void(int, hipStream_t)> &body);

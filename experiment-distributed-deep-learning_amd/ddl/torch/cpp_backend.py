@@ -43,9 +43,17 @@ OP_SUM, OP_AVG = 0, 1  # enum ddl_allreduce_op
 OP_MIN, OP_MAX = 3, 4  # element-wise IEEE 754-2019 minimum / maximum (integers: their order); 2 is not an op
 WIRE_FP16, WIRE_BF16 = 0x100, 0x200  # enum ddl_allreduce_wire: OR-ed into a keyed fp32 device request's op
 WIRE_FEEDBACK = 0x1000  # error feedback: only together with exactly one of the two wire flags
+SUMSQ = 0x2000  # enum ddl_allreduce_stat: `user` points to a SumsqArg (struct ddl_sumsq_arg)
 MEMORY_DEVICE, MEMORY_HOST = 0, 1  # enum ddl_memory
 
 DONE_FN = ctypes.CFUNCTYPE(None, ctypes.c_int, ctypes.c_void_p)
+
+
+class SumsqArg(ctypes.Structure):
+    """struct ddl_sumsq_arg: the `user` of a keyed allreduce whose op carries SUMSQ."""
+    _fields_ = [('user', ctypes.c_void_p), ('sumsq', ctypes.c_void_p)]
+
+
 # ddl_alloc_fn: output allocation of a keyed allgather (first_dim, bytes, user) -> device pointer
 ALLOC_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p)
 
@@ -129,6 +137,20 @@ class CPPBackend:
         sig('ddl_allreduce_submit_mem', ci, cid, ctypes.c_char_p, vp, vp, sz, ci, ci, ci, vp, DONE_FN, vp)
         sig('ddl_allreduce_submit_batch_mem', ci, cid, ci, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(vp),
             ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(ci), ci, ci, vp, DONE_FN, ctypes.POINTER(vp))
+        dp = ctypes.POINTER(ctypes.c_double)
+        # (testing library: DDL_ALLREDUCE_SUMSQ with the value's address as an argument)
+        sig('ddl_allreduce_submit_sumsq', ci, cid, ctypes.c_char_p, vp, vp, sz, ci, ci, vp, DONE_FN, vp, dp)
+        sig('ddl_allreduce_submit_batch_sumsq', ci, cid, ci, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(vp),
+            ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(ci), ci, vp, DONE_FN, ctypes.POINTER(vp),
+            ctypes.POINTER(vp))
+        ub = ctypes.POINTER(ctypes.c_ubyte)
+        sig('ddl_unpack_ops_sumsq', ci, ctypes.POINTER(vp), vp, ctypes.POINTER(sz), ctypes.POINTER(ci), ci, ci, ci, vp,
+            ub, dp)
+        sig('ddl_unpack_cvt_sumsq', ci, ctypes.POINTER(vp), vp, ctypes.POINTER(sz), ctypes.POINTER(ci), ci, ci, ci, vp,
+            ub, dp)
+        sig('ddl_testing_thread_fused_allreduce_sumsq', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp),
+            ctypes.POINTER(sz), ctypes.POINTER(ci), ci, vp, ctypes.POINTER(sz), ub, dp, ctypes.POINTER(sz),
+            ctypes.POINTER(sz), ci, ctypes.POINTER(ci))
         sig('ddl_broadcast_submit_mem', ci, cid, ctypes.c_char_p, vp, vp, sz, ci, ci, ci, vp, DONE_FN, vp)
         sig('ddl_allgather_submit_mem', ci, cid, ctypes.c_char_p, vp, sz, sz, ci, ci, vp, ALLOC_FN, DONE_FN, vp)
         sig('ddl_control_channel_open', ctypes.c_longlong, ctypes.c_char_p, sz)

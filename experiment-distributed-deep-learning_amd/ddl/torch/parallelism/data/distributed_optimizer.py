@@ -46,9 +46,26 @@ Cost: one fp32 copy of every compressed gradient in device memory, and a fusion 
 bytes per element instead of 6; what travels between the ranks is unchanged. Call
 `ddl.torch.compression.reset_error_feedback()` after loading a checkpoint and after a change of the
 loss scale by a large factor.
+
+`track_grad_norm=True` (implied by `max_grad_norm` and `skip_nonfinite`): after
+`allreduce_gradients()`, `optimizer.grad_norm` is the global L2 norm of the averaged gradients (a
+float) and `optimizer.found_nonfinite` is `not math.isfinite(grad_norm)`. Every dense fp32 device
+gradient contributes the engine's sum of squares (`allreduce_async(..., sumsq=True)`: taken by the
+kernel that writes the reduced gradient, no second read of it from HBM, and the same bits on every
+rank), on both paths, step() and the `overlap_backward` hooks; every other gradient (other dtypes,
+CPU, sparse values, strided copies) contributes `g.double().pow(2).sum().item()` taken after its
+reduction. The norm is `sqrt(math.fsum(contributions))` — `fsum` is exactly rounded, so the order
+does not matter — divided by the size when `fused_mean` is off (the engine then saw the sums). A
+sum of squares is finite exactly when every element is, so the one number is also the overflow
+check of a loss scaler. `max_grad_norm`: when the norm is finite and exceeds it, every gradient is
+multiplied by `max_grad_norm / (norm + 1e-6)` (`torch.nn.utils.clip_grad_norm_`'s rule; the factor
+is the same double on every rank) with one `torch._foreach_mul_` per device. `skip_nonfinite`: a
+non-finite norm makes step() return without calling the wrapped step(). At size 1 nothing is
+communicated and the norm is torch's.
 """
 import contextlib
 import functools
+import math
 
 import torch
 
@@ -64,6 +81,11 @@ class DataParallelismDistributedOptimizer:
     pin_host_gradients: bool = True
     fused_mean: bool = False
     compression = Compression.none
+    track_grad_norm: bool = False
+    max_grad_norm: float = None
+    skip_nonfinite: bool = False
+    grad_norm: float = None        # of the last allreduce_gradients() (with tracking on)
+    found_nonfinite: bool = False
     _ddl_name = 'DataParallelismDistributedOptimizer'
     _grad_handles = None  # overlap_backward: param -> Handle submitted by its hook
     _syncing = True
@@ -76,6 +98,41 @@ class DataParallelismDistributedOptimizer:
 
     def _op(self) -> int:
         return cb.OP_AVG if self.fused_mean else cb.OP_SUM
+
+    def _tracking(self) -> bool:
+        return bool(self.track_grad_norm or self.max_grad_norm is not None or self.skip_nonfinite)
+
+    @staticmethod
+    def _engine_sumsq(g) -> bool:
+        """Whether the engine takes this gradient's sum of squares (a dense fp32 device tensor)."""
+        return g.is_cuda and not g.is_sparse and g.dtype == torch.float32 and g.is_contiguous()
+
+    @staticmethod
+    def _torch_sumsq(g) -> float:
+        g = g.coalesce().values() if g.is_sparse else g
+        return g.double().pow(2).sum().item()
+
+    def _finish_norm(self, contributions, in_sums: bool) -> None:
+        """grad_norm / found_nonfinite from the contributions, then the clip. `in_sums`: the
+        contributions are those of the summed gradients (fused_mean off), so the norm is divided."""
+        norm = math.nan if any(math.isnan(c) for c in contributions) else math.sqrt(math.fsum(contributions))
+        if in_sums:
+            norm /= self._comm().size
+        self.grad_norm, self.found_nonfinite = norm, not math.isfinite(norm)
+        if self.max_grad_norm is None or self.found_nonfinite or norm <= self.max_grad_norm:
+            return
+        coef = float(self.max_grad_norm) / (norm + 1e-6)
+        by_device = {}
+        for group in self.param_groups:
+            for p in group['params']:
+                if p.grad is None:
+                    continue
+                if p.grad.is_sparse:
+                    p.grad.mul_(coef)
+                else:
+                    by_device.setdefault(p.grad.device, []).append(p.grad)
+        for grads in by_device.values():
+            torch._foreach_mul_(grads, coef)
 
     def _register_overlap_hooks(self) -> None:
         # keys numbered from the last parameter back: the engine runs a round's plans in key
@@ -99,7 +156,8 @@ class DataParallelismDistributedOptimizer:
         if self._pinning() and not g.is_cuda and not g.is_pinned():
             p.grad = g = g.pin_memory()
         self._grad_handles[p] = allreduce_async(g, key, self._comm(), output=g, op=self._op(),
-                                               compression=self.compression)
+                                               compression=self.compression,
+                                               sumsq=self._tracking() and self._engine_sumsq(g))
 
     @contextlib.contextmanager
     def no_sync(self):
@@ -123,13 +181,21 @@ class DataParallelismDistributedOptimizer:
 
     def allreduce_gradients(self) -> None:
         comm = self._comm()
+        track = self._tracking()
         if comm.size <= 1:
+            if track:  # nothing is communicated: the norm of the local gradients
+                self._finish_norm([self._torch_sumsq(p.grad) for group in self.param_groups for p in group['params']
+                                   if p.grad is not None], False)
             return
         # gradients already submitted by the backward hooks (overlap_backward)
         hooked = self._drain_hooked()
         fused = self.fused_mean  # the engine has divided already
+        # the squared norm's contributions, all of the sums (fused_mean off) or all of the means
+        contributions = []
         for p, h in hooked.items():
             out = h.wait()
+            if track:
+                contributions.append(h.sumsq if h.sumsq is not None else self._torch_sumsq(out))
             if not fused:
                 out.div_(comm.size)
         pin = self._pinning()
@@ -149,9 +215,13 @@ class DataParallelismDistributedOptimizer:
         # one keyed request per gradient (the reference builds one Allreduce op per grad,
         # distributed_optimizer.py:50-63), registered as one batch, reduced in place
         handles = zip(params, allreduce_async_batch(grads, keys, comm, outputs=grads, op=self._op(),
-                                                          compression=self.compression))
+                                                          compression=self.compression,
+                                                          sumsq=[track and g is p.grad and self._engine_sumsq(g)
+                                                                 for p, g in zip(params, grads)]))
         for p, h in handles:
             out = h.wait()
+            if track:
+                contributions.append(h.sumsq if h.sumsq is not None else self._torch_sumsq(out))
             if not fused:
                 out.div_(comm.size)
             if out.data_ptr() != p.grad.data_ptr():
@@ -159,6 +229,10 @@ class DataParallelismDistributedOptimizer:
         # sparse gradients: every rank's rows gathered, values averaged (same order on all ranks)
         for p in sparse:
             p.grad = allreduce_gradient(p.grad, comm)  # (sparse: the allgather branch, fused_mean or not)
+            if track:  # averaged already: in the sums' units where the others are
+                contributions.append(self._torch_sumsq(p.grad) * (1.0 if fused else float(comm.size) ** 2))
+        if track:
+            self._finish_norm(contributions, not fused)
 
     def zero_grad(self, set_to_none: bool = True) -> None:
         # pinned host gradients survive zero_grad (zeroed in place), so the next backward
@@ -179,6 +253,8 @@ class DataParallelismDistributedOptimizer:
     @torch.no_grad()
     def step(self, closure=None):
         self.allreduce_gradients()
+        if self.skip_nonfinite and self.found_nonfinite:
+            return None  # an inf or NaN gradient: the step is skipped (the loss scaler's overflow case)
         return super().step(closure)
 
     @property
@@ -193,7 +269,10 @@ def data_parallelism_distributed_optimizer_wrapper(
         overlap_backward: bool = False,
         bucket_bytes: int = 32 << 20,
         fused_mean: bool = False,
-        compression=Compression.none) -> torch.optim.Optimizer:
+        compression=Compression.none,
+        track_grad_norm: bool = False,
+        max_grad_norm: float = None,
+        skip_nonfinite: bool = False) -> torch.optim.Optimizer:
     """Return an optimizer of a subclass of `type(optimizer)` whose step() first averages the
     gradients across `communicator` (default: the world). Parameter groups and state are
     shared with `optimizer`. `pin_host_gradients`: keep CPU gradients in pinned memory;
@@ -212,7 +291,11 @@ def data_parallelism_distributed_optimizer_wrapper(
     feedback (module docstring): it costs one fp32 copy of every compressed gradient in device
     memory and a pack of 14 instead of 6 bytes per element; reset it with
     ddl.torch.compression.reset_error_feedback() after loading a checkpoint or a change of the loss
-    scale by a large factor."""
+    scale by a large factor. `track_grad_norm`: `optimizer.grad_norm` / `optimizer.found_nonfinite`
+    after every allreduce_gradients(), from the engine's sums of squares (module docstring);
+    `max_grad_norm`: clip the averaged gradients to that global L2 norm before the step;
+    `skip_nonfinite`: skip the wrapped step() when a gradient holds an inf or NaN. The last two imply
+    the first."""
     opt_cls = optimizer.__class__
     assert issubclass(opt_cls, torch.optim.Optimizer)
     cls = type(opt_cls.__name__, (DataParallelismDistributedOptimizer, opt_cls), {})
@@ -223,6 +306,9 @@ def data_parallelism_distributed_optimizer_wrapper(
     res.fused_mean = bool(fused_mean)
     wire_flag(compression)  # a TypeError here, not at the first step
     res.compression = Compression.none if compression is None else compression
+    res.track_grad_norm = bool(track_grad_norm)
+    res.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+    res.skip_nonfinite = bool(skip_nonfinite)
     if overlap_backward:
         if bucket_bytes:
             from ddl.torch import config

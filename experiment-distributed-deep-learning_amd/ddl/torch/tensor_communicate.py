@@ -319,6 +319,8 @@ def _native_done():
 class _NativeHandle(Handle):
     """Handle of a request completed through a completion group (no Python done callback)."""
     __slots__ = ('_group', '_index')
+    sumsq = None       # after wait(): the engine's sum of squares of the output (requests with sumsq=True)
+    _sumsq_ref = None  # (the ctypes doubles the engine writes, this request's index in them)
 
     def __init__(self, key: str, output: torch.Tensor, keep_alive, group: _Completion, index: int):
         # (no threading.Event: the slot is the completion)
@@ -340,6 +342,8 @@ class _NativeHandle(Handle):
         self._keep = None
         if self.status != cb.STATUS_OK:
             raise cb.DDLError(self.status, f'request {self.key!r}', '')
+        if self._sumsq_ref is not None:  # written by the engine before the slot completed
+            self.sumsq = float(self._sumsq_ref[0][self._sumsq_ref[1]])
         return self.output
 
 
@@ -444,6 +448,19 @@ def _compressible(tensor: torch.Tensor, communicator: Communicator, flag: int, m
     return communicator.size > 1 or CPPBackend.c_api().ddl_get_config(b'one_rank_shortcut') == 0
 
 
+def _check_sumsq(tensors, op: int, what: str) -> None:
+    """`sumsq=True` is the engine's DDL_ALLREDUCE_SUMSQ: dense fp32 device tensors, SUM or AVG.
+    Raised before any library call."""
+    if int(op) in (cb.OP_MIN, cb.OP_MAX):
+        raise ValueError(f'{what}: sumsq is defined for OP_SUM and OP_AVG, not OP_MIN / OP_MAX')
+    for t in tensors:
+        if t.is_sparse or not t.is_cuda:
+            raise ValueError(f'{what}: sumsq needs a dense device tensor, not a {t.device.type} '
+                             f'{"sparse " if t.is_sparse else ""}one')
+        if t.dtype != torch.float32:
+            raise ValueError(f'{what}: sumsq is defined for float32 tensors, not {t.dtype}')
+
+
 def _same_memory(a: torch.Tensor, b: torch.Tensor, what: str) -> int:
     ma, mb = memory_kind(a, f'{what} input'), memory_kind(b, f'{what} output')
     if ma != mb:
@@ -452,7 +469,8 @@ def _same_memory(a: torch.Tensor, b: torch.Tensor, what: str) -> int:
 
 
 def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator = None,
-                    output: torch.Tensor = None, op: int = cb.OP_SUM, compression=Compression.none) -> Handle:
+                    output: torch.Tensor = None, op: int = cb.OP_SUM, compression=Compression.none,
+                    sumsq: bool = False) -> Handle:
     """Register a keyed allreduce (`op`: cb.OP_SUM, cb.OP_AVG for the mean, cb.OP_MIN / cb.OP_MAX for
     the element-wise minimum / maximum — like a compression, the same on every rank for a name, and
     never together with one: ValueError); returns a Handle.
@@ -464,6 +482,10 @@ def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator 
     of the tensor in device memory per distinct name until the communicator goes, so keep the names
     stable from step to step; ddl.torch.compression.reset_error_feedback after loading a checkpoint
     or a large change of the loss scale).
+    `sumsq=True` (a dense fp32 device tensor, OP_SUM or OP_AVG; anything else: ValueError): after
+    wait(), `handle.sumsq` is a Python float, the fp64 sum of the squares of the output's elements,
+    taken by the engine where it writes them (include/ddl_amd.h "Sum of squares": no extra pass in a
+    fused plan, the same bits on every rank, finite if and only if every element is finite).
 
     `name` plays the role of the TF op name: the same name on every rank identifies the same
     gradient, and only one request per name may be pending (TensorCommunicateRequest.h:21).
@@ -471,6 +493,8 @@ def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator 
     DEVICE_CPU (AllreduceOp.cc:68) — are fused through pinned staging to the GPU and back.
     """
     _check_op_compression(op, compression)
+    if sumsq:
+        _check_sumsq((tensor,) if output is None else (tensor, output), op, 'allreduce_async')
     communicator = _comm(communicator)
     out = torch.empty_like(tensor) if output is None else output
     mem = _same_memory(tensor, out, 'allreduce_async')
@@ -480,11 +504,22 @@ def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator 
     key, dt, stream = name.encode(), ddl_dtype(tensor), stream_handle_for(tensor)
     if _compressible(tensor, communicator, wire_flag(compression), mem):
         op = int(op) | wire_flag(compression)
-    group = _Completion(1, (tensor, out))
-    h = _NativeHandle(name, out, None, group, 0)  # the group holds the tensors
+    if sumsq:
+        import ctypes
+        value = (ctypes.c_double * 1)()  # lives in the group's keep until the request has completed
+        group = _Completion(1, (tensor, out, value))
+        h = _NativeHandle(name, out, None, group, 0)
+        h._sumsq_ref = (value, 0)
+        # DDL_ALLREDUCE_SUMSQ: the user pointer is a ddl_sumsq_arg (read during the call) naming the slot and the double
+        arg = cb.SumsqArg(group.slots()[0], ctypes.addressof(value))
+        op, user = int(op) | cb.SUMSQ, ctypes.addressof(arg)
+    else:
+        group = _Completion(1, (tensor, out))
+        h = _NativeHandle(name, out, None, group, 0)  # the group holds the tensors
+        user = group.slots()[0]
     st = CPPBackend.c_api().ddl_allreduce_submit_mem(
         communicator.id, key, tensor.data_ptr(), out.data_ptr(), tensor.numel(), dt, int(op), mem, stream,
-        _native_done(), group.slots()[0])
+        _native_done(), user)
     if st != cb.STATUS_OK:
         group.fail([0], st)
         check(st, 'ddl_allreduce_submit_mem')
@@ -492,21 +527,29 @@ def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator 
 
 
 def allreduce_async_batch(tensors, names, communicator: Communicator = None, outputs=None, op: int = cb.OP_SUM,
-                          compression=Compression.none):
+                          compression=Compression.none, sumsq=False):
     """Register several keyed allreduces at once (one engine wake-up, one input-ready event), all
     with `op` (cb.OP_SUM, cb.OP_AVG for the mean, cb.OP_MIN / cb.OP_MAX); returns one Handle per tensor. Same key rules as `allreduce_async`; device and host tensors
     may be mixed (one submission per memory kind). `compression` (Compression.fp16 / .bf16) applies
     to the dense fp32 device tensors at size > 1 (ddl.torch.compression); the others are submitted
     uncompressed, so a mixed batch goes as one compressed and one plain submission. The handles
     come back in the caller's order either way. The error-feedback kinds as in `allreduce_async`:
-    one residual per name, so stable names."""
+    one residual per name, so stable names. `sumsq` as in `allreduce_async`: True for every tensor, or
+    one bool per tensor (a batch may mix requests with and without it); the flagged tensors must be
+    dense fp32 device tensors (ValueError otherwise) and their handles carry `sumsq` after wait()."""
     import ctypes
     _check_op_compression(op, compression)
-    communicator = _comm(communicator)
     tensors = list(tensors)
     names = list(names)
     if len(tensors) != len(names):
         raise ValueError('one name per tensor')
+    wanted = [bool(sumsq)] * len(tensors) if isinstance(sumsq, (bool, int)) else [bool(w) for w in sumsq]
+    if len(wanted) != len(tensors):
+        raise ValueError('sumsq: one flag per tensor')
+    if any(wanted):
+        outs_ = tensors if outputs is None else list(outputs)
+        _check_sumsq([x for t, o, w in zip(tensors, outs_, wanted) if w for x in (t, o)], op, 'allreduce_async_batch')
+    communicator = _comm(communicator)
     outputs = [torch.empty_like(t) for t in tensors] if outputs is None else list(outputs)
     k = len(tensors)
     if k == 0:
@@ -521,8 +564,13 @@ def allreduce_async_batch(tensors, names, communicator: Communicator = None, out
     # one completion group for the batch: the engine completes every request natively (no
     # Python done() per tensor); the group keeps every tensor until the batch has completed, so
     # the handles hold only their outputs
-    group = _Completion(k, (tensors, outputs))
+    # the engine writes the sums of squares into ctypes doubles that live in the group's keep
+    values = (ctypes.c_double * k)() if any(wanted) else None
+    group = _Completion(k, (tensors, outputs) if values is None else (tensors, outputs, values))
     handles = [_NativeHandle(n, o, None, group, i) for i, (n, o) in enumerate(zip(names, outputs))]
+    for i, w in enumerate(wanted):
+        if w:
+            handles[i]._sumsq_ref = (values, i)
     done, slots = _native_done(), group.slots()
     # one submission per (memory kind, wire flag): the engine takes one op per batch, so the fp32
     # device tensors that travel compressed go apart from the rest
@@ -544,9 +592,17 @@ def allreduce_async_batch(tensors, names, communicator: Communicator = None, out
         try:
             ins = (ctypes.c_void_p * m)(*[t.data_ptr() for t in ts])
             outs = ins if in_place else (ctypes.c_void_p * m)(*[o.data_ptr() for o in os_])
+            stat = 0
+            if any(wanted[i] for i in idx):
+                # DDL_ALLREDUCE_SUMSQ: every user pointer is a ddl_sumsq_arg (read during the call) naming
+                # the request's slot and its double, NULL where not wanted (device tensors: _check_sumsq)
+                base, stat = ctypes.addressof(values), cb.SUMSQ
+                args = (cb.SumsqArg * m)(*[cb.SumsqArg(slots[i], base + 8 * i if wanted[i] else None) for i in idx])
+                step = ctypes.sizeof(cb.SumsqArg)
+                users = (ctypes.c_void_p * m)(*[ctypes.addressof(args) + j * step for j in range(m)])
             st = CPPBackend.c_api().ddl_allreduce_submit_batch_mem(
                 communicator.id, m, (ctypes.c_char_p * m)(*ks), ins, outs,
-                (ctypes.c_size_t * m)(*[t.numel() for t in ts]), (ctypes.c_int * m)(*ds), int(op) | wire, mem,
+                (ctypes.c_size_t * m)(*[t.numel() for t in ts]), (ctypes.c_int * m)(*ds), int(op) | wire | stat, mem,
                 stream_handle_for(tensors[idx[0]]), done, users)
         except BaseException:
             group.fail(rest, _STATUS_ERROR_UNKNOWN)  # not submitted: no slot may stay pending

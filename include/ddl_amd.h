@@ -87,6 +87,17 @@ enum ddl_allreduce_op { DDL_ALLREDUCE_OP_SUM = 0, DDL_ALLREDUCE_OP_AVG = 1, DDL_
 enum ddl_allreduce_wire { DDL_ALLREDUCE_WIRE_FP16 = 0x100, DDL_ALLREDUCE_WIRE_BF16 = 0x200,
                           /* error feedback: only OR-ed with exactly one of the two above */
                           DDL_ALLREDUCE_WIRE_FEEDBACK = 0x1000 };
+/* Sum of squares of a keyed device allreduce of DDL_FLOAT tensors (MI355X extension; the data-plane
+ * section): OR-ed into the `op` of ddl_allreduce_submit / _submit_batch (and _submit_mem /
+ * _submit_batch_mem with DDL_MEMORY_DEVICE), SUM or AVG, with or without a wire flag. With the bit
+ * `user` (every users[i] of a batch) points to a ddl_sumsq_arg, read during the call only: `done`
+ * receives arg->user, and *arg->sumsq (host memory, valid until `done`; NULL = this request does not
+ * want it) holds the value when `done` fires with DDL_STATUS_OK. */
+enum ddl_allreduce_stat { DDL_ALLREDUCE_SUMSQ = 0x2000 };
+struct ddl_sumsq_arg {
+    void *user;    /* what `done` receives */
+    double *sumsq; /* where the sum of squares goes, or NULL */
+};
 
 typedef long long ddl_communicator_id;
 
@@ -314,7 +325,58 @@ void py_error(const char *log_str);
  * the SUM / AVG group of the same dtype and memory, MIN before MAX). Ranks that disagree about a
  * key's kind post different collectives.
  * Refusals, before anything is registered: MIN / MAX with a wire flag or DDL_ALLREDUCE_WIRE_FEEDBACK
- * returns DDL_STATUS_INVALID_ARGUMENT; op values 2 and above 4 stay DDL_STATUS_INVALID_ARGUMENT. */
+ * returns DDL_STATUS_INVALID_ARGUMENT; op values 2 and above 4 stay DDL_STATUS_INVALID_ARGUMENT.
+ *
+ * Sum of squares (DDL_ALLREDUCE_SUMSQ in `op`, `user` a ddl_sumsq_arg): an optional per-request output of a
+ * keyed DDL_FLOAT device request with op SUM or AVG (a wire flag and the feedback bit allowed):
+ * *sumsq = the fp64 sum of the squares of the fp32 elements written to `out` — the final values,
+ * after AVG's quotient and after the wire's widening — stored before `done` fires. It is the
+ * squared L2 norm a gradient clip needs, and the finite check of a loss scaler: the square of a
+ * finite fp32 value is exact in fp64 and no sum of fewer than 2^64 of them overflows, so *sumsq is
+ * FINITE IF AND ONLY IF EVERY ELEMENT IS FINITE (an inf gives +inf, a NaN or inf and NaN give NaN).
+ * `out` is bit-identical on every rank and the order of the additions below is fixed, so *sumsq is
+ * the same double on every rank: a clip factor derived from it keeps the replicas in step.
+ * Order. A request is cut into PIECES at the element offsets where a fusion plan
+ * ("fusion_threshold_bytes") or a pipeline sub-plan ("fusion_pipeline_bytes", cuts at 256-byte
+ * multiples of the communicated stream) ends inside it — shared tunables and the negotiated round,
+ * so every rank cuts alike. For a piece of n elements x[0..n): T = 256 and E = 4 for an
+ * uncompressed request, T = 512 and E = 8 for one with a wire flag. The piece has ceil(n / T) tiles;
+ * lane l (0..63) of tile t owns elements t*T + l*E .. t*T + l*E + E-1 and computes
+ *     s[l] = (((+0.0 + x0*x0) + x1*x1) + ...)       left to right in fp64, x widened to fp64 first,
+ * an element at or past n counting as +0.0 (every product is exact, so whether the compiler
+ * contracts acc + x*x into a fused multiply-add changes no bit); the lanes combine by the butterfly
+ *     for d = 32, 16, 8, 4, 2, 1:  s[l] = s[l] + s[l ^ d]     (all lanes at once)
+ * and s[0] is the tile's partial p[t]. The partials are combined in GROUPS of up to 4096 consecutive
+ * values: for a group v[0..m), lane l computes q[l] = ((+0.0 + v[l]) + v[l + 64]) + v[l + 128] + ...
+ * (missing values +0.0), the same butterfly follows, and q[0] is the group's value. A piece of at
+ * most 4096 tiles (1 Mi elements uncompressed) is one group and its value is that group's; a longer
+ * piece's group values, in order, form one more group whose value is the piece's (pieces of up to
+ * 4096^2 tiles, 16 GiB; longer ones fail with DDL_STATUS_INVALID_ARGUMENT). The request's *sumsq is its
+ * pieces' values added in increasing element offset, starting from the first piece's value. n == 0
+ * gives +0.0.
+ * tests/_sumsq_helpers.py restates this in NumPy, bit for bit.
+ * Invariances. The order depends only on an element's index inside its piece, the piece's length
+ * and whether the request is compressed — not on the tensor pointer's alignment, not on whether the
+ * piece went through the fusion buffer or was read in place, not on which other requests share its
+ * plan or unpack launch. No floating-point atomic is used anywhere.
+ * Cost. A fused plan takes it inside the unpack launch that writes the elements (csrc/pack.hip
+ * k_seg_sumsq: 8 bytes written per 1 KiB tile, plus one small finishing kernel and one async copy
+ * per launch): no extra pass over the tensors. A plan of one uncompressed request (reduced in place,
+ * no fusion buffer) and the one-rank shortcut pay ONE READ-ONLY PASS over the result with the same
+ * kernel. No host synchronisation is added: the values reach pinned host memory by an async copy
+ * ahead of the event the completion already waits for.
+ * Like SUM against AVG it is rank-local: it is in no fusion group key, plan cut or negotiation, one
+ * plan or launch may mix requests with and without it, requests without it run exactly the launches,
+ * kernels and tables they ran before, and ranks that disagree about it never hang.
+ * P = 1: with "one_rank_shortcut" 1 the value is that of the input moved to `out`, in the
+ * uncompressed order also with a wire flag (nothing is compressed); with 0 the data plane runs and
+ * the value is its result's. On a failed request the value is unspecified.
+ * Refusals, before anything is registered (the communicator works afterwards): a non-NULL sumsq with
+ * a dtype other than DDL_FLOAT returns DDL_STATUS_UNSUPPORTED_DTYPE, with MIN / MAX or with
+ * DDL_MEMORY_HOST DDL_STATUS_INVALID_ARGUMENT; the bit with a NULL `user` (`users`, users[i]), and the
+ * bit on ddl_allreduce, ddl_allreduce_batch or ddl_allreduce_host, DDL_STATUS_INVALID_ARGUMENT; the
+ * op's own refusals apply as without the bit. With every arg->sumsq NULL the request is the one
+ * without the bit. No new entry point: the deployment surface is unchanged. */
 /* recv = SUM over ranks of send (elementwise), bit for bit the reference's MPI_Allreduce (MPICH
  * 3.3.2's order) with reference_order 1. The schedule is the tuned one for the bucket's size
  * class: by default at P > 2 the direct reduce-scatter (slices of every chunk to every peer over

@@ -142,6 +142,27 @@ int ddl_pack_cvt(void *dst, const void *const *srcs, const size_t *elements, int
                  void *hip_stream);
 int ddl_unpack_cvt(void *const *dsts, const void *src, const size_t *elements, const int *ops, int count,
                    int wire_dtype, int divisor, void *hip_stream);
+/* DDL_ALLREDUCE_SUMSQ (ddl_amd.h "Sum of squares") with the value's address as an argument instead of a
+ * ddl_sumsq_arg: ddl_allreduce_submit / _submit_batch with the bit and one ddl_sumsq_arg {user, sumsq}
+ * per request, built here. Device memory, dtype DDL_FLOAT, op SUM or AVG (optionally a wire flag and the
+ * feedback bit); `sumsq` (sumsqs[i]; entries may be NULL = not wanted) is host memory valid until `done`.
+ * With every sumsq NULL the calls are ddl_allreduce_submit / _submit_batch. */
+int ddl_allreduce_submit_sumsq(ddl_communicator_id id, const char *key, const void *in, void *out, size_t elements,
+                               int dtype, int op, void *hip_stream, ddl_done_fn done, void *user, double *sumsq);
+int ddl_allreduce_submit_batch_sumsq(ddl_communicator_id id, int count, const char *const *keys,
+                                     const void *const *ins, void *const *outs, const size_t *elements,
+                                     const int *dtypes, int op, void *hip_stream, ddl_done_fn done,
+                                     void *const *users, double *const *sumsqs /* entries may be NULL */);
+/* ddl_unpack_ops / ddl_unpack_cvt with the sums of squares (ddl_amd.h "Sum of squares"; csrc/pack.hip
+ * k_seg_sumsq and its finishing kernel): fp32 tensors; want[i] != 0 asks for segment i's value, every
+ * segment taken as one piece; sumsq_out[i] (count entries; +0.0 where not wanted) holds it when the
+ * call returns (it waits for hip_stream). With no wanted non-empty segment the launch is
+ * ddl_unpack_ops' / ddl_unpack_cvt's. src == NULL: the in-place, read-only form — the wanted segments
+ * are read where they are, nothing is divided or written. */
+int ddl_unpack_ops_sumsq(void *const *dsts, const void *src, const size_t *bytes, const int *ops, int count, int dtype,
+                         int divisor, void *hip_stream, const unsigned char *want, double *sumsq_out);
+int ddl_unpack_cvt_sumsq(void *const *dsts, const void *src, const size_t *elements, const int *ops, int count,
+                         int wire_dtype, int divisor, void *hip_stream, const unsigned char *want, double *sumsq_out);
 /* ddl_pack_cvt with error feedback (DDL_ALLREDUCE_WIRE_FEEDBACK; k_seg<CvtPackOp<WIRE, true>>) on caller-owned
  * residuals: residuals[i] = elements[i] fp32 values (4-byte aligned), added to segment i before the
  * rounding and overwritten with what the rounding removed; NULL = segment i is converted as
@@ -217,6 +238,17 @@ int ddl_testing_thread_fused_allreduce_wire(int nranks, int count, const void *c
 int ddl_testing_thread_fused_allreduce_wire_fb(int nranks, int count, const void *const *srcs, void *const *dsts,
                                                void *const *residuals, const size_t *elements, const int *ops,
                                                int wire_dtype, void *hip_stream, size_t *subplans);
+/* The _ops and _wire entries in one, with the sums of squares: fp32 tensors of elements[i] values,
+ * wire_dtype 0 = uncompressed, else DDL_HALF / DDL_BFLOAT16. want[i] != 0 asks for segment i's value;
+ * sumsq_out[r * count + i] = rank r's value of segment i, its sub-plan pieces added in increasing
+ * offset as the keyed handler adds them (+0.0 where not wanted). The pieces' cuts, for a restatement:
+ * *ncuts = the wanted pieces that start inside a segment, (cut_segs[k], cut_elems[k]) = the segment
+ * and first element of the first max_cuts of them (rank 0's; every rank cuts alike). Waits for
+ * hip_stream before it returns. */
+int ddl_testing_thread_fused_allreduce_sumsq(int nranks, int count, const void *const *srcs, void *const *dsts,
+                                             const size_t *elements, const int *ops, int wire_dtype, void *hip_stream,
+                                             size_t *subplans, const unsigned char *want, double *sumsq_out,
+                                             size_t *cut_segs, size_t *cut_elems, int max_cuts, int *ncuts);
 /* Data movement of the thread worlds made from now on: rccl = 0 device copies (default); 1 every
  * matched send / receive pair goes through RcclTransport::group as a self send + self receive on
  * the RCCL loopback communicator (ddl_rccl_loopback_init first), posted on the receiver's stream
