@@ -39,6 +39,10 @@ def parse():
     p.add_argument('--compression', default='none', choices=['none', 'fp16', 'bf16'],
                    help='send the fp32 device gradients as 16-bit values (Compression.fp16 / .bf16; bf16 for unscaled '
                         'gradients)')
+    p.add_argument('--loss-scale', default=0.0, type=float,
+                   help='dynamic loss scaling from this initial scale (DynamicLossScaler: the engine unscales the '
+                        'gradients in its unpack kernel and finds overflows from its sum of squares); with '
+                        '--compression fp16 the gradients are also pre-divided by the size. 0: off')
     return p.parse_args()
 
 
@@ -82,7 +86,13 @@ def main():
     scaled_lr = world.size * args.lr
     optimizer = data_parallelism_distributed_optimizer_wrapper(torch.optim.Adam(model.parameters(), lr=scaled_lr),
                                                                world, fused_mean=args.fused_mean,
-                                                               compression=getattr(Compression, args.compression))
+                                                               compression=getattr(Compression, args.compression),
+                                                               gradient_predivide_factor=world.size
+                                                               if args.loss_scale and args.compression == 'fp16' else 1.0)
+    scaler = None
+    if args.loss_scale:
+        from ddl.torch.parallelism.data import DynamicLossScaler
+        scaler = DynamicLossScaler(optimizer, init_scale=args.loss_scale)
     if world.size > 1:
         InitialParametersBroadcast(model, 0, optimizer, communicator=world).broadcast()
     steps = max(1, len(x_train) // args.batch_size)
@@ -104,8 +114,12 @@ def main():
             optimizer.zero_grad()
             out = model(xb)
             loss = loss_fn(out, yb)
-            loss.backward()
-            optimizer.step()
+            if scaler is None:
+                loss.backward()
+                optimizer.step()
+            else:
+                scaler.scale(loss).backward()
+                scaler.step()
             warmup.on_batch_end(b)
             total += loss.item() * len(idx)
             correct += int((out.argmax(1) == yb).sum())

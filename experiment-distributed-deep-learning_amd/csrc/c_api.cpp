@@ -3,6 +3,7 @@
 // C++ exception crosses the ABI. The test / measurement entry points (include/ddl_amd_testing.h)
 // are in c_api_testing.cpp, linked into libddl_amd_testing.so only.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -324,8 +325,21 @@ namespace {
 // DDL_ALLREDUCE_SUMSQ (ddl_amd.h): with the bit `user` is a ddl_sumsq_arg, read here and now. Takes the
 // bit out of `op`, leaves what done() receives in *user and where the value goes in *sumsq (null: not
 // wanted, also without the bit).
-static void take_sumsq(int *op, void **user, double **sumsq) {
+// DDL_ALLREDUCE_SCALE: `user` is a ddl_scale_arg, whose first two members are ddl_sumsq_arg's (its sumsq is
+// read only with the SUMSQ bit too); the factors go to *pre / *post (1 without the bit).
+static void take_sumsq(int *op, void **user, double **sumsq, float *pre, float *post) {
     *sumsq = nullptr;
+    *pre = *post = 1.0f;
+    if (*op & DDL_ALLREDUCE_SCALE) {
+        DDL_REQUIRE(*user, DDL_STATUS_INVALID_ARGUMENT, "DDL_ALLREDUCE_SCALE needs a ddl_scale_arg as the user pointer");
+        const ddl_scale_arg arg = *static_cast<const ddl_scale_arg *>(*user);
+        if (*op & DDL_ALLREDUCE_SUMSQ) *sumsq = arg.sumsq;
+        *op &= ~(DDL_ALLREDUCE_SCALE | DDL_ALLREDUCE_SUMSQ);
+        *user = arg.user;
+        *pre = arg.prescale;
+        *post = arg.postscale;
+        return;
+    }
     if (!(*op & DDL_ALLREDUCE_SUMSQ)) return;
     DDL_REQUIRE(*user, DDL_STATUS_INVALID_ARGUMENT, "DDL_ALLREDUCE_SUMSQ needs a ddl_sumsq_arg as the user pointer");
     const ddl_sumsq_arg arg = *static_cast<const ddl_sumsq_arg *>(*user);
@@ -340,6 +354,16 @@ static void check_sumsq(const double *sumsq, int dtype, int op, bool host) {
                 "the sum of squares is defined for float32 requests, not " << dtype_name(dtype));
     DDL_REQUIRE(!op_is_minmax(op), DDL_STATUS_INVALID_ARGUMENT, "the sum of squares takes SUM or AVG, not MIN / MAX");
     DDL_REQUIRE(!host, DDL_STATUS_INVALID_ARGUMENT, "the sum of squares takes device memory");
+}
+// the refusals of the scale factors, before anything is registered or recorded; both 1: the plain request
+static void check_scale(float pre, float post, int dtype, int op, bool host) {
+    DDL_REQUIRE(std::isfinite(pre) && pre > 0.0f && std::isfinite(post) && post > 0.0f, DDL_STATUS_INVALID_ARGUMENT,
+                "scale factors must be finite and positive, not " << pre << " / " << post);
+    if (pre == 1.0f && post == 1.0f) return;
+    DDL_REQUIRE(dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
+                "scale factors are defined for float32 requests, not " << dtype_name(dtype));
+    DDL_REQUIRE(!op_is_minmax(op), DDL_STATUS_INVALID_ARGUMENT, "scale factors take SUM or AVG, not MIN / MAX");
+    DDL_REQUIRE(!host, DDL_STATUS_INVALID_ARGUMENT, "scale factors take device memory");
 }
 }  // namespace
 
@@ -356,9 +380,10 @@ int ddl_allreduce_submit_mem(ddl_communicator_id id, const char *key, const void
         r.n = elements;
         r.dtype = dtype;
         r.host = memory == DDL_MEMORY_HOST;
-        take_sumsq(&op, &user, &r.sumsq);
+        take_sumsq(&op, &user, &r.sumsq, &r.prescale, &r.postscale);
         r.wire = decode_keyed_op(op, dtype, r.host, &r.op, &r.feedback);  // refusals before anything is posted
         check_sumsq(r.sumsq, dtype, r.op, r.host);
+        check_scale(r.prescale, r.postscale, dtype, r.op, r.host);
         r.done = done;
         r.user = user;
         r.ready = ready_event(memory, hip_stream);
@@ -438,8 +463,8 @@ int ddl_allreduce_submit_batch_mem(ddl_communicator_id id, int count, const char
         if (count == 0) return;
         auto c = Registry::get().find(id);
         DeviceGuard g(c->device());
-        DDL_REQUIRE(!(op & DDL_ALLREDUCE_SUMSQ) || users, DDL_STATUS_INVALID_ARGUMENT,
-                    "DDL_ALLREDUCE_SUMSQ needs one ddl_sumsq_arg per request in users");
+        DDL_REQUIRE(!(op & (DDL_ALLREDUCE_SUMSQ | DDL_ALLREDUCE_SCALE)) || users, DDL_STATUS_INVALID_ARGUMENT,
+                    "DDL_ALLREDUCE_SUMSQ / DDL_ALLREDUCE_SCALE need one argument struct per request in users");
         // one op for the batch: with a wire flag every entry must be fp32 (all-or-nothing, decided
         // before the ready event is recorded)
         std::vector<Request> rs(count);
@@ -453,9 +478,10 @@ int ddl_allreduce_submit_batch_mem(ddl_communicator_id id, int count, const char
             rs[i].host = memory == DDL_MEMORY_HOST;
             int opi = op;
             rs[i].user = users ? users[i] : nullptr;
-            take_sumsq(&opi, &rs[i].user, &rs[i].sumsq);  // (the args' sumsq entries may be NULL)
+            take_sumsq(&opi, &rs[i].user, &rs[i].sumsq, &rs[i].prescale, &rs[i].postscale);  // (sumsq entries may be NULL)
             rs[i].wire = decode_keyed_op(opi, dtypes[i], rs[i].host, &rs[i].op, &rs[i].feedback);
             check_sumsq(rs[i].sumsq, dtypes[i], rs[i].op, rs[i].host);
+            check_scale(rs[i].prescale, rs[i].postscale, dtypes[i], rs[i].op, rs[i].host);
             rs[i].done = done;
         }
         auto ready = ready_event(memory, hip_stream);

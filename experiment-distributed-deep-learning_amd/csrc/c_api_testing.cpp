@@ -5,6 +5,7 @@
 // happens-before recorder and schedule introspection.
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -509,6 +510,56 @@ int ddl_unpack_cvt_sumsq(void *const *dsts, const void *src, const size_t *eleme
     });
 }
 
+// The scaled copies (ddl_amd_testing.h): the copier's calls with a factor per segment.
+int ddl_pack_scale(void *dst, const void *const *srcs, void *const *residuals, const size_t *elements, int count,
+                   int wire_dtype, const float *scale, void *hip_stream) {
+    return guarded([&] {
+        DDL_REQUIRE(count >= 0 && (count == 0 || (dst && srcs && elements && scale)) && (!residuals || wire_dtype),
+                    DDL_STATUS_INVALID_ARGUMENT, "bad pack_scale args");
+        std::lock_guard<std::mutex> g(abi_copier_mu());
+        if (wire_dtype) {
+            const std::vector<size_t> b = wire_bytes(elements, count, wire_dtype);
+            abi_copier().run_cvt(0, dst, const_cast<void *const *>(srcs), b.data(), count, as_stream(hip_stream), DDL_FLOAT,
+                                 wire_dtype, 1, nullptr, residuals, nullptr, nullptr, scale);
+        } else {
+            std::vector<size_t> b((size_t)count);
+            for (int i = 0; i < count; ++i) b[(size_t)i] = elements[i] * sizeof(float);
+            abi_copier().run(0, dst, const_cast<void *const *>(srcs), b.data(), count, as_stream(hip_stream), DDL_FLOAT, 1,
+                             nullptr, nullptr, nullptr, scale);
+        }
+    });
+}
+
+int ddl_unpack_scale(void *const *dsts, const void *src, const size_t *elements, const int *ops, int count,
+                     int wire_dtype, int divisor, const float *scale, void *hip_stream, const unsigned char *want,
+                     double *sumsq_out) {
+    return guarded([&] {
+        DDL_REQUIRE(count >= 0 && (count == 0 || (dsts && elements && ops && scale)) && divisor >= 1 &&
+                        (!want || sumsq_out) && (src || (!wire_dtype && !want)),
+                    DDL_STATUS_INVALID_ARGUMENT, "bad unpack_scale args");
+        if (count == 0) return;
+        for (int i = 0; i < count; ++i) {
+            check_allreduce_op(ops[i], DDL_FLOAT);
+            DDL_REQUIRE(!op_is_minmax(ops[i]), DDL_STATUS_INVALID_ARGUMENT, "scale factors take SUM or AVG");
+        }
+        std::vector<size_t> b((size_t)count);
+        if (wire_dtype) b = wire_bytes(elements, count, wire_dtype);
+        else
+            for (int i = 0; i < count; ++i) b[(size_t)i] = elements[i] * sizeof(float);
+        std::lock_guard<std::mutex> g(abi_copier_mu());
+        auto run = [&](double *sq) {
+            if (wire_dtype)
+                abi_copier().run_cvt(1, const_cast<void *>(src), dsts, b.data(), count, as_stream(hip_stream), DDL_FLOAT,
+                                     wire_dtype, divisor, ops, nullptr, want, sq, scale);
+            else
+                abi_copier().run(src ? 1 : SegmentCopier::kDivInPlace, const_cast<void *>(src), dsts, b.data(), count,
+                                 as_stream(hip_stream), DDL_FLOAT, divisor, ops, want, sq, scale);
+        };
+        if (want) unpack_sumsq(count, hip_stream, sumsq_out, run);
+        else run(nullptr);
+    });
+}
+
 int ddl_pack_cvt(void *dst, const void *const *srcs, const size_t *elements, int count, int wire_dtype,
                  void *hip_stream) {
     return guarded([&] {
@@ -728,6 +779,42 @@ int ddl_testing_thread_fused_allreduce_sumsq(int nranks, int count, const void *
         const size_t j = thread_world(nranks).fused_allreduce(
             srcs, dsts, b.data(), count, wire_dtype ? wire_dtype : DDL_FLOAT, as_stream(hip_stream), config().ring(),
             (size_t)config().fusion_pipeline_bytes.load(), ops, wire_dtype ? DDL_FLOAT : 0, nullptr, want, sumsq_out, &cuts);
+        if (subplans) *subplans = j;
+        if (ncuts) *ncuts = (int)cuts.size();
+        for (int k = 0; k < max_cuts && k < (int)cuts.size() && cut_segs && cut_elems; ++k) {
+            cut_segs[k] = cuts[k].first;
+            cut_elems[k] = cuts[k].second;
+        }
+    });
+}
+
+int ddl_testing_thread_fused_allreduce_scale(int nranks, int count, const void *const *srcs, void *const *dsts,
+                                             void *const *residuals, const size_t *elements, const int *ops,
+                                             int wire_dtype, const float *prescale, const float *postscale,
+                                             void *hip_stream, size_t *subplans, const unsigned char *want,
+                                             double *sumsq_out, size_t *cut_segs, size_t *cut_elems, int max_cuts,
+                                             int *ncuts) {
+    return guarded([&] {
+        DDL_REQUIRE(nranks >= 1 && nranks <= 64 && count >= 1 && srcs && dsts && elements && (!want || sumsq_out) &&
+                        (!residuals || wire_dtype),
+                    DDL_STATUS_INVALID_ARGUMENT, "bad thread fused allreduce");
+        for (int i = 0; ops && i < count; ++i) {
+            check_allreduce_op(ops[i], DDL_FLOAT);
+            DDL_REQUIRE(!op_is_minmax(ops[i]), DDL_STATUS_INVALID_ARGUMENT, "scale factors take SUM or AVG");
+        }
+        for (int i = 0; i < count; ++i)
+            for (const float *f : {prescale, postscale})
+                DDL_REQUIRE(!f || (std::isfinite(f[i]) && f[i] > 0.0f), DDL_STATUS_INVALID_ARGUMENT,
+                            "scale factors must be finite and positive");
+        std::vector<size_t> b(count);
+        if (wire_dtype) b = wire_bytes(elements, count, wire_dtype);
+        else
+            for (int i = 0; i < count; ++i) b[i] = elements[i] * sizeof(float);
+        std::vector<std::pair<size_t, size_t>> cuts;
+        const size_t j = thread_world(nranks).fused_allreduce(
+            srcs, dsts, b.data(), count, wire_dtype ? wire_dtype : DDL_FLOAT, as_stream(hip_stream), config().ring(),
+            (size_t)config().fusion_pipeline_bytes.load(), ops, wire_dtype ? DDL_FLOAT : 0, residuals, want, sumsq_out, &cuts,
+            prescale, postscale);
         if (subplans) *subplans = j;
         if (ncuts) *ncuts = (int)cuts.size();
         for (int k = 0; k < max_cuts && k < (int)cuts.size() && cut_segs && cut_elems; ++k) {

@@ -269,9 +269,16 @@ public:
     // segments that already hold their results (`flat` and `ops` unused; nothing posted if nothing
     // is wanted).
     static constexpr int kSumsqInPlace = 3;
+    // The scale factors (DDL_ALLREDUCE_SCALE; `scale` one fp32 factor per segment, finite and > 0,
+    // null = none; DDL_FLOAT segments): a launch in which some non-empty segment has a factor other
+    // than 1 is the scaled kernel of its kind — dir 0 multiplies the elements on their way into the flat
+    // buffer (the prescale), dir 1 and kDivInPlace on their way into the tensors, behind AVG's quotient
+    // (the postscale; kDivInPlace then covers the AVG and the scaled segments), and the sum of squares is
+    // of the scaled values. A segment with factor 1 inside such a launch is moved as the unscaled kernel
+    // moves it; every other launch is the kernel it was. kSumsqInPlace ignores `scale`.
     void run(int dir, void *flat, void *const *segs, const size_t *bytes, int count, hipStream_t stream,
              int dtype = 0, int divisor = 1, const int *ops = nullptr, const unsigned char *want = nullptr,
-             double *sumsq = nullptr);
+             double *sumsq = nullptr, const float *scale = nullptr);
     // The converting copies of the wire compression (ddl_allreduce_wire): the tensors hold `src_dtype`
     // (DDL_FLOAT) elements, the flat buffer `wire_dtype` (DDL_HALF / DDL_BFLOAT16) ones. `wire_bytes[i]`
     // = segment i's bytes on the FLAT side (elements x 2), so offsets, tiles and flat_bytes are those
@@ -287,12 +294,16 @@ public:
                  void *const *residuals = nullptr,
                  // dir 1 / kSumsqInPlace: the sums of squares as in run(), in the compressed order
                  // (512 elements per tile, 8 per lane)
-                 const unsigned char *want = nullptr, double *sumsq = nullptr);
+                 const unsigned char *want = nullptr, double *sumsq = nullptr,
+                 // dir 0: the prescale ahead of the narrowing (and of the residual's addition); dir 1: the
+                 // postscale behind the widening and the quotient — as in run()
+                 const float *scale = nullptr);
     static size_t flat_bytes(const size_t *bytes, int count);
 
 private:
     void run_(int dir, void *flat, void *const *segs, const size_t *bytes, int count, hipStream_t stream, int dtype,
-              int divisor, const int *ops, int wire, void *const *residuals, const unsigned char *want, double *sumsq);
+              int divisor, const int *ops, int wire, void *const *residuals, const unsigned char *want, double *sumsq,
+              const float *scale);
     struct Slot {
         void *host = nullptr, *dev = nullptr;
         size_t cap = 0;

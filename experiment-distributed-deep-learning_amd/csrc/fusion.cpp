@@ -42,7 +42,7 @@ hipEvent_t FusionPipe::event_(size_t i) {
 void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<void *> &dsts,
                      const std::vector<size_t> &bytes, int dt, size_t cap, hipStream_t stream, const Allreduce &ar,
                      const std::vector<int> *ops, int divisor, int src_dt, const std::vector<void *> *residuals,
-                     PlanSumsq *sumsq) {
+                     PlanSumsq *sumsq, const std::vector<float> *prescale, const std::vector<float> *postscale) {
     const size_t es = dtype_size(dt);
     DDL_REQUIRE(es != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported dtype " << dt);
     const bool cvt = src_dt != 0 && src_dt != dt;
@@ -50,13 +50,17 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
     DDL_REQUIRE(ses != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported source dtype " << src_dt);
     // gather (dir 0) / scatter (dir 1) of one (sub-)plan: the converting kernels with a wire dtype
     // (`res`: the pack's residuals of a plan with error feedback)
-    // (`want`, `sq`: the unpack's sums of squares, SegmentCopier::run)
+    // (`want`, `sq`: the unpack's sums of squares, SegmentCopier::run; `scl`: the pack's prescale
+    // factors, the unpack's postscale factors)
     auto copy = [&](int dir, void *fb, void *const *segs, const size_t *b, int n, hipStream_t s, const int *o,
-                    void *const *res = nullptr, const unsigned char *want = nullptr, double *sq = nullptr) {
-        if (cvt) copier.run_cvt(dir, fb, segs, b, n, s, src_dt, dt, divisor, o, dir == 0 ? res : nullptr, want, sq);
-        else if (dir == 0) copier.run(0, fb, segs, b, n, s);
-        else copier.run(1, fb, segs, b, n, s, dt, divisor, o, want, sq);
+                    void *const *res = nullptr, const unsigned char *want = nullptr, double *sq = nullptr,
+                    const float *scl = nullptr) {
+        if (cvt) copier.run_cvt(dir, fb, segs, b, n, s, src_dt, dt, divisor, o, dir == 0 ? res : nullptr, want, sq, scl);
+        else if (dir == 0) copier.run(0, fb, segs, b, n, s, dt, 1, nullptr, nullptr, nullptr, scl);
+        else copier.run(1, fb, segs, b, n, s, dt, divisor, o, want, sq, scl);
     };
+    DDL_REQUIRE((!prescale || prescale->size() == bytes.size()) && (!postscale || postscale->size() == bytes.size()),
+                DDL_STATUS_INVALID_ARGUMENT, "fusion plan: one scale factor per segment");
     // the statistic only where some segment asks for it: otherwise every launch below is as without it
     bool stat = false;
     for (size_t i = 0; sumsq && sumsq->want && i < bytes.size(); ++i) stat = stat || sumsq->want[i];
@@ -77,11 +81,12 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
         last_subplans_ = 1;
         void *fb = ensure(0, total, stream);
         copy(0, fb, const_cast<void *const *>(reinterpret_cast<const void *const *>(srcs.data())), bytes.data(),
-             (int)srcs.size(), stream, nullptr, residuals ? residuals->data() : nullptr);
+             (int)srcs.size(), stream, nullptr, residuals ? residuals->data() : nullptr, nullptr, nullptr,
+             prescale ? prescale->data() : nullptr);
         ar(fb, total / es, message);
         double *sq = stat ? sumsq->pinned(bytes.size()) : nullptr;
         copy(1, fb, dsts.data(), bytes.data(), (int)dsts.size(), stream, ops ? ops->data() : nullptr, nullptr,
-             stat ? sumsq->want : nullptr, sq);
+             stat ? sumsq->want : nullptr, sq, postscale ? postscale->data() : nullptr);
         for (size_t i = 0; stat && i < bytes.size(); ++i)
             if (sumsq->want[i]) sumsq->pieces.push_back(PlanSumsq::Piece{i, 0, sq + i});
         return;
@@ -95,6 +100,7 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
         std::vector<unsigned char> want;  // of each piece: its segment's (only with a wanted statistic)
         std::vector<size_t> seg, elem;    //   and the piece's segment and first element in it
         bool stat = false;
+        std::vector<float> pre, post;  // of each piece: its segment's factors (only with `prescale` / `postscale`)
         size_t flat = 0;
     };
     std::vector<Sub> subs(1);
@@ -117,6 +123,8 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
             // the residual is indexed like the tensor: the same fp32 element offset at a cut
             if (residuals)
                 cur->res.push_back((*residuals)[i] ? static_cast<char *>((*residuals)[i]) + off / es * ses : nullptr);
+            if (prescale) cur->pre.push_back((*prescale)[i]);
+            if (postscale) cur->post.push_back((*postscale)[i]);
             if (stat) {
                 cur->want.push_back(sumsq->want[i]);
                 cur->seg.push_back(i);
@@ -145,7 +153,7 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
         const Sub &sb = subs[j];
         double *sq = sb.stat ? sumsq->pinned(sb.bytes.size()) : nullptr;
         copy(1, buf[j % 2], sb.dst.data(), sb.bytes.data(), (int)sb.dst.size(), side_, ops ? sb.ops.data() : nullptr,
-             nullptr, sb.stat ? sb.want.data() : nullptr, sq);
+             nullptr, sb.stat ? sb.want.data() : nullptr, sq, postscale ? sb.post.data() : nullptr);
         // the pieces of a segment in increasing offset: the sub-plans are unpacked in order
         for (size_t k = 0; sb.stat && k < sb.bytes.size(); ++k)
             if (sb.want[k] && sb.bytes[k]) sumsq->pieces.push_back(PlanSumsq::Piece{sb.seg[k], sb.elem[k], sq + k});
@@ -153,7 +161,8 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
     for (size_t j = 0; j < J; ++j) {
         Sub &sb = subs[j];
         copy(0, buf[j % 2], const_cast<void *const *>(reinterpret_cast<const void *const *>(sb.src.data())),
-             sb.bytes.data(), (int)sb.src.size(), side_, nullptr, residuals ? sb.res.data() : nullptr);
+             sb.bytes.data(), (int)sb.src.size(), side_, nullptr, residuals ? sb.res.data() : nullptr, nullptr, nullptr,
+             prescale ? sb.pre.data() : nullptr);
         DDL_HIP(hipEventRecord(events_[1 + 2 * j], side_));
         dep::record(events_[1 + 2 * j], side_);
         DDL_HIP(hipStreamWaitEvent(stream, events_[1 + 2 * j], 0));

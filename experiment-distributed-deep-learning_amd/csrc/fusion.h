@@ -76,7 +76,12 @@ public:
     void run(const std::vector<const void *> &srcs, const std::vector<void *> &dsts,
              const std::vector<size_t> &bytes, int dtype, size_t cap, hipStream_t stream, const Allreduce &ar,
              const std::vector<int> *ops = nullptr, int divisor = 1, int src_dtype = 0,
-             const std::vector<void *> *residuals = nullptr, PlanSumsq *sumsq = nullptr);
+             const std::vector<void *> *residuals = nullptr, PlanSumsq *sumsq = nullptr,
+             // the scale factors (DDL_ALLREDUCE_SCALE; fp32 tensors only), one per segment, null = none: every
+             // piece of a segment is packed with the segment's prescale and unpacked with its postscale
+             // (SegmentCopier::run: a launch without a factor other than 1 is the kernel it was); cuts and
+             // allreduces do not depend on them
+             const std::vector<float> *prescale = nullptr, const std::vector<float> *postscale = nullptr);
     size_t subplans() const { return last_subplans_; }  // of the last run
 
     SegmentCopier copier;

@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <thread>
 #include <tuple>
@@ -131,6 +132,14 @@ void validate(const Request &r, int size) {
                         "the sum of squares is defined for float32 requests, not " << dtype_name(r.dtype));
             DDL_REQUIRE(!r.sumsq || (!r.host && !op_is_minmax(r.op)), DDL_STATUS_INVALID_ARGUMENT,
                         "the sum of squares takes a SUM or AVG request in device memory");
+            DDL_REQUIRE(std::isfinite(r.prescale) && r.prescale > 0.0f && std::isfinite(r.postscale) && r.postscale > 0.0f,
+                        DDL_STATUS_INVALID_ARGUMENT, "scale factors must be finite and positive");
+            if (r.prescale != 1.0f || r.postscale != 1.0f) {
+                DDL_REQUIRE(r.dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
+                            "scale factors are defined for float32 requests, not " << dtype_name(r.dtype));
+                DDL_REQUIRE(!r.host && !op_is_minmax(r.op), DDL_STATUS_INVALID_ARGUMENT,
+                            "scale factors take a SUM or AVG request in device memory");
+            }
             break;
         case kReqBroadcast:
             DDL_REQUIRE(r.root >= 0 && r.root < size, DDL_STATUS_INVALID_ARGUMENT,
@@ -536,6 +545,11 @@ void RequestHandler::stat_in_place_(size_t req, void *out, size_t bytes) {
     round_stat_.emplace_back(req, sq);
 }
 
+void RequestHandler::scale_in_place_(void *out, size_t bytes, int op, int divisor, float factor) {
+    fp_.copier.run(SegmentCopier::kDivInPlace, nullptr, &out, &bytes, 1, stream_, DDL_FLOAT, divisor, &op, nullptr, nullptr,
+                   &factor);
+}
+
 std::unique_lock<std::mutex> RequestHandler::lock_host_group_(const std::vector<Request> &reqs,
                                                               const std::vector<size_t> &group, size_t es, bool host) {
     if (!host) return {};
@@ -646,17 +660,38 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
                 // a one-rank world: the sum is the input; move bytes only where out != in (nothing
                 // is communicated, so nothing is compressed either — and a sum of squares is taken in
                 // the uncompressed order, in place)
+                // the scale factors: (g (x) a) (x) b in one in-place launch behind the copy, each factor
+                // skipped when it is 1 (two launches when both are present: two separately rounded products)
                 size_t q = p.req_begin;
                 plan_slices(p, reqs, g.second, ses, [&](const char *s, char *d, size_t n) {
+                    const Request &r = reqs[g.second[q]];
                     if (s != d && n) DDL_HIP(hipMemcpyAsync(d, s, n, hipMemcpyDeviceToDevice, stream_));
+                    if (n && r.prescale != 1.0f) scale_in_place_(d, n, DDL_ALLREDUCE_OP_SUM, 1, r.prescale);
+                    if (n && r.postscale != 1.0f) scale_in_place_(d, n, DDL_ALLREDUCE_OP_SUM, 1, r.postscale);
                     if (reqs[g.second[q]].sumsq && n) stat_in_place_(g.second[q], d, n);
                     ++q;
                 });
             } else if (p.req_begin == p.req_end && !comp) {
                 const Request &r = reqs[g.second[p.req_begin]];
                 const size_t cnt = p.elem_end - p.elem_begin;
-                data_->allreduce(static_cast<const char *>(r.in) + p.elem_begin * es,
-                                 static_cast<char *>(r.out) + p.elem_begin * es, cnt, dt, r.op, stream_);
+                const char *src = static_cast<const char *>(r.in) + p.elem_begin * es;
+                char *dst = static_cast<char *>(r.out) + p.elem_begin * es;
+                // a prescale: the slice is moved to `out` (where out != in) and multiplied there by one
+                // in-place launch; the allreduce then runs in place over exactly the elements it would
+                // have reduced without the factor. NOT the fusion-buffer branch: its allreduce covers the
+                // padded buffer, another element count, and the factors are rank-local — ranks that
+                // disagree about a prescale must still post the same collective.
+                if (r.prescale != 1.0f && cnt) {
+                    if (src != dst) DDL_HIP(hipMemcpyAsync(dst, src, cnt * es, hipMemcpyDeviceToDevice, stream_));
+                    scale_in_place_(dst, cnt * es, DDL_ALLREDUCE_OP_SUM, 1, r.prescale);
+                    src = dst;
+                }
+                // a postscale: the allreduce of the reduction kind alone, then ONE in-place launch that
+                // takes AVG's quotient and the factor together
+                const bool post = r.postscale != 1.0f;
+                data_->allreduce(src, dst, cnt, dt, post ? kind : r.op, stream_);
+                if (post && cnt)
+                    scale_in_place_(static_cast<char *>(r.out) + p.elem_begin * es, cnt * es, r.op, data_->size(), r.postscale);
                 // no unpack to take it from: one read-only pass over the finished slice
                 if (r.sumsq && cnt) stat_in_place_(g.second[p.req_begin], static_cast<char *>(r.out) + p.elem_begin * es, cnt * es);
             } else {
@@ -686,11 +721,21 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
                     ps.want = want.data();
                     ps.pinned = [this](size_t n) { return stat_take_(n); };
                 }
+                // the scale factors (Request::prescale / postscale, rank-local too): the pack's and the unpack's
+                std::vector<float> pre, post;
+                bool any_pre = false, any_post = false;
+                for (size_t q = p.req_begin; q <= p.req_end; ++q) {
+                    pre.push_back(reqs[g.second[q]].prescale);
+                    post.push_back(reqs[g.second[q]].postscale);
+                    any_pre = any_pre || pre.back() != 1.0f;
+                    any_post = any_post || post.back() != 1.0f;
+                }
                 fp_.run(srcs, dsts, bytes, dt, (size_t)config().fusion_pipeline_bytes.load(), stream_,
                         [&](void *buf, size_t elems, size_t message) {
                             data_->allreduce(buf, buf, elems, dt, kind, stream_, message);
                         },
-                        &ops, data_->size(), sdt, resid.empty() ? nullptr : &res, stat ? &ps : nullptr);
+                        &ops, data_->size(), sdt, resid.empty() ? nullptr : &res, stat ? &ps : nullptr,
+                        any_pre ? &pre : nullptr, any_post ? &post : nullptr);
                 for (const PlanSumsq::Piece &pc : ps.pieces) round_stat_.emplace_back(g.second[p.req_begin + pc.seg], pc.value);
             }
             finish_plan_(p, reqs, g.second, dones, nplans);

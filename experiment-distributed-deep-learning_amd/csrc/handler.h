@@ -58,6 +58,10 @@ struct Request {
     int wire = 0;                     // allreduce: wire dtype of a compressed fp32 request (0: its own dtype)
     bool feedback = false;            // allreduce: DDL_ALLREDUCE_WIRE_FEEDBACK (only with `wire`; rank-local)
     double *sumsq = nullptr;          // allreduce: where the sum of squares of `out` goes before done() (host; rank-local)
+    // allreduce: DDL_ALLREDUCE_SCALE's factors (1 = absent; fp32 device SUM / AVG requests). Rank-local like
+    // the op and `sumsq`: in no group key, plan cut, pipeline cut or negotiation.
+    float prescale = 1.0f;            //   every element times this on its way into the reduction
+    float postscale = 1.0f;           //   every result (behind AVG's quotient) times this on its way into `out`
     int root = 0;                     // broadcast: TensorBroadcastRequest::rootRank()
     size_t first_dim = 0;             // allgather: rows of `in` (n = first_dim * row_elems)
     size_t row_elems = 1;             //   elements per row (the shape without its first dim)
@@ -121,6 +125,9 @@ private:
     double *stat_take_(size_t n);
     // the in-place, read-only sum of squares (SegmentCopier::kSumsqInPlace) of reqs[req]'s slice on stream_
     void stat_in_place_(size_t req, void *out, size_t bytes);
+    // one in-place launch of the scaled scatter on stream_ over a finished fp32 slice: AVG's quotient by
+    // `divisor` where `op` is AVG, then `factor` (SegmentCopier::kDivInPlace with a factor)
+    void scale_in_place_(void *out, size_t bytes, int op, int divisor, float factor);
     struct Done {
         size_t plan;  // index into the round's plan events (kNoPlan: nothing to wait for)
         size_t req;

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -33,11 +34,13 @@ struct SegDesc {
     uint64_t ptr;   // segment address (tensor side)
     uint64_t off;   // offset in the flat buffer (256-byte aligned)
     uint64_t len;   // bytes
-    uint32_t vec;   // kSegVec: ptr is 16-byte aligned (16-byte units, else elements); kSegAvg; kSegStat
+    uint32_t vec;   // kSegVec: ptr is 16-byte aligned (16-byte units, else elements); kSegAvg; kSegStat; kSegScale
     uint32_t tile0; // segment-aligned tiling: index of the segment's first tile
 };
 // kSegStat: the segment's sum of squares is wanted (k_seg_sumsq only; the other kernels never see it)
-constexpr uint32_t kSegVec = 1, kSegAvg = 2, kSegStat = 4;
+// kSegScale: the segment's elements are multiplied by its factor of the launch's factor table (the scaled
+// kernels only; the other kernels never see it)
+constexpr uint32_t kSegVec = 1, kSegAvg = 2, kSegStat = 4, kSegScale = 8;
 
 // Segment-aligned tiling: every segment is cut into tiles of kSegTile bytes that restart at the
 // segment start, so a tile never crosses a segment and its workgroup needs no per-chunk search:
@@ -253,8 +256,9 @@ template <class T> union Wire8 {
 //     v = g + r;  w = narrow(v);  r' = isfinite(widen(w)) ? v - widen(w) : 0
 // w goes to the flat buffer, r' replaces r. One fp32 rounding (g + r, nearest even, subnormals kept)
 // beyond the wire's own: v - widen(w) is exact whenever widen(w) is finite. A NaN or inf in v, or
-// an overflow of the narrowing, clears the residual. No multiply, so nothing can contract; no
-// reciprocal. Moves 14 bytes per element against the plain converting pack's 6: the vector path
+// an overflow of the narrowing, clears the residual. The plain feedback pack has no multiply, so nothing
+// can contract; the scaled one (ScaleCvtPackOp below) multiplies first, through mul_rn, whose product is
+// rounded on its own and never fuses with this addition. No reciprocal. Moves 14 bytes per element against the plain converting pack's 6: the vector path
 // (tensor AND residual 16-byte aligned) is two 16-byte loads from each, one 16-byte wire store and
 // two 16-byte residual stores. The tensor loads and all stores are non-temporal (the residual is
 // next read a whole step later); the residual LOADS are plain: with non-temporal loads of both read
@@ -363,6 +367,180 @@ template <int WIRE> struct CvtUnpackOp {
     }
 };
 
+// ---- the scaled copies (DDL_ALLREDUCE_SCALE: prescale in the packs, postscale in the unpacks) -------
+// The launch carries one fp32 factor per segment (scl[seg], uploaded behind the block bases and the
+// residual addresses); a segment flagged kSegScale has every element multiplied by it, a segment
+// without the flag is moved exactly as the unscaled Op moves it (no multiply is issued: the bits are
+// untouched). fp32 tensors only. Every product is one fp32 operation rounded to nearest even with
+// subnormals kept, and never part of an fma: hipcc contracts a * b + c by default, so the multiply
+// is mul_rn, compiled with contraction off.
+//   pack:    c = g (x) a, then what the unscaled pack does with c (store / narrow / feedback's c (+) r)
+//   unpack:  y = s (widened), y = y (/) (float)P for kSegAvg, y = y (x) b for kSegScale, store y
+__device__ inline float mul_rn(float x, float a) {
+#pragma clang fp contract(off)
+    return x * a;
+}
+
+// ScaleGatherOp: the uncompressed prescale, tensor -> flat. Whole fp32 elements (kUnit 4).
+struct ScaleGatherOp {
+    static constexpr uint32_t kUnit = 4;
+    float *fl;
+    const float *tp;
+    float a;
+    bool sc, v;
+    __device__ ScaleGatherOp(char *flat, const SegDesc &sd, int seg, const float *__restrict__ scl)
+        : fl(reinterpret_cast<float *>(flat + sd.off)), tp(reinterpret_cast<const float *>(sd.ptr)),
+          sc((sd.vec & kSegScale) != 0), v((sd.vec & kSegVec) != 0) {
+        a = sc ? scl[seg] : 1.0f;
+    }
+    __device__ bool vector() const { return v; }
+    __device__ void vec(uint64_t b) const {
+        F32x4 x;
+        x.v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(tp) + b));
+        if (sc) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) x.e[k] = mul_rn(x.e[k], a);
+        }
+        __builtin_nontemporal_store(x.v, reinterpret_cast<u32x4 *>(reinterpret_cast<char *>(fl) + b));
+    }
+    __device__ void elem(uint64_t e) const { fl[e] = sc ? mul_rn(tp[e], a) : tp[e]; }
+};
+
+// ScaleCvtPackOp<WIRE, FB>: CvtPackOp<WIRE, FB> with the product ahead of the narrowing (FB: ahead of
+// the residual's addition, so the residual is in prescaled units). FB carries both tables.
+template <int WIRE, bool FB> struct ScaleCvtPackOp {
+    using Tr = WireTraits<WIRE>;
+    using T = typename Tr::T;
+    static constexpr uint32_t kUnit = sizeof(T);
+    T *fl;
+    const float *tp;
+    float *rs;
+    float a;
+    bool sc, v;
+    __device__ ScaleCvtPackOp(char *flat, const SegDesc &sd, int seg, const float *__restrict__ scl)
+        : fl(reinterpret_cast<T *>(flat + sd.off)), tp(reinterpret_cast<const float *>(sd.ptr)), rs(nullptr),
+          sc((sd.vec & kSegScale) != 0), v((sd.vec & kSegVec) != 0) {
+        a = sc ? scl[seg] : 1.0f;
+    }
+    __device__ ScaleCvtPackOp(char *flat, const SegDesc &sd, int seg, const uint64_t *__restrict__ res,
+                              const float *__restrict__ scl)
+        : fl(reinterpret_cast<T *>(flat + sd.off)), tp(reinterpret_cast<const float *>(sd.ptr)),
+          rs(reinterpret_cast<float *>(res[seg])), sc((sd.vec & kSegScale) != 0),
+          v((sd.vec & kSegVec) != 0 && (res[seg] & 15u) == 0) {
+        a = sc ? scl[seg] : 1.0f;
+    }
+    __device__ bool vector() const { return v; }
+    __device__ void vec(uint64_t b) const {
+        const u32x4 *src = reinterpret_cast<const u32x4 *>(tp + b / sizeof(T));
+        F32x4 lo, hi;
+        lo.v = __builtin_nontemporal_load(src);
+        hi.v = __builtin_nontemporal_load(src + 1);
+        if (sc) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                lo.e[k] = mul_rn(lo.e[k], a);
+                hi.e[k] = mul_rn(hi.e[k], a);
+            }
+        }
+        Wire8<T> o;
+        if (FB && rs) {
+            u32x4 *rv = reinterpret_cast<u32x4 *>(rs + b / sizeof(T));
+            F32x4 rlo, rhi;
+            rlo.v = rv[0];  // plain loads, as CvtPackOp
+            rhi.v = rv[1];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                o.e[k] = feedback<WIRE>(lo.e[k], rlo.e[k]);
+                o.e[4 + k] = feedback<WIRE>(hi.e[k], rhi.e[k]);
+            }
+            __builtin_nontemporal_store(rlo.v, rv);
+            __builtin_nontemporal_store(rhi.v, rv + 1);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                o.e[k] = Tr::narrow(lo.e[k]);
+                o.e[4 + k] = Tr::narrow(hi.e[k]);
+            }
+        }
+        __builtin_nontemporal_store(o.v, reinterpret_cast<u32x4 *>(reinterpret_cast<char *>(fl) + b));
+    }
+    __device__ void elem(uint64_t e) const {
+        const float c = sc ? mul_rn(tp[e], a) : tp[e];
+        if (FB && rs) {
+            float r = rs[e];
+            fl[e] = feedback<WIRE>(c, r);
+            rs[e] = r;
+        } else {
+            fl[e] = Tr::narrow(c);
+        }
+    }
+};
+
+// ScaleScatterOp: fp32 flat -> tensor, or with flat == nullptr the segment itself (in place, as DivOp):
+// DivOp<kDivF32>'s quotient for kSegAvg, then the factor for kSegScale.
+struct ScaleScatterOp {
+    static constexpr uint32_t kUnit = 4;
+    float *tp;
+    const float *sp;
+    float dv, b_;
+    bool avg, sc, v;
+    __device__ ScaleScatterOp(const char *flat, const SegDesc &sd, int seg, float divisor, const float *__restrict__ scl)
+        : tp(reinterpret_cast<float *>(sd.ptr)), sp(flat ? reinterpret_cast<const float *>(flat + sd.off) : tp),
+          dv(divisor), avg((sd.vec & kSegAvg) != 0), sc((sd.vec & kSegScale) != 0), v((sd.vec & kSegVec) != 0) {
+        b_ = sc ? scl[seg] : 1.0f;
+    }
+    __device__ float y(float x) const {
+        if (avg) x = x / dv;
+        if (sc) x = mul_rn(x, b_);
+        return x;
+    }
+    __device__ bool vector() const { return v; }
+    __device__ void vec(uint64_t b) const {
+        F32x4 x;
+        x.v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(sp) + b));
+#pragma unroll
+        for (int k = 0; k < 4; ++k) x.e[k] = y(x.e[k]);
+        __builtin_nontemporal_store(x.v, reinterpret_cast<u32x4 *>(reinterpret_cast<char *>(tp) + b));
+    }
+    __device__ void elem(uint64_t e) const { tp[e] = y(sp[e]); }
+};
+
+// ScaleCvtUnpackOp<WIRE>: CvtUnpackOp<WIRE> with the factor behind the quotient.
+template <int WIRE> struct ScaleCvtUnpackOp {
+    using Tr = WireTraits<WIRE>;
+    using T = typename Tr::T;
+    static constexpr uint32_t kUnit = sizeof(T);
+    const T *fl;
+    float *tp;
+    float divisor, b_;
+    bool avg, sc, v;
+    __device__ ScaleCvtUnpackOp(const char *flat, const SegDesc &sd, int seg, float dv, const float *__restrict__ scl)
+        : fl(reinterpret_cast<const T *>(flat + sd.off)), tp(reinterpret_cast<float *>(sd.ptr)), divisor(dv),
+          avg((sd.vec & kSegAvg) != 0), sc((sd.vec & kSegScale) != 0), v((sd.vec & kSegVec) != 0) {
+        b_ = sc ? scl[seg] : 1.0f;
+    }
+    __device__ float y(float x) const {
+        if (avg) x = x / divisor;
+        if (sc) x = mul_rn(x, b_);
+        return x;
+    }
+    __device__ bool vector() const { return v; }
+    __device__ void vec(uint64_t b) const {
+        Wire8<T> x;
+        x.v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(fl) + b));
+        F32x4 lo, hi;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            lo.e[k] = y(Tr::widen(x.e[k]));
+            hi.e[k] = y(Tr::widen(x.e[4 + k]));
+        }
+        u32x4 *dst = reinterpret_cast<u32x4 *>(tp + b / sizeof(T));
+        __builtin_nontemporal_store(lo.v, dst);
+        __builtin_nontemporal_store(hi.v, dst + 1);
+    }
+    __device__ void elem(uint64_t e) const { tp[e] = y(Tr::widen(fl[e])); }
+};
+
 // ---- the unpacks with the sum of squares (DDL_ALLREDUCE_SUMSQ) -----------------------------
 // k_seg_sumsq: the plain, the dividing (WIRE < 0: fp32 flat buffer, DivOp<kDivF32>'s quotient) and the
 // converting scatter (WIRE = kWireF16 / kWireBF16: CvtUnpackOp's widening and quotient) of fp32
@@ -388,10 +566,10 @@ __device__ inline double wave_sum(double s) {
     return s;
 }
 
-template <int WIRE, bool NARROW>
-__global__ void __launch_bounds__(64) k_seg_sumsq(const char *flat, const SegDesc *__restrict__ d,
-                                                  const uint32_t *__restrict__ blk_base, const void *__restrict__ map,
-                                                  float divisor, double *__restrict__ partials) {
+template <int WIRE, bool NARROW, bool SCALE>
+__device__ __forceinline__ void seg_sumsq(const char *flat, const SegDesc *__restrict__ d,
+                                          const uint32_t *__restrict__ blk_base, const void *__restrict__ map,
+                                          float divisor, double *__restrict__ partials, const float *__restrict__ scl) {
     constexpr int E = WIRE < 0 ? 4 : 8;
     constexpr uint64_t kUnit = WIRE < 0 ? 4 : 2;  // bytes of SegDesc::len per element
     const unsigned tile = blockIdx.x;
@@ -422,6 +600,13 @@ __global__ void __launch_bounds__(64) k_seg_sumsq(const char *flat, const SegDes
             if (sd.vec & kSegAvg) {
 #pragma unroll
                 for (int k = 0; k < E; ++k) x[k] = x[k] / divisor;
+            }
+            if constexpr (SCALE) {
+                if (sd.vec & kSegScale) {
+                    const float b = scl[seg];
+#pragma unroll
+                    for (int k = 0; k < E; ++k) x[k] = mul_rn(x[k], b);
+                }
             }
             if (whole) {
 #pragma unroll
@@ -459,6 +644,23 @@ __global__ void __launch_bounds__(64) k_seg_sumsq(const char *flat, const SegDes
     }
     acc = wave_sum(acc);
     if (threadIdx.x == 0) partials[tile] = acc;
+}
+
+template <int WIRE, bool NARROW>
+__global__ void __launch_bounds__(64) k_seg_sumsq(const char *flat, const SegDesc *__restrict__ d,
+                                                  const uint32_t *__restrict__ blk_base, const void *__restrict__ map,
+                                                  float divisor, double *__restrict__ partials) {
+    seg_sumsq<WIRE, NARROW, false>(flat, d, blk_base, map, divisor, partials, nullptr);
+}
+
+// k_seg_sumsq with the postscale: the factor of a kSegScale segment behind the quotient, ahead of the
+// store and the squares (the statistic is of what is stored). Scatters only (flat != nullptr).
+template <int WIRE, bool NARROW>
+__global__ void __launch_bounds__(64) k_seg_sumsq_scale(const char *flat, const SegDesc *__restrict__ d,
+                                                        const uint32_t *__restrict__ blk_base,
+                                                        const void *__restrict__ map, float divisor,
+                                                        double *__restrict__ partials, const float *__restrict__ scl) {
+    seg_sumsq<WIRE, NARROW, true>(flat, d, blk_base, map, divisor, partials, scl);
 }
 
 // The finishing kernels: a segment's tile partials (nt of them, contiguous from tile0) into out[seg], in a
@@ -512,11 +714,23 @@ void launch_sumsq(bool narrow, dim3 g, hipStream_t stream, const char *fl, const
     else hipLaunchKernelGGL((k_seg_sumsq<WIRE, false>), g, dim3(64), 0, stream, fl, dd, db, map, divisor, partials);
 }
 
+template <int WIRE>
+void launch_sumsq_scale(bool narrow, dim3 g, hipStream_t stream, const char *fl, const SegDesc *dd, const uint32_t *db,
+                        const void *map, float divisor, double *partials, const float *scl) {
+    if (narrow)
+        hipLaunchKernelGGL((k_seg_sumsq_scale<WIRE, true>), g, dim3(64), 0, stream, fl, dd, db, map, divisor, partials, scl);
+    else
+        hipLaunchKernelGGL((k_seg_sumsq_scale<WIRE, false>), g, dim3(64), 0, stream, fl, dd, db, map, divisor, partials, scl);
+}
+
 // What one run_ is, decided once: its kernel, its tables, its happens-before spans and its label.
 // kCvtUnpack and kCvtUnpackAvg share a kernel (the AVG segments carry kSegAvg).
 // kUnpackStat / kCvtUnpackStat / kSumsq: k_seg_sumsq (fp32 flat, wire flat, in place) and its finishing kernel.
+// The k*Scale ops: the scaled kernels (ScaleGatherOp ... k_seg_sumsq_scale), with the factor table.
 enum SegOp : int {
-    kPack, kUnpack, kUnpackAvg, kDivide, kCvtPack, kCvtPackFb, kCvtUnpack, kCvtUnpackAvg, kUnpackStat, kCvtUnpackStat, kSumsq
+    kPack, kUnpack, kUnpackAvg, kDivide, kCvtPack, kCvtPackFb, kCvtUnpack, kCvtUnpackAvg, kUnpackStat, kCvtUnpackStat, kSumsq,
+    kPackScale, kCvtPackScale, kCvtPackFbScale, kUnpackScale, kScaleInPlace, kCvtUnpackScale, kUnpackStatScale,
+    kCvtUnpackStatScale
 };
 struct SegOpInfo {
     const char *label;  // of the happens-before trace
@@ -524,7 +738,10 @@ struct SegOpInfo {
 };
 constexpr SegOpInfo kSegOps[] = {{"pack", true},     {"unpack", false},     {"unpack avg", false}, {"divide", false},
                                  {"pack cvt", true}, {"pack cvt fb", true}, {"unpack cvt", false}, {"unpack cvt avg", false},
-                                 {"unpack sumsq", false}, {"unpack cvt sumsq", false}, {"sumsq", true}};
+                                 {"unpack sumsq", false}, {"unpack cvt sumsq", false}, {"sumsq", true},
+                                 {"pack scale", true}, {"pack cvt scale", true}, {"pack cvt fb scale", true},
+                                 {"unpack scale", false}, {"scale", false}, {"unpack cvt scale", false},
+                                 {"unpack scale sumsq", false}, {"unpack cvt scale sumsq", false}};
 
 }  // namespace
 
@@ -573,13 +790,13 @@ size_t SegmentCopier::flat_bytes(const size_t *bytes, int count) {
 
 void SegmentCopier::run(int dir, void *flat, void *const *segs, const size_t *bytes, int count,
                         hipStream_t stream, int dtype, int divisor, const int *ops, const unsigned char *want,
-                        double *sumsq) {
-    run_(dir, flat, segs, bytes, count, stream, dtype, divisor, ops, 0, nullptr, want, sumsq);
+                        double *sumsq, const float *scale) {
+    run_(dir, flat, segs, bytes, count, stream, dtype, divisor, ops, 0, nullptr, want, sumsq, scale);
 }
 
 void SegmentCopier::run_cvt(int dir, void *flat, void *const *segs, const size_t *wire_bytes, int count,
                             hipStream_t stream, int src_dtype, int wire_dtype, int divisor, const int *ops,
-                            void *const *residuals, const unsigned char *want, double *sumsq) {
+                            void *const *residuals, const unsigned char *want, double *sumsq, const float *scale) {
     DDL_REQUIRE(src_dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
                 "wire compression is defined for float32 sources, not " << dtype_name(src_dtype));
     DDL_REQUIRE(wire_dtype == DDL_HALF || wire_dtype == DDL_BFLOAT16, DDL_STATUS_UNSUPPORTED_DTYPE,
@@ -599,16 +816,36 @@ void SegmentCopier::run_cvt(int dir, void *flat, void *const *segs, const size_t
         fb = true;
     }
     run_(dir, flat, segs, wire_bytes, count, stream, src_dtype, divisor, dir == 1 ? ops : nullptr, wire_dtype,
-         fb ? residuals : nullptr, dir == 0 ? nullptr : want, sumsq);
+         fb ? residuals : nullptr, dir == 0 ? nullptr : want, sumsq, scale);
 }
 
 // wire == 0: the plain copies and the dividing scatter over `bytes` of `dtype`; else the converting
 // copies, `bytes` the wire-side lengths; `residuals` (a converting pack only): the feedback pack;
-// `want` / `sumsq` (a scatter or kSumsqInPlace): the sums of squares (common.h)
+// `want` / `sumsq` (a scatter or kSumsqInPlace): the sums of squares (common.h); `scale`: the factors
+// (a pack's prescale, a scatter's or kDivInPlace's postscale)
 void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *bytes, int count, hipStream_t stream,
                          int dtype, int divisor, const int *ops, int wire, void *const *residuals,
-                         const unsigned char *want, double *sumsq) {
+                         const unsigned char *want, double *sumsq, const float *scale) {
     if (count <= 0) return;
+    // a scaled kernel only where some non-empty segment has a factor other than 1: every other launch
+    // is the kernel it was, its tables exactly as before
+    bool sc = false;
+    if (scale && bytes && (dir == 0 || dir == 1 || dir == kDivInPlace)) {
+        for (int i = 0; i < count; ++i) {
+            if (!bytes[i] || scale[i] == 1.0f) continue;
+            DDL_REQUIRE(std::isfinite(scale[i]) && scale[i] > 0.0f, DDL_STATUS_INVALID_ARGUMENT,
+                        "scale factor " << scale[i] << " of segment " << i << " is not finite and positive");
+            sc = true;
+        }
+    }
+    if (sc) {
+        DDL_REQUIRE(dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
+                    "scale factors are defined for float32 tensors, not " << dtype_name(dtype));
+        const size_t unit = wire ? 2 : 4;
+        for (int i = 0; i < count; ++i)
+            DDL_REQUIRE(bytes[i] % unit == 0 && reinterpret_cast<uintptr_t>(segs[i]) % 4 == 0, DDL_STATUS_INVALID_ARGUMENT,
+                        "segment " << i << " is not whole, aligned float32 elements");
+    }
     // the statistic only where some non-empty segment of a scatter asks for it: every other launch
     // is the kernel it was, its tables exactly as before
     bool stat = false;
@@ -637,7 +874,7 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
     if (ops && divisor > 1)
         for (int i = 0; i < count && !div; ++i) div = ops[i] == DDL_ALLREDUCE_OP_AVG && bytes[i] != 0;
     if (dir == kDivInPlace) {
-        if (!div) return;  // nothing to divide: the segments already hold their results
+        if (!div && !sc) return;  // nothing to divide or scale: the segments already hold their results
         flat = nullptr;
     } else if (dir == kSumsqInPlace) {
         flat = nullptr;
@@ -647,7 +884,11 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
     }
     DDL_REQUIRE((flat || dir == kDivInPlace || dir == kSumsqInPlace) && segs && bytes, DDL_STATUS_INVALID_ARGUMENT,
                 "null pack arguments");
-    const SegOp op = dir == kDivInPlace ? kDivide
+    const SegOp op = sc ? (dir == kDivInPlace ? kScaleInPlace
+                           : stat ? (wire ? kCvtUnpackStatScale : kUnpackStatScale)
+                           : wire ? (dir == 0 ? (residuals ? kCvtPackFbScale : kCvtPackScale) : kCvtUnpackScale)
+                           : dir == 0 ? kPackScale : kUnpackScale)
+                     : dir == kDivInPlace ? kDivide
                      : dir == kSumsqInPlace ? kSumsq
                      : stat ? (wire ? kCvtUnpackStat : kUnpackStat)
                      : wire ? (dir == 0 ? (residuals ? kCvtPackFb : kCvtPack) : div ? kCvtUnpackAvg : kCvtUnpack)
@@ -668,6 +909,12 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
             if (ops[i] != DDL_ALLREDUCE_OP_AVG) own[i] = 0;
         bytes = own.data();
     }
+    if (op == kScaleInPlace) {  // in place only the AVG and the scaled segments have tiles
+        own.assign(bytes, bytes + count);
+        for (int i = 0; i < count; ++i)
+            if (!(div && ops[i] == DDL_ALLREDUCE_OP_AVG) && scale[i] == 1.0f) own[i] = 0;
+        bytes = own.data();
+    }
     if (op == kSumsq) {  // in place only the wanted segments have tiles (nothing else is read)
         own.assign(bytes, bytes + count);
         for (int i = 0; i < count; ++i)
@@ -682,9 +929,12 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
     DDL_REQUIRE(tiles < (1ull << 31), DDL_STATUS_INVALID_ARGUMENT, "fusion buffer too large");
     const uint64_t nblk = (tiles + kIdxBlock - 1) / kIdxBlock;
     const size_t table = (size_t)count * sizeof(SegDesc);
-    // descriptors, then the block bases, then (feedback pack) one residual address per segment
+    // descriptors, then the block bases, then (feedback pack) one residual address per segment, then
+    // (scaled launch) one factor per segment
+    const bool fbk = op == kCvtPackFb || op == kCvtPackFbScale;
     const size_t rtab = (table + nblk * sizeof(uint32_t) + 7) & ~size_t(7);
-    const size_t need = op == kCvtPackFb ? rtab + (size_t)count * sizeof(uint64_t) : table + nblk * sizeof(uint32_t);
+    const size_t stab = fbk ? rtab + (size_t)count * sizeof(uint64_t) : table + nblk * sizeof(uint32_t);
+    const size_t need = sc ? stab + (size_t)count * sizeof(float) : stab;
     if (need > sl.cap) {  // outgrown tables kept until ddl_finalize: no hipFree on a data path (engine.h)
         retire_host(sl.host);
         retire_device(sl.dev);
@@ -704,15 +954,17 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
         t[i].vec = (reinterpret_cast<uintptr_t>(segs[i]) & 15u) == 0 ? kSegVec : 0;
         if (div && ops[i] == DDL_ALLREDUCE_OP_AVG) t[i].vec |= kSegAvg;
         if (stat && want[i] && bytes[i]) t[i].vec |= kSegStat;
+        if (sc && bytes[i] && scale[i] != 1.0f) t[i].vec |= kSegScale;
         t[i].tile0 = (uint32_t)tl;
         off += (bytes[i] + 255) & ~uint64_t(255);
         tl += (bytes[i] + seg_tile - 1) / seg_tile;
     }
     if (off == 0) return;
-    if (op == kCvtPackFb) {
+    if (fbk) {
         uint64_t *rt = reinterpret_cast<uint64_t *>(static_cast<char *>(sl.host) + rtab);
         for (int i = 0; i < count; ++i) rt[i] = bytes[i] ? reinterpret_cast<uint64_t>(residuals[i]) : 0;
     }
+    if (sc) std::memcpy(static_cast<char *>(sl.host) + stab, scale, (size_t)count * sizeof(float));
     // block b's base: the segment of tile b * 128 (the last one with tile0 <= it, as
     // k_tile_index resolves); narrow when no block spans more than 255 segments
     bool narrow = true;
@@ -759,6 +1011,8 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
             }
             partials = static_cast<double *>(sl.stat);
         }
+        const uint64_t *res = reinterpret_cast<const uint64_t *>(static_cast<char *>(sl.dev) + rtab);  // (fbk)
+        const float *scl = reinterpret_cast<const float *>(static_cast<char *>(sl.dev) + stab);        // (sc)
         switch (op) {
             case kPack: launch<CopyOp<0>>(narrow, g, stream, fl, dd, db, sl.idx); break;
             case kUnpack: launch<CopyOp<1>>(narrow, g, stream, fl, dd, db, sl.idx); break;
@@ -779,7 +1033,6 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
                 else launch<CvtPackOp<kWireBF16, false>>(narrow, g, stream, fl, dd, db, sl.idx);
                 break;
             case kCvtPackFb: {
-                const uint64_t *res = reinterpret_cast<const uint64_t *>(static_cast<char *>(sl.dev) + rtab);
                 if (f16) launch<CvtPackOp<kWireF16, true>>(narrow, g, stream, fl, dd, db, sl.idx, res);
                 else launch<CvtPackOp<kWireBF16, true>>(narrow, g, stream, fl, dd, db, sl.idx, res);
                 break;
@@ -796,6 +1049,29 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
                 else if (f16) launch_sumsq<kWireF16>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor, partials);
                 else launch_sumsq<kWireBF16>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor, partials);
                 break;
+            case kPackScale: launch<ScaleGatherOp>(narrow, g, stream, fl, dd, db, sl.idx, scl); break;
+            case kCvtPackScale:
+                if (f16) launch<ScaleCvtPackOp<kWireF16, false>>(narrow, g, stream, fl, dd, db, sl.idx, scl);
+                else launch<ScaleCvtPackOp<kWireBF16, false>>(narrow, g, stream, fl, dd, db, sl.idx, scl);
+                break;
+            case kCvtPackFbScale:
+                if (f16) launch<ScaleCvtPackOp<kWireF16, true>>(narrow, g, stream, fl, dd, db, sl.idx, res, scl);
+                else launch<ScaleCvtPackOp<kWireBF16, true>>(narrow, g, stream, fl, dd, db, sl.idx, res, scl);
+                break;
+            case kUnpackScale:
+            case kScaleInPlace:
+                launch<ScaleScatterOp>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor, scl);
+                break;
+            case kCvtUnpackScale:
+                if (f16) launch<ScaleCvtUnpackOp<kWireF16>>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor, scl);
+                else launch<ScaleCvtUnpackOp<kWireBF16>>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor, scl);
+                break;
+            case kUnpackStatScale:
+            case kCvtUnpackStatScale:
+                if (!wire) launch_sumsq_scale<-1>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor, partials, scl);
+                else if (f16) launch_sumsq_scale<kWireF16>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor, partials, scl);
+                else launch_sumsq_scale<kWireBF16>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor, partials, scl);
+                break;
         }
         if (stat) {  // the segments' values, then to the caller's host memory ahead of whatever it records next
             double *lvl = partials + tiles, *res = lvl + lvl_n;
@@ -810,12 +1086,12 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
     if (dep::on()) {  // happens-before trace (deptrace.h): the segments and the flat buffer
         std::vector<dep::Access> acc;
         const bool gather = kSegOps[op].gather;
-        if (op != kDivide && op != kSumsq) acc.push_back(gather ? dep::wr(flat, off) : dep::rd(flat, off));
+        if (op != kDivide && op != kSumsq && op != kScaleInPlace) acc.push_back(gather ? dep::wr(flat, off) : dep::rd(flat, off));
         const size_t widen = wire ? dtype_size(dtype) / dtype_size(wire) : 1;  // the tensor side in its own bytes
         for (int i = 0; i < count; ++i)
             if (bytes[i])
                 acc.push_back(gather ? dep::rd(segs[i], bytes[i] * widen) : dep::wr(segs[i], bytes[i] * widen));
-        for (int i = 0; i < count && op == kCvtPackFb; ++i)
+        for (int i = 0; i < count && fbk; ++i)
             if (bytes[i] && residuals[i]) {  // read and written: both, so the race check sees either side
                 acc.push_back(dep::rd(residuals[i], bytes[i] * widen));
                 acc.push_back(dep::wr(residuals[i], bytes[i] * widen));

@@ -285,7 +285,8 @@ void ThreadWorld::allreduce_batch(const void *const *in, void *const *out, const
 size_t ThreadWorld::fused_allreduce(const void *const *srcs, void *const *dsts, const size_t *bytes, int count,
                                     int dtype, hipStream_t user, const RingConfig &cfg, size_t cap, const int *ops,
                                     int src_dtype, void *const *residuals, const unsigned char *want,
-                                    double *sumsq_out, std::vector<std::pair<size_t, size_t>> *cuts) {
+                                    double *sumsq_out, std::vector<std::pair<size_t, size_t>> *cuts,
+                                    const float *prescale, const float *postscale) {
     // the plan's kind: MIN / MAX plans hold one kind only (the keyed handler's groups)
     const int kind = ops && count > 0 ? reduce_kind(ops[0]) : DDL_ALLREDUCE_OP_SUM;
     for (int i = 0; ops && i < count; ++i)
@@ -295,6 +296,8 @@ size_t ThreadWorld::fused_allreduce(const void *const *srcs, void *const *dsts, 
     while (pipes_.size() < (size_t)P_) pipes_.emplace_back(new FusionPipe);
     const std::vector<size_t> b(bytes, bytes + count);
     const std::vector<int> o(ops ? ops : nullptr, ops ? ops + count : nullptr);
+    const std::vector<float> pre(prescale ? prescale : nullptr, prescale ? prescale + count : nullptr);
+    const std::vector<float> post(postscale ? postscale : nullptr, postscale ? postscale + count : nullptr);
     // the piece values: pinned blocks made as the pipes ask for them, freed once `user` has been waited for
     std::vector<PlanSumsq> stats(want && sumsq_out ? P_ : 0);
     std::vector<void *> pinned;
@@ -324,7 +327,8 @@ size_t ThreadWorld::fused_allreduce(const void *const *srcs, void *const *dsts, 
             RingConfig c = cfg;
             c.order_bytes = message;
             ex_[r]->allreduce(buf, buf, elems, dtype, s, c, kind);
-        }, ops ? &o : nullptr, P_, src_dtype, residuals ? &res : nullptr, stats.empty() ? nullptr : &stats[r]);
+        }, ops ? &o : nullptr, P_, src_dtype, residuals ? &res : nullptr, stats.empty() ? nullptr : &stats[r],
+           prescale ? &pre : nullptr, postscale ? &post : nullptr);
     });
     if (!stats.empty()) {
         DDL_HIP(hipStreamSynchronize(user));

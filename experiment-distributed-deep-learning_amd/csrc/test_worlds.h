@@ -184,7 +184,9 @@ public:
                            // wanted); *cuts = rank 0's (segment, first element) of every wanted piece that
                            // starts inside a segment. Waits for `user` before it returns.
                            const unsigned char *want = nullptr, double *sumsq_out = nullptr,
-                           std::vector<std::pair<size_t, size_t>> *cuts = nullptr);
+                           std::vector<std::pair<size_t, size_t>> *cuts = nullptr,
+                           // the scale factors (FusionPipe::run), one per segment, the same on every rank
+                           const float *prescale = nullptr, const float *postscale = nullptr);
 
 private:
     void run_(hipStream_t user, const std::function<void(int, hipStream_t)> &body);

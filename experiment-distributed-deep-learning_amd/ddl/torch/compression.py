@@ -7,8 +7,11 @@ with `op=OP_AVG`) — no `.half()` / `.float()` pass over the tensors (include/d
 ddl_allreduce_wire). `Compression.none` (the default everywhere) changes nothing.
 
 fp16 overflows: a gradient or a partial sum beyond 65504 in magnitude becomes inf, and values
-below 6e-8 become zero — use it with a loss scale that keeps the gradients in range. bf16 keeps
-fp32's range with 8 bits of precision and is the choice for unscaled gradients.
+below 6e-8 become zero. The cure for the partial sums is to divide before the narrowing, which the
+engine does inside the pack: `allreduce_async(..., prescale=1 / size)`, or the data-parallel wrapper's
+`gradient_predivide_factor=size`, makes what is summed in fp16 the mean; a loss scale
+(`optimizer.loss_scale`, undone by the engine's postscale) keeps the gradients themselves in range.
+bf16 keeps fp32's range with 8 bits of precision and is the choice for unscaled gradients.
 
 Error feedback: `Compression.fp16_feedback` / `Compression.bf16_feedback` (EF-SGD, 1-bit SGD). What
 the rounding removes is otherwise lost at every step, in the same direction for a gradient that
@@ -23,7 +26,8 @@ step, as the data-parallel wrapper's are; never with names made fresh per call),
 moves 14 bytes per element instead of 6. What travels between the ranks is unchanged.
 When to reset: the residuals belong to the gradients' recent past. Call `reset_error_feedback()`
 after loading a checkpoint, and after a change of the loss scale by a large factor (the residuals
-were scaled by the old one).
+were scaled by the old one) — unless the requests carry prescale = 1 / loss scale: the residual is
+kept in prescaled units, which are then the true gradient's and survive a change of the scale.
 """
 from ddl.torch import cpp_backend as cb
 

@@ -44,6 +44,7 @@ OP_MIN, OP_MAX = 3, 4  # element-wise IEEE 754-2019 minimum / maximum (integers:
 WIRE_FP16, WIRE_BF16 = 0x100, 0x200  # enum ddl_allreduce_wire: OR-ed into a keyed fp32 device request's op
 WIRE_FEEDBACK = 0x1000  # error feedback: only together with exactly one of the two wire flags
 SUMSQ = 0x2000  # enum ddl_allreduce_stat: `user` points to a SumsqArg (struct ddl_sumsq_arg)
+SCALE = 0x4000  # enum ddl_allreduce_scale: `user` points to a ScaleArg (struct ddl_scale_arg)
 MEMORY_DEVICE, MEMORY_HOST = 0, 1  # enum ddl_memory
 
 DONE_FN = ctypes.CFUNCTYPE(None, ctypes.c_int, ctypes.c_void_p)
@@ -52,6 +53,13 @@ DONE_FN = ctypes.CFUNCTYPE(None, ctypes.c_int, ctypes.c_void_p)
 class SumsqArg(ctypes.Structure):
     """struct ddl_sumsq_arg: the `user` of a keyed allreduce whose op carries SUMSQ."""
     _fields_ = [('user', ctypes.c_void_p), ('sumsq', ctypes.c_void_p)]
+
+
+class ScaleArg(ctypes.Structure):
+    """struct ddl_scale_arg: the `user` of a keyed allreduce whose op carries SCALE (its first two members are
+    SumsqArg's: with SCALE | SUMSQ the engine reads `sumsq` from it too)."""
+    _fields_ = [('user', ctypes.c_void_p), ('sumsq', ctypes.c_void_p), ('prescale', ctypes.c_float),
+                ('postscale', ctypes.c_float)]
 
 
 # ddl_alloc_fn: output allocation of a keyed allgather (first_dim, bytes, user) -> device pointer
@@ -151,6 +159,14 @@ class CPPBackend:
         sig('ddl_testing_thread_fused_allreduce_sumsq', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp),
             ctypes.POINTER(sz), ctypes.POINTER(ci), ci, vp, ctypes.POINTER(sz), ub, dp, ctypes.POINTER(sz),
             ctypes.POINTER(sz), ci, ctypes.POINTER(ci))
+        # (testing library: the scaled copies and the thread world's fused allreduce with factors)
+        fp = ctypes.POINTER(ctypes.c_float)
+        sig('ddl_pack_scale', ci, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(sz), ci, ci, fp, vp)
+        sig('ddl_unpack_scale', ci, ctypes.POINTER(vp), vp, ctypes.POINTER(sz), ctypes.POINTER(ci), ci, ci, ci, fp, vp,
+            ub, dp)
+        sig('ddl_testing_thread_fused_allreduce_scale', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp),
+            ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(ci), ci, fp, fp, vp, ctypes.POINTER(sz), ub, dp,
+            ctypes.POINTER(sz), ctypes.POINTER(sz), ci, ctypes.POINTER(ci))
         sig('ddl_broadcast_submit_mem', ci, cid, ctypes.c_char_p, vp, vp, sz, ci, ci, ci, vp, DONE_FN, vp)
         sig('ddl_allgather_submit_mem', ci, cid, ctypes.c_char_p, vp, sz, sz, ci, ci, vp, ALLOC_FN, DONE_FN, vp)
         sig('ddl_control_channel_open', ctypes.c_longlong, ctypes.c_char_p, sz)

@@ -62,6 +62,22 @@ multiplied by `max_grad_norm / (norm + 1e-6)` (`torch.nn.utils.clip_grad_norm_`'
 is the same double on every rank) with one `torch._foreach_mul_` per device. `skip_nonfinite`: a
 non-finite norm makes step() return without calling the wrapped step(). At size 1 nothing is
 communicated and the norm is torch's.
+
+`gradient_predivide_factor=f` (Horovod's): every dense fp32 contiguous device gradient is submitted with
+the engine's prescale 1 / f and postscale f (`allreduce_async(..., prescale=, postscale=)`), on both
+paths, so what is summed is g / f — with `compression=Compression.fp16` and f = the size, the mean, which
+cannot overflow where the gradients themselves do not. The two products are taken inside the pack and
+the unpack kernels: no pass over the gradients is added. Other gradients ignore it (the net factor is 1).
+Every rank must pass the same value. Default 1 (off).
+
+`optimizer.loss_scale` (a plain attribute, default 1.0; read when a gradient is submitted, so with
+`overlap_backward` set it before backward()): the gradients are those of `loss * loss_scale`, and come
+back divided by it — the engine-handled gradients (dense fp32 contiguous device) by a postscale of
+1 / loss_scale in the unpack kernel (together with the predivide's f), every other gradient by a torch
+multiply after its reduction. `grad_norm`, `max_grad_norm` and `found_nonfinite` then refer to the
+unscaled, averaged gradients, and no `unscale_` pass runs. `DynamicLossScaler` drives it. With an
+error-feedback compression, `gradient_predivide_factor = loss_scale` would keep the residuals in true
+units; the wrapper itself puts 1 / loss_scale on the postscale side.
 """
 import contextlib
 import functools
@@ -84,6 +100,8 @@ class DataParallelismDistributedOptimizer:
     track_grad_norm: bool = False
     max_grad_norm: float = None
     skip_nonfinite: bool = False
+    gradient_predivide_factor: float = 1.0
+    loss_scale: float = 1.0        # read at submission; the reduced gradients come back divided by it
     grad_norm: float = None        # of the last allreduce_gradients() (with tracking on)
     found_nonfinite: bool = False
     _ddl_name = 'DataParallelismDistributedOptimizer'
@@ -106,6 +124,17 @@ class DataParallelismDistributedOptimizer:
     def _engine_sumsq(g) -> bool:
         """Whether the engine takes this gradient's sum of squares (a dense fp32 device tensor)."""
         return g.is_cuda and not g.is_sparse and g.dtype == torch.float32 and g.is_contiguous()
+
+    def _unscale(self) -> float:
+        return 1.0 / float(self.loss_scale)
+
+    def _engine_factors(self, g):
+        """(prescale, postscale) of a gradient's request: the predivide factor and the loss scale for
+        the gradients the engine can scale, (1, 1) for the others (unscaled by torch afterwards)."""
+        if not self._engine_sumsq(g):
+            return 1.0, 1.0
+        f = float(self.gradient_predivide_factor)
+        return 1.0 / f, f * self._unscale()
 
     @staticmethod
     def _torch_sumsq(g) -> float:
@@ -155,9 +184,12 @@ class DataParallelismDistributedOptimizer:
                                'earlier backward passes inside no_sync()')
         if self._pinning() and not g.is_cuda and not g.is_pinned():
             p.grad = g = g.pin_memory()
-        self._grad_handles[p] = allreduce_async(g, key, self._comm(), output=g, op=self._op(),
-                                               compression=self.compression,
-                                               sumsq=self._tracking() and self._engine_sumsq(g))
+        pre, post = self._engine_factors(g)
+        h = allreduce_async(g, key, self._comm(), output=g, op=self._op(), compression=self.compression,
+                            sumsq=self._tracking() and self._engine_sumsq(g), prescale=pre, postscale=post)
+        # what torch still owes this gradient after its reduction (the loss scale at submission)
+        h._ddl_unscale = 1.0 if self._engine_sumsq(g) else self._unscale()
+        self._grad_handles[p] = h
 
     @contextlib.contextmanager
     def no_sync(self):
@@ -182,7 +214,13 @@ class DataParallelismDistributedOptimizer:
     def allreduce_gradients(self) -> None:
         comm = self._comm()
         track = self._tracking()
+        inv = self._unscale()
         if comm.size <= 1:
+            if inv != 1.0:  # nothing is communicated: the unscale is torch's
+                for group in self.param_groups:
+                    for p in group['params']:
+                        if p.grad is not None:
+                            p.grad.mul_(inv)
             if track:  # nothing is communicated: the norm of the local gradients
                 self._finish_norm([self._torch_sumsq(p.grad) for group in self.param_groups for p in group['params']
                                    if p.grad is not None], False)
@@ -194,6 +232,8 @@ class DataParallelismDistributedOptimizer:
         contributions = []
         for p, h in hooked.items():
             out = h.wait()
+            if getattr(h, '_ddl_unscale', 1.0) != 1.0:
+                out.mul_(h._ddl_unscale)
             if track:
                 contributions.append(h.sumsq if h.sumsq is not None else self._torch_sumsq(out))
             if not fused:
@@ -214,12 +254,17 @@ class DataParallelismDistributedOptimizer:
                 keys.append(self._key(gi, pi))
         # one keyed request per gradient (the reference builds one Allreduce op per grad,
         # distributed_optimizer.py:50-63), registered as one batch, reduced in place
+        factors = [self._engine_factors(g) for g in grads]
         handles = zip(params, allreduce_async_batch(grads, keys, comm, outputs=grads, op=self._op(),
                                                           compression=self.compression,
                                                           sumsq=[track and g is p.grad and self._engine_sumsq(g)
-                                                                 for p, g in zip(params, grads)]))
+                                                                 for p, g in zip(params, grads)],
+                                                          prescale=[a for a, _ in factors],
+                                                          postscale=[b for _, b in factors]))
         for p, h in handles:
             out = h.wait()
+            if inv != 1.0 and not self._engine_sumsq(out):
+                out.mul_(inv)
             if track:
                 contributions.append(h.sumsq if h.sumsq is not None else self._torch_sumsq(out))
             if not fused:
@@ -229,6 +274,8 @@ class DataParallelismDistributedOptimizer:
         # sparse gradients: every rank's rows gathered, values averaged (same order on all ranks)
         for p in sparse:
             p.grad = allreduce_gradient(p.grad, comm)  # (sparse: the allgather branch, fused_mean or not)
+            if inv != 1.0:
+                p.grad.mul_(inv)
             if track:  # averaged already: in the sums' units where the others are
                 contributions.append(self._torch_sumsq(p.grad) * (1.0 if fused else float(comm.size) ** 2))
         if track:
@@ -262,6 +309,58 @@ class DataParallelismDistributedOptimizer:
         return True
 
 
+class DynamicLossScaler:
+    """Dynamic loss scaling on top of the wrapper, with no pass over the gradients of its own: the
+    unscale is the engine's postscale (`optimizer.loss_scale`) and the overflow check is the engine's sum
+    of squares (`skip_nonfinite`).
+
+        scaler = DynamicLossScaler(optimizer)
+        scaler.scale(loss).backward()
+        taken = scaler.step()
+
+    `scale(loss)` sets `optimizer.loss_scale` and returns `loss * scale`. `step()` calls
+    `optimizer.step()` with `skip_nonfinite` on; when a gradient was not finite the step was skipped and
+    the scale is multiplied by `backoff_factor`, and after `growth_interval` consecutive clean steps by
+    `growth_factor`. Returns whether the step was taken. With powers of two every multiply is exact.
+    Every rank sees the same `found_nonfinite` (the engine's value is the same double everywhere), so the
+    scales stay in step without communication."""
+
+    def __init__(self, optimizer, init_scale: float = 2.0 ** 16, growth_factor: float = 2.0,
+                 backoff_factor: float = 0.5, growth_interval: int = 2000):
+        if not getattr(optimizer, 'is_distributed_optimizer', False):
+            raise TypeError('DynamicLossScaler needs an optimizer from data_parallelism_distributed_optimizer_wrapper')
+        if not (math.isfinite(init_scale) and init_scale > 0 and growth_factor >= 1.0 and 0.0 < backoff_factor <= 1.0
+                and growth_interval >= 1):
+            raise ValueError('DynamicLossScaler: init_scale > 0, growth_factor >= 1, 0 < backoff_factor <= 1, '
+                             'growth_interval >= 1')
+        self.optimizer = optimizer
+        self.loss_scale = float(init_scale)
+        self.growth_factor, self.backoff_factor = float(growth_factor), float(backoff_factor)
+        self.growth_interval = int(growth_interval)
+        self._clean = 0
+        optimizer.skip_nonfinite = True
+        optimizer.loss_scale = self.loss_scale
+
+    def scale(self, loss):
+        self.optimizer.loss_scale = self.loss_scale
+        return loss * self.loss_scale
+
+    def step(self, closure=None) -> bool:
+        opt = self.optimizer
+        opt.skip_nonfinite = True
+        opt.step(closure)
+        if opt.found_nonfinite:
+            self.loss_scale *= self.backoff_factor
+            self._clean = 0
+        else:
+            self._clean += 1
+            if self._clean >= self.growth_interval:
+                self.loss_scale *= self.growth_factor
+                self._clean = 0
+        opt.loss_scale = self.loss_scale
+        return not opt.found_nonfinite
+
+
 def data_parallelism_distributed_optimizer_wrapper(
         optimizer: torch.optim.Optimizer,
         communicator: Communicator = None,
@@ -272,7 +371,8 @@ def data_parallelism_distributed_optimizer_wrapper(
         compression=Compression.none,
         track_grad_norm: bool = False,
         max_grad_norm: float = None,
-        skip_nonfinite: bool = False) -> torch.optim.Optimizer:
+        skip_nonfinite: bool = False,
+        gradient_predivide_factor: float = 1.0) -> torch.optim.Optimizer:
     """Return an optimizer of a subclass of `type(optimizer)` whose step() first averages the
     gradients across `communicator` (default: the world). Parameter groups and state are
     shared with `optimizer`. `pin_host_gradients`: keep CPU gradients in pinned memory;
@@ -285,8 +385,9 @@ def data_parallelism_distributed_optimizer_wrapper(
     (Compression.fp16 / Compression.bf16): the dense fp32 device gradients are sent and summed as
     16-bit values on both paths, step() and the `overlap_backward` hooks, and every rank must build
     the wrapper with the same value. fp16 OVERFLOWS: a gradient, or a partial sum over the ranks,
-    above 65504 in magnitude becomes inf and one below 6e-8 becomes 0, so use fp16 only with a loss
-    scale that keeps the gradients in range; bf16 has fp32's range (8 bits of precision) and is the
+    above 65504 in magnitude becomes inf and one below 6e-8 becomes 0: pass
+    `gradient_predivide_factor` = the size, so that what is summed in fp16 is the mean, and keep the
+    gradients themselves in range with a loss scale (`optimizer.loss_scale`); bf16 has fp32's range (8 bits of precision) and is the
     recommended choice for unscaled gradients. Compression.fp16_feedback / .bf16_feedback add error
     feedback (module docstring): it costs one fp32 copy of every compressed gradient in device
     memory and a pack of 14 instead of 6 bytes per element; reset it with
@@ -295,7 +396,8 @@ def data_parallelism_distributed_optimizer_wrapper(
     after every allreduce_gradients(), from the engine's sums of squares (module docstring);
     `max_grad_norm`: clip the averaged gradients to that global L2 norm before the step;
     `skip_nonfinite`: skip the wrapped step() when a gradient holds an inf or NaN. The last two imply
-    the first."""
+    the first. `gradient_predivide_factor` (finite, > 0; the same on every rank): the engine-handled
+    gradients are divided by it before the sum and multiplied by it after (module docstring)."""
     opt_cls = optimizer.__class__
     assert issubclass(opt_cls, torch.optim.Optimizer)
     cls = type(opt_cls.__name__, (DataParallelismDistributedOptimizer, opt_cls), {})
@@ -309,6 +411,11 @@ def data_parallelism_distributed_optimizer_wrapper(
     res.track_grad_norm = bool(track_grad_norm)
     res.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
     res.skip_nonfinite = bool(skip_nonfinite)
+    f = float(gradient_predivide_factor)
+    if not math.isfinite(f) or f <= 0.0:
+        raise ValueError(f'gradient_predivide_factor must be finite and > 0, not {gradient_predivide_factor!r}')
+    res.gradient_predivide_factor = f
+    res.loss_scale = float(getattr(optimizer, 'loss_scale', 1.0))
     if overlap_backward:
         if bucket_bytes:
             from ddl.torch import config

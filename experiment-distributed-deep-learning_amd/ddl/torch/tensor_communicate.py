@@ -461,6 +461,35 @@ def _check_sumsq(tensors, op: int, what: str) -> None:
             raise ValueError(f'{what}: sumsq is defined for float32 tensors, not {t.dtype}')
 
 
+def _scale_factor(value, what: str) -> float:
+    """A prescale / postscale as the engine takes it: an fp32 value, finite and > 0 (ValueError otherwise)."""
+    import math
+    import struct
+    f = float(value)
+    if not math.isfinite(f) or f <= 0.0:
+        raise ValueError(f'{what}: a scale factor must be finite and > 0, not {value!r}')
+    try:
+        f = struct.unpack('f', struct.pack('f', f))[0]  # what the engine will see
+    except OverflowError:
+        f = math.inf
+    if not math.isfinite(f) or f <= 0.0:
+        raise ValueError(f'{what}: the scale factor {value!r} is not a finite, positive float32')
+    return f
+
+
+def _check_scale(tensors, op: int, what: str) -> None:
+    """A factor other than 1 is the engine's DDL_ALLREDUCE_SCALE: dense fp32 device tensors, SUM or AVG.
+    Raised before any library call."""
+    if int(op) in (cb.OP_MIN, cb.OP_MAX):
+        raise ValueError(f'{what}: prescale / postscale are defined for OP_SUM and OP_AVG, not OP_MIN / OP_MAX')
+    for t in tensors:
+        if t.is_sparse or not t.is_cuda:
+            raise ValueError(f'{what}: prescale / postscale need a dense device tensor, not a {t.device.type} '
+                             f'{"sparse " if t.is_sparse else ""}one')
+        if t.dtype != torch.float32:
+            raise ValueError(f'{what}: prescale / postscale are defined for float32 tensors, not {t.dtype}')
+
+
 def _same_memory(a: torch.Tensor, b: torch.Tensor, what: str) -> int:
     ma, mb = memory_kind(a, f'{what} input'), memory_kind(b, f'{what} output')
     if ma != mb:
@@ -470,7 +499,7 @@ def _same_memory(a: torch.Tensor, b: torch.Tensor, what: str) -> int:
 
 def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator = None,
                     output: torch.Tensor = None, op: int = cb.OP_SUM, compression=Compression.none,
-                    sumsq: bool = False) -> Handle:
+                    sumsq: bool = False, prescale: float = 1.0, postscale: float = 1.0) -> Handle:
     """Register a keyed allreduce (`op`: cb.OP_SUM, cb.OP_AVG for the mean, cb.OP_MIN / cb.OP_MAX for
     the element-wise minimum / maximum — like a compression, the same on every rank for a name, and
     never together with one: ValueError); returns a Handle.
@@ -486,6 +515,11 @@ def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator 
     wait(), `handle.sumsq` is a Python float, the fp64 sum of the squares of the output's elements,
     taken by the engine where it writes them (include/ddl_amd.h "Sum of squares": no extra pass in a
     fused plan, the same bits on every rank, finite if and only if every element is finite).
+    `prescale` / `postscale` (a dense fp32 device tensor, OP_SUM or OP_AVG; a factor must be finite and
+    > 0; anything else: ValueError before anything is submitted): every element is multiplied by
+    `prescale` on its way into the reduction and every result, behind OP_AVG's quotient, by `postscale`
+    on its way into the output — by the kernels that move those bytes anyway (include/ddl_amd.h "Scale
+    factors"). They compose with `op`, `compression` and `sumsq` (which is then of the scaled output).
 
     `name` plays the role of the TF op name: the same name on every rank identifies the same
     gradient, and only one request per name may be pending (TensorCommunicateRequest.h:21).
@@ -495,6 +529,10 @@ def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator 
     _check_op_compression(op, compression)
     if sumsq:
         _check_sumsq((tensor,) if output is None else (tensor, output), op, 'allreduce_async')
+    pre, post = _scale_factor(prescale, 'allreduce_async'), _scale_factor(postscale, 'allreduce_async')
+    scaled = pre != 1.0 or post != 1.0
+    if scaled:
+        _check_scale((tensor,) if output is None else (tensor, output), op, 'allreduce_async')
     communicator = _comm(communicator)
     out = torch.empty_like(tensor) if output is None else output
     mem = _same_memory(tensor, out, 'allreduce_async')
@@ -504,15 +542,22 @@ def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator 
     key, dt, stream = name.encode(), ddl_dtype(tensor), stream_handle_for(tensor)
     if _compressible(tensor, communicator, wire_flag(compression), mem):
         op = int(op) | wire_flag(compression)
-    if sumsq:
+    if sumsq or scaled:
         import ctypes
         value = (ctypes.c_double * 1)()  # lives in the group's keep until the request has completed
         group = _Completion(1, (tensor, out, value))
         h = _NativeHandle(name, out, None, group, 0)
-        h._sumsq_ref = (value, 0)
-        # DDL_ALLREDUCE_SUMSQ: the user pointer is a ddl_sumsq_arg (read during the call) naming the slot and the double
-        arg = cb.SumsqArg(group.slots()[0], ctypes.addressof(value))
-        op, user = int(op) | cb.SUMSQ, ctypes.addressof(arg)
+        if sumsq:
+            h._sumsq_ref = (value, 0)
+        # DDL_ALLREDUCE_SUMSQ / _SCALE: the user pointer is a ddl_sumsq_arg / ddl_scale_arg (read during the
+        # call) naming the slot, the double and the factors
+        if scaled:
+            arg = cb.ScaleArg(group.slots()[0], ctypes.addressof(value) if sumsq else None, pre, post)
+            op = int(op) | cb.SCALE | (cb.SUMSQ if sumsq else 0)
+        else:
+            arg = cb.SumsqArg(group.slots()[0], ctypes.addressof(value))
+            op = int(op) | cb.SUMSQ
+        user = ctypes.addressof(arg)
     else:
         group = _Completion(1, (tensor, out))
         h = _NativeHandle(name, out, None, group, 0)  # the group holds the tensors
@@ -527,7 +572,7 @@ def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator 
 
 
 def allreduce_async_batch(tensors, names, communicator: Communicator = None, outputs=None, op: int = cb.OP_SUM,
-                          compression=Compression.none, sumsq=False):
+                          compression=Compression.none, sumsq=False, prescale=1.0, postscale=1.0):
     """Register several keyed allreduces at once (one engine wake-up, one input-ready event), all
     with `op` (cb.OP_SUM, cb.OP_AVG for the mean, cb.OP_MIN / cb.OP_MAX); returns one Handle per tensor. Same key rules as `allreduce_async`; device and host tensors
     may be mixed (one submission per memory kind). `compression` (Compression.fp16 / .bf16) applies
@@ -536,7 +581,10 @@ def allreduce_async_batch(tensors, names, communicator: Communicator = None, out
     come back in the caller's order either way. The error-feedback kinds as in `allreduce_async`:
     one residual per name, so stable names. `sumsq` as in `allreduce_async`: True for every tensor, or
     one bool per tensor (a batch may mix requests with and without it); the flagged tensors must be
-    dense fp32 device tensors (ValueError otherwise) and their handles carry `sumsq` after wait()."""
+    dense fp32 device tensors (ValueError otherwise) and their handles carry `sumsq` after wait().
+    `prescale` / `postscale` as in `allreduce_async`: one value for every tensor, or one per tensor (a
+    batch may mix scaled and unscaled requests); the tensors with a factor other than 1 must be dense
+    fp32 device tensors (ValueError otherwise, before anything is submitted)."""
     import ctypes
     _check_op_compression(op, compression)
     tensors = list(tensors)
@@ -549,6 +597,17 @@ def allreduce_async_batch(tensors, names, communicator: Communicator = None, out
     if any(wanted):
         outs_ = tensors if outputs is None else list(outputs)
         _check_sumsq([x for t, o, w in zip(tensors, outs_, wanted) if w for x in (t, o)], op, 'allreduce_async_batch')
+
+    def factors(v, what):
+        vs = list(v) if isinstance(v, (list, tuple)) or hasattr(v, '__len__') else [v] * len(tensors)
+        if len(vs) != len(tensors):
+            raise ValueError(f'{what}: one value, or one per tensor')
+        return [_scale_factor(x, f'allreduce_async_batch {what}') for x in vs]
+    pres, posts = factors(prescale, 'prescale'), factors(postscale, 'postscale')
+    scaled = [a != 1.0 or b != 1.0 for a, b in zip(pres, posts)]
+    if any(scaled):
+        outs_ = tensors if outputs is None else list(outputs)
+        _check_scale([x for t, o, w in zip(tensors, outs_, scaled) if w for x in (t, o)], op, 'allreduce_async_batch')
     communicator = _comm(communicator)
     outputs = [torch.empty_like(t) for t in tensors] if outputs is None else list(outputs)
     k = len(tensors)
@@ -593,7 +652,16 @@ def allreduce_async_batch(tensors, names, communicator: Communicator = None, out
             ins = (ctypes.c_void_p * m)(*[t.data_ptr() for t in ts])
             outs = ins if in_place else (ctypes.c_void_p * m)(*[o.data_ptr() for o in os_])
             stat = 0
-            if any(wanted[i] for i in idx):
+            if any(scaled[i] for i in idx):
+                # DDL_ALLREDUCE_SCALE: every user pointer is a ddl_scale_arg (read during the call) naming the
+                # request's slot, its factors and, with the SUMSQ bit, its double (NULL where not wanted)
+                want = any(wanted[i] for i in idx)
+                base, stat = ctypes.addressof(values) if want else 0, cb.SCALE | (cb.SUMSQ if want else 0)
+                args = (cb.ScaleArg * m)(*[cb.ScaleArg(slots[i], base + 8 * i if wanted[i] else None, pres[i], posts[i])
+                                           for i in idx])
+                step = ctypes.sizeof(cb.ScaleArg)
+                users = (ctypes.c_void_p * m)(*[ctypes.addressof(args) + j * step for j in range(m)])
+            elif any(wanted[i] for i in idx):
                 # DDL_ALLREDUCE_SUMSQ: every user pointer is a ddl_sumsq_arg (read during the call) naming
                 # the request's slot and its double, NULL where not wanted (device tensors: _check_sumsq)
                 base, stat = ctypes.addressof(values), cb.SUMSQ

@@ -99,6 +99,21 @@ struct ddl_sumsq_arg {
     double *sumsq; /* where the sum of squares goes, or NULL */
 };
 
+/* Scale factors of a keyed device allreduce of DDL_FLOAT tensors (MI355X extension, Horovod's
+ * prescale_factor / postscale_factor; the data-plane section): OR-ed into the `op` of the same entry
+ * points as DDL_ALLREDUCE_SUMSQ, SUM or AVG, with or without a wire flag, the feedback bit and
+ * DDL_ALLREDUCE_SUMSQ. With the bit `user` (every users[i] of a batch) points to a ddl_scale_arg, read
+ * during the call only; `done` receives arg->user. Its first two members are ddl_sumsq_arg's, so with
+ * DDL_ALLREDUCE_SCALE | DDL_ALLREDUCE_SUMSQ `sumsq` is read from the same struct; without the SUMSQ bit
+ * `sumsq` is ignored. */
+enum ddl_allreduce_scale { DDL_ALLREDUCE_SCALE = 0x4000 };
+struct ddl_scale_arg {
+    void *user;      /* what `done` receives */
+    double *sumsq;   /* with DDL_ALLREDUCE_SUMSQ: where the sum of squares goes, or NULL */
+    float prescale;  /* finite, > 0; 1.0f = absent */
+    float postscale; /* finite, > 0; 1.0f = absent */
+};
+
 typedef long long ddl_communicator_id;
 
 /* Completion callback of a keyed request: TensorCommunicateRequest::done(StatusCode)
@@ -376,7 +391,43 @@ void py_error(const char *log_str);
  * DDL_MEMORY_HOST DDL_STATUS_INVALID_ARGUMENT; the bit with a NULL `user` (`users`, users[i]), and the
  * bit on ddl_allreduce, ddl_allreduce_batch or ddl_allreduce_host, DDL_STATUS_INVALID_ARGUMENT; the
  * op's own refusals apply as without the bit. With every arg->sumsq NULL the request is the one
- * without the bit. No new entry point: the deployment surface is unchanged. */
+ * without the bit. No new entry point: the deployment surface is unchanged.
+ *
+ * Scale factors (DDL_ALLREDUCE_SCALE in `op`, `user` a ddl_scale_arg): two optional fp32 factors of a keyed
+ * DDL_FLOAT device request with op SUM or AVG (a wire flag, the feedback bit and DDL_ALLREDUCE_SUMSQ
+ * allowed), each finite and > 0, 1.0f meaning "absent". prescale a multiplies every element on its way
+ * INTO the reduction, postscale b every result on its way into `out`; both products are taken by the
+ * kernels that already move those bytes (csrc/pack.hip, the scaled Ops), so a loss scale's unscale and
+ * the division that keeps an fp16 wire's partial sums under 65504 cost no pass over the gradients.
+ * All arithmetic is fp32, round to nearest even, subnormals kept; every product is rounded on its own
+ * and is never fused with a neighbouring addition. With (x) the product, (+) the sum, (/) the quotient:
+ *   contribution of a rank, element g:  c = g (x) a   (a = 1: c = g, the bits untouched, no multiply);
+ *     uncompressed c enters the fusion buffer; with a wire flag w = narrow(c); with the feedback bit
+ *     v = c (+) r and the rule of the feedback paragraph unchanged — THE RESIDUAL IS IN PRESCALED UNITS:
+ *     with prescale = 1 / S for a loss scale S it is in true-gradient units and survives a change of S;
+ *   reduction: unchanged — the same bytes, schedules and order of additions;
+ *   result, element s of the reduced stream:  y = s (widened from the wire);  AVG: y = y (/) (float)P,
+ *     the correctly rounded quotient;  b != 1: y = y (x) b;  y is stored to `out`.
+ * The sum of squares, when wanted, is of these final y, in the order above. "*sumsq is finite if and
+ * only if every stored element is finite" keeps holding. A NaN stays a NaN (payload unspecified).
+ * Like SUM against AVG and the sum of squares the factors are rank-local: they are in no fusion group
+ * key, plan cut or negotiation, one plan or launch may mix scaled and unscaled requests (a segment
+ * without a factor inside a scaled launch is moved exactly as the unscaled kernel moves it), requests
+ * without factors run exactly the launches, kernels and tables they ran before, and ranks that
+ * disagree about a factor get different numbers and never hang.
+ * Cost. Fused plans: none beyond one multiply per element in the pack / unpack launch. A plan of one
+ * uncompressed request keeps its in-place allreduce over exactly the elements it reduces without
+ * factors (so ranks that disagree about a factor still post the same collective): a prescale is ONE
+ * in-place launch over `out` ahead of it (behind a device copy where out != in), a postscale ONE
+ * in-place launch behind it that takes AVG's quotient and the factor together.
+ * P = 1: with "one_rank_shortcut" 1, out = (g (x) a) (x) b, each factor skipped when it is 1, no wire
+ * rounding; with 0 the data plane runs and defines the value.
+ * Refusals, before anything is registered (the communicator works afterwards): a factor that is not
+ * finite or is <= 0 returns DDL_STATUS_INVALID_ARGUMENT; a factor other than 1 with a dtype other than
+ * DDL_FLOAT DDL_STATUS_UNSUPPORTED_DTYPE, with MIN / MAX or DDL_MEMORY_HOST DDL_STATUS_INVALID_ARGUMENT;
+ * the bit with a NULL `user` (`users`, users[i]), and the bit on ddl_allreduce, ddl_allreduce_batch or
+ * ddl_allreduce_host, DDL_STATUS_INVALID_ARGUMENT. If both factors are 1 the request is the one without
+ * the bit. No new entry point. */
 /* recv = SUM over ranks of send (elementwise), bit for bit the reference's MPI_Allreduce (MPICH
  * 3.3.2's order) with reference_order 1. The schedule is the tuned one for the bucket's size
  * class: by default at P > 2 the direct reduce-scatter (slices of every chunk to every peer over

@@ -163,6 +163,22 @@ int ddl_unpack_ops_sumsq(void *const *dsts, const void *src, const size_t *bytes
                          int divisor, void *hip_stream, const unsigned char *want, double *sumsq_out);
 int ddl_unpack_cvt_sumsq(void *const *dsts, const void *src, const size_t *elements, const int *ops, int count,
                          int wire_dtype, int divisor, void *hip_stream, const unsigned char *want, double *sumsq_out);
+/* The scaled copies (ddl_amd.h "Scale factors"; csrc/pack.hip ScaleGatherOp, ScaleCvtPackOp, ScaleScatterOp,
+ * ScaleCvtUnpackOp, k_seg_sumsq_scale): fp32 tensors of elements[i] values, scale[i] one fp32 factor per
+ * segment (finite, > 0; 1.0f = the segment is moved as the unscaled kernel moves it; with every factor of
+ * the non-empty segments 1 the launch IS the unscaled kernel's).
+ * ddl_pack_scale = ddl_pack (wire_dtype 0, segments of 4 * elements[i] bytes), ddl_pack_cvt (wire_dtype
+ * DDL_HALF / DDL_BFLOAT16, residuals NULL) or ddl_pack_cvt_fb (residuals non-NULL) with every element
+ * multiplied first.
+ * ddl_unpack_scale = ddl_unpack_ops on DDL_FLOAT (wire_dtype 0) or ddl_unpack_cvt, with the factor behind
+ * the quotient; want != NULL: the _sumsq forms (sumsq_out[i] as there, of the scaled values; waits for
+ * hip_stream). src == NULL (wire_dtype 0, want NULL): the in-place form — the AVG and the scaled segments
+ * are rewritten where they are, the others untouched. */
+int ddl_pack_scale(void *dst, const void *const *srcs, void *const *residuals, const size_t *elements, int count,
+                   int wire_dtype, const float *scale, void *hip_stream);
+int ddl_unpack_scale(void *const *dsts, const void *src, const size_t *elements, const int *ops, int count,
+                     int wire_dtype, int divisor, const float *scale, void *hip_stream, const unsigned char *want,
+                     double *sumsq_out);
 /* ddl_pack_cvt with error feedback (DDL_ALLREDUCE_WIRE_FEEDBACK; k_seg<CvtPackOp<WIRE, true>>) on caller-owned
  * residuals: residuals[i] = elements[i] fp32 values (4-byte aligned), added to segment i before the
  * rounding and overwritten with what the rounding removed; NULL = segment i is converted as
@@ -249,6 +265,16 @@ int ddl_testing_thread_fused_allreduce_sumsq(int nranks, int count, const void *
                                              const size_t *elements, const int *ops, int wire_dtype, void *hip_stream,
                                              size_t *subplans, const unsigned char *want, double *sumsq_out,
                                              size_t *cut_segs, size_t *cut_elems, int max_cuts, int *ncuts);
+/* ddl_testing_thread_fused_allreduce_sumsq with the scale factors and the feedback residuals: prescale[i]
+ * / postscale[i] per segment (NULL = none; the same on every virtual rank), residuals[r * count + i] as
+ * in the _wire_fb entry (NULL = none; only with a wire dtype), want / sumsq_out / cuts as in the _sumsq
+ * entry (want NULL = no statistic, and the call does not wait for hip_stream). */
+int ddl_testing_thread_fused_allreduce_scale(int nranks, int count, const void *const *srcs, void *const *dsts,
+                                             void *const *residuals, const size_t *elements, const int *ops,
+                                             int wire_dtype, const float *prescale, const float *postscale,
+                                             void *hip_stream, size_t *subplans, const unsigned char *want,
+                                             double *sumsq_out, size_t *cut_segs, size_t *cut_elems, int max_cuts,
+                                             int *ncuts);
 /* Data movement of the thread worlds made from now on: rccl = 0 device copies (default); 1 every
  * matched send / receive pair goes through RcclTransport::group as a self send + self receive on
  * the RCCL loopback communicator (ddl_rccl_loopback_init first), posted on the receiver's stream
