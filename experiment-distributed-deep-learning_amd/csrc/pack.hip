@@ -19,6 +19,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <string>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -124,6 +126,47 @@ void launch(bool narrow, dim3 g, hipStream_t stream, char *fl, const SegDesc *dd
     else hipLaunchKernelGGL((k_seg<Op, false, A...>), g, dim3(64), 0, stream, fl, dd, db, map, a...);
 }
 
+// The launch's extra argument of type T, wherever it stands in `a...` (an Op takes its tables through
+// one variadic constructor). A launch that does not carry it does not compile.
+template <class T, class A0, class... A> __device__ inline T arg_of(A0 a0, A... a) {
+    if constexpr (std::is_same_v<T, A0>) return a0;
+    else return arg_of<T>(a...);
+}
+
+// ---- the scale factors (DDL_ALLREDUCE_SCALE: prescale in the packs, postscale in the unpacks) -------
+// Every Op that can scale has a SCALE parameter; SCALE = false is the kernel it was, its argument list
+// included. A scaled launch carries one fp32 factor per segment (a const float * behind the launch's
+// other arguments: scl[seg], uploaded behind the block bases and the residual addresses); a segment
+// flagged kSegScale has every element multiplied by it, a segment without the flag is moved exactly as
+// the unscaled Op moves it (no multiply is issued: the bits are untouched). fp32 tensors only. Every
+// product is one fp32 operation rounded to nearest even with subnormals kept, and never part of an fma:
+// hipcc contracts a * b + c by default, so the multiply is mul_rn, compiled with contraction off.
+//   pack:    c = g (x) a, then what the unscaled pack does with c (store / narrow / feedback's c (+) r)
+//   unpack:  y = s (widened), y = y (/) (float)P for kSegAvg, y = y (x) b for kSegScale, store y
+__device__ inline float mul_rn(float x, float a) {
+#pragma clang fp contract(off)
+    return x * a;
+}
+
+// A segment's factor inside a launch: nothing at all when SCALE is false.
+template <bool SCALE> struct Factor {
+    float a = 1.0f;
+    bool on = false;
+    template <class... A> __device__ Factor(const SegDesc &sd, int seg, A... x) {
+        if constexpr (SCALE) {
+            on = (sd.vec & kSegScale) != 0;
+            if (on) a = arg_of<const float *>(x...)[seg];
+        }
+    }
+    __device__ float operator()(float x) const { return SCALE && on ? mul_rn(x, a) : x; }
+    template <int N> __device__ void operator()(float (&x)[N]) const {
+        if (SCALE && on) {
+#pragma unroll
+            for (int k = 0; k < N; ++k) x[k] = mul_rn(x[k], a);
+        }
+    }
+};
+
 // ---- the plain copies ---------------------------------------------------------------------------
 // DIR 0: gather segments -> flat; DIR 1: scatter flat -> segments. Bytes.
 template <int DIR> struct CopyOp {
@@ -182,35 +225,54 @@ template <> struct DivTraits<kDivBF16> {
     }
 };
 
-template <int DT> struct DivOp {
+// What every scatter does to the values on their way into a tensor, written once (DivOp, CvtUnpackOp
+// and k_seg_sumsq after their loads and widenings): q(x, P) for a kSegAvg segment, then (SCALE) the
+// factor for a kSegScale one. This order is contract.
+template <int DT, bool SCALE> struct Chain {
+    static_assert(!SCALE || DT == kDivF32, "scale factors are defined for float32 tensors");
     using Tr = DivTraits<DT>;
-    using T = typename Tr::T;
+    typename Tr::D dv;
+    bool avg;
+    Factor<SCALE> fac;
+    template <class... A>
+    __device__ Chain(const SegDesc &sd, int seg, typename Tr::D divisor, A... a)
+        : dv(divisor), avg((sd.vec & kSegAvg) != 0), fac(sd, seg, a...) {}
+    template <int N> __device__ void operator()(typename Tr::T (&x)[N]) const {
+        if (avg) {
+#pragma unroll
+            for (int k = 0; k < N; ++k) x[k] = Tr::q(x[k], dv);
+        }
+        if constexpr (SCALE) fac(x);
+    }
+};
+
+// SCALE (kDivF32 only): the scaled scatter, with the factor table behind the divisor.
+template <int DT, bool SCALE = false> struct DivOp {
+    using T = typename DivTraits<DT>::T;
     static constexpr uint32_t kUnit = sizeof(T);
-    static constexpr uint32_t kPer = 16 / sizeof(T);
     union Vec {
         u32x4 v;
-        T e[kPer];
+        T e[16 / sizeof(T)];
     };
     char *tp;
     const char *sp;
-    typename Tr::D dv;
-    bool avg, v;
-    __device__ DivOp(const char *flat, const SegDesc &sd, int, double divisor)
-        : tp(reinterpret_cast<char *>(sd.ptr)), sp(flat ? flat + sd.off : tp), dv((typename Tr::D)divisor),
-          avg((sd.vec & kSegAvg) != 0), v((sd.vec & kSegVec) != 0) {}
+    Chain<DT, SCALE> val;
+    bool v;
+    template <class... A>
+    __device__ DivOp(const char *flat, const SegDesc &sd, int seg, double divisor, A... a)
+        : tp(reinterpret_cast<char *>(sd.ptr)), sp(flat ? flat + sd.off : tp),
+          val(sd, seg, (typename DivTraits<DT>::D)divisor, a...), v((sd.vec & kSegVec) != 0) {}
     __device__ bool vector() const { return v; }
     __device__ void vec(uint64_t b) const {
         Vec x;
         x.v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(sp + b));
-        if (avg) {
-#pragma unroll
-            for (uint32_t k = 0; k < kPer; ++k) x.e[k] = Tr::q(x.e[k], dv);
-        }
+        val(x.e);
         __builtin_nontemporal_store(x.v, reinterpret_cast<u32x4 *>(tp + b));
     }
     __device__ void elem(uint64_t e) const {
-        const T x = reinterpret_cast<const T *>(sp)[e];
-        reinterpret_cast<T *>(tp)[e] = avg ? Tr::q(x, dv) : x;
+        T x[1] = {reinterpret_cast<const T *>(sp)[e]};
+        val(x);
+        reinterpret_cast<T *>(tp)[e] = x[0];
     }
 };
 
@@ -257,7 +319,7 @@ template <class T> union Wire8 {
 // w goes to the flat buffer, r' replaces r. One fp32 rounding (g + r, nearest even, subnormals kept)
 // beyond the wire's own: v - widen(w) is exact whenever widen(w) is finite. A NaN or inf in v, or
 // an overflow of the narrowing, clears the residual. The plain feedback pack has no multiply, so nothing
-// can contract; the scaled one (ScaleCvtPackOp below) multiplies first, through mul_rn, whose product is
+// can contract; the scaled one (SCALE) multiplies first, through mul_rn, whose product is
 // rounded on its own and never fuses with this addition. No reciprocal. Moves 14 bytes per element against the plain converting pack's 6: the vector path
 // (tensor AND residual 16-byte aligned) is two 16-byte loads from each, one 16-byte wire store and
 // two 16-byte residual stores. The tensor loads and all stores are non-temporal (the residual is
@@ -275,7 +337,9 @@ __device__ inline typename WireTraits<WIRE>::T feedback(float g, float &r) {
     return w;
 }
 
-template <int WIRE, bool FB> struct CvtPackOp {
+// SCALE: the product ahead of the narrowing (FB: ahead of the residual's addition, so the residual is in
+// prescaled units); the factor table behind the residual table.
+template <int WIRE, bool FB, bool SCALE = false> struct CvtPackOp {
     using Tr = WireTraits<WIRE>;
     using T = typename Tr::T;
     static constexpr uint32_t kUnit = sizeof(T);
@@ -283,19 +347,25 @@ template <int WIRE, bool FB> struct CvtPackOp {
     const float *tp;
     float *rs;
     bool v;
-    __device__ CvtPackOp(char *flat, const SegDesc &sd, int)
+    Factor<SCALE> fac;
+    template <class... A>
+    __device__ CvtPackOp(char *flat, const SegDesc &sd, int seg, A... a)
         : fl(reinterpret_cast<T *>(flat + sd.off)), tp(reinterpret_cast<const float *>(sd.ptr)), rs(nullptr),
-          v((sd.vec & kSegVec) != 0) {}
-    __device__ CvtPackOp(char *flat, const SegDesc &sd, int seg, const uint64_t *__restrict__ res)
-        : fl(reinterpret_cast<T *>(flat + sd.off)), tp(reinterpret_cast<const float *>(sd.ptr)),
-          rs(reinterpret_cast<float *>(res[seg])),  // tensor or residual only 4-byte aligned: elements
-          v((sd.vec & kSegVec) != 0 && (res[seg] & 15u) == 0) {}
+          v((sd.vec & kSegVec) != 0), fac(sd, seg, a...) {
+        if constexpr (FB) {  // tensor or residual only 4-byte aligned: elements
+            const uint64_t r = arg_of<const uint64_t *>(a...)[seg];
+            rs = reinterpret_cast<float *>(r);
+            v = v && (r & 15u) == 0;
+        }
+    }
     __device__ bool vector() const { return v; }
     __device__ void vec(uint64_t b) const {
         const u32x4 *src = reinterpret_cast<const u32x4 *>(tp + b / sizeof(T));
         F32x4 lo, hi;
         lo.v = __builtin_nontemporal_load(src);
         hi.v = __builtin_nontemporal_load(src + 1);
+        fac(lo.e);
+        fac(hi.e);
         Wire8<T> o;
         if (FB && rs) {
             u32x4 *rv = reinterpret_cast<u32x4 *>(rs + b / sizeof(T));
@@ -321,67 +391,55 @@ template <int WIRE, bool FB> struct CvtPackOp {
     __device__ void elem(uint64_t e) const {
         if (FB && rs) {
             float r = rs[e];
-            fl[e] = feedback<WIRE>(tp[e], r);
+            fl[e] = feedback<WIRE>(fac(tp[e]), r);
             rs[e] = r;
         } else {
-            fl[e] = Tr::narrow(tp[e]);
+            fl[e] = Tr::narrow(fac(tp[e]));
         }
     }
 };
 
-template <int WIRE> struct CvtUnpackOp {
+// SCALE: the factor behind the quotient; the factor table behind the divisor.
+template <int WIRE, bool SCALE = false> struct CvtUnpackOp {
     using Tr = WireTraits<WIRE>;
     using T = typename Tr::T;
     static constexpr uint32_t kUnit = sizeof(T);
+    union F32x8 {
+        u32x4 v[2];
+        float e[8];
+    };
     const T *fl;
     float *tp;
-    float divisor;
-    bool avg, v;
-    __device__ CvtUnpackOp(const char *flat, const SegDesc &sd, int, float dv)
-        : fl(reinterpret_cast<const T *>(flat + sd.off)), tp(reinterpret_cast<float *>(sd.ptr)), divisor(dv),
-          avg((sd.vec & kSegAvg) != 0), v((sd.vec & kSegVec) != 0) {}
+    Chain<kDivF32, SCALE> val;
+    bool v;
+    template <class... A>
+    __device__ CvtUnpackOp(const char *flat, const SegDesc &sd, int seg, float dv, A... a)
+        : fl(reinterpret_cast<const T *>(flat + sd.off)), tp(reinterpret_cast<float *>(sd.ptr)), val(sd, seg, dv, a...),
+          v((sd.vec & kSegVec) != 0) {}
     __device__ bool vector() const { return v; }
     __device__ void vec(uint64_t b) const {
         Wire8<T> x;
         x.v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(fl) + b));
-        F32x4 lo, hi;
+        F32x8 y;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            lo.e[k] = Tr::widen(x.e[k]);
-            hi.e[k] = Tr::widen(x.e[4 + k]);
+            y.e[k] = Tr::widen(x.e[k]);
+            y.e[4 + k] = Tr::widen(x.e[4 + k]);
         }
-        if (avg) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                lo.e[k] = lo.e[k] / divisor;
-                hi.e[k] = hi.e[k] / divisor;
-            }
-        }
+        val(y.e);
         u32x4 *dst = reinterpret_cast<u32x4 *>(tp + b / sizeof(T));
-        __builtin_nontemporal_store(lo.v, dst);
-        __builtin_nontemporal_store(hi.v, dst + 1);
+        __builtin_nontemporal_store(y.v[0], dst);
+        __builtin_nontemporal_store(y.v[1], dst + 1);
     }
     __device__ void elem(uint64_t e) const {
-        const float x = Tr::widen(fl[e]);
-        tp[e] = avg ? x / divisor : x;
+        float y[1] = {Tr::widen(fl[e])};
+        val(y);
+        tp[e] = y[0];
     }
 };
 
-// ---- the scaled copies (DDL_ALLREDUCE_SCALE: prescale in the packs, postscale in the unpacks) -------
-// The launch carries one fp32 factor per segment (scl[seg], uploaded behind the block bases and the
-// residual addresses); a segment flagged kSegScale has every element multiplied by it, a segment
-// without the flag is moved exactly as the unscaled Op moves it (no multiply is issued: the bits are
-// untouched). fp32 tensors only. Every product is one fp32 operation rounded to nearest even with
-// subnormals kept, and never part of an fma: hipcc contracts a * b + c by default, so the multiply
-// is mul_rn, compiled with contraction off.
-//   pack:    c = g (x) a, then what the unscaled pack does with c (store / narrow / feedback's c (+) r)
-//   unpack:  y = s (widened), y = y (/) (float)P for kSegAvg, y = y (x) b for kSegScale, store y
-__device__ inline float mul_rn(float x, float a) {
-#pragma clang fp contract(off)
-    return x * a;
-}
-
-// ScaleGatherOp: the uncompressed prescale, tensor -> flat. Whole fp32 elements (kUnit 4).
+// ScaleGatherOp: the uncompressed prescale, tensor -> flat. Whole fp32 elements (kUnit 4): CopyOp moves
+// bytes, so it has no twin to fold into.
 struct ScaleGatherOp {
     static constexpr uint32_t kUnit = 4;
     float *fl;
@@ -406,147 +464,14 @@ struct ScaleGatherOp {
     __device__ void elem(uint64_t e) const { fl[e] = sc ? mul_rn(tp[e], a) : tp[e]; }
 };
 
-// ScaleCvtPackOp<WIRE, FB>: CvtPackOp<WIRE, FB> with the product ahead of the narrowing (FB: ahead of
-// the residual's addition, so the residual is in prescaled units). FB carries both tables.
-template <int WIRE, bool FB> struct ScaleCvtPackOp {
-    using Tr = WireTraits<WIRE>;
-    using T = typename Tr::T;
-    static constexpr uint32_t kUnit = sizeof(T);
-    T *fl;
-    const float *tp;
-    float *rs;
-    float a;
-    bool sc, v;
-    __device__ ScaleCvtPackOp(char *flat, const SegDesc &sd, int seg, const float *__restrict__ scl)
-        : fl(reinterpret_cast<T *>(flat + sd.off)), tp(reinterpret_cast<const float *>(sd.ptr)), rs(nullptr),
-          sc((sd.vec & kSegScale) != 0), v((sd.vec & kSegVec) != 0) {
-        a = sc ? scl[seg] : 1.0f;
-    }
-    __device__ ScaleCvtPackOp(char *flat, const SegDesc &sd, int seg, const uint64_t *__restrict__ res,
-                              const float *__restrict__ scl)
-        : fl(reinterpret_cast<T *>(flat + sd.off)), tp(reinterpret_cast<const float *>(sd.ptr)),
-          rs(reinterpret_cast<float *>(res[seg])), sc((sd.vec & kSegScale) != 0),
-          v((sd.vec & kSegVec) != 0 && (res[seg] & 15u) == 0) {
-        a = sc ? scl[seg] : 1.0f;
-    }
-    __device__ bool vector() const { return v; }
-    __device__ void vec(uint64_t b) const {
-        const u32x4 *src = reinterpret_cast<const u32x4 *>(tp + b / sizeof(T));
-        F32x4 lo, hi;
-        lo.v = __builtin_nontemporal_load(src);
-        hi.v = __builtin_nontemporal_load(src + 1);
-        if (sc) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                lo.e[k] = mul_rn(lo.e[k], a);
-                hi.e[k] = mul_rn(hi.e[k], a);
-            }
-        }
-        Wire8<T> o;
-        if (FB && rs) {
-            u32x4 *rv = reinterpret_cast<u32x4 *>(rs + b / sizeof(T));
-            F32x4 rlo, rhi;
-            rlo.v = rv[0];  // plain loads, as CvtPackOp
-            rhi.v = rv[1];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                o.e[k] = feedback<WIRE>(lo.e[k], rlo.e[k]);
-                o.e[4 + k] = feedback<WIRE>(hi.e[k], rhi.e[k]);
-            }
-            __builtin_nontemporal_store(rlo.v, rv);
-            __builtin_nontemporal_store(rhi.v, rv + 1);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                o.e[k] = Tr::narrow(lo.e[k]);
-                o.e[4 + k] = Tr::narrow(hi.e[k]);
-            }
-        }
-        __builtin_nontemporal_store(o.v, reinterpret_cast<u32x4 *>(reinterpret_cast<char *>(fl) + b));
-    }
-    __device__ void elem(uint64_t e) const {
-        const float c = sc ? mul_rn(tp[e], a) : tp[e];
-        if (FB && rs) {
-            float r = rs[e];
-            fl[e] = feedback<WIRE>(c, r);
-            rs[e] = r;
-        } else {
-            fl[e] = Tr::narrow(c);
-        }
-    }
-};
-
-// ScaleScatterOp: fp32 flat -> tensor, or with flat == nullptr the segment itself (in place, as DivOp):
-// DivOp<kDivF32>'s quotient for kSegAvg, then the factor for kSegScale.
-struct ScaleScatterOp {
-    static constexpr uint32_t kUnit = 4;
-    float *tp;
-    const float *sp;
-    float dv, b_;
-    bool avg, sc, v;
-    __device__ ScaleScatterOp(const char *flat, const SegDesc &sd, int seg, float divisor, const float *__restrict__ scl)
-        : tp(reinterpret_cast<float *>(sd.ptr)), sp(flat ? reinterpret_cast<const float *>(flat + sd.off) : tp),
-          dv(divisor), avg((sd.vec & kSegAvg) != 0), sc((sd.vec & kSegScale) != 0), v((sd.vec & kSegVec) != 0) {
-        b_ = sc ? scl[seg] : 1.0f;
-    }
-    __device__ float y(float x) const {
-        if (avg) x = x / dv;
-        if (sc) x = mul_rn(x, b_);
-        return x;
-    }
-    __device__ bool vector() const { return v; }
-    __device__ void vec(uint64_t b) const {
-        F32x4 x;
-        x.v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(sp) + b));
-#pragma unroll
-        for (int k = 0; k < 4; ++k) x.e[k] = y(x.e[k]);
-        __builtin_nontemporal_store(x.v, reinterpret_cast<u32x4 *>(reinterpret_cast<char *>(tp) + b));
-    }
-    __device__ void elem(uint64_t e) const { tp[e] = y(sp[e]); }
-};
-
-// ScaleCvtUnpackOp<WIRE>: CvtUnpackOp<WIRE> with the factor behind the quotient.
-template <int WIRE> struct ScaleCvtUnpackOp {
-    using Tr = WireTraits<WIRE>;
-    using T = typename Tr::T;
-    static constexpr uint32_t kUnit = sizeof(T);
-    const T *fl;
-    float *tp;
-    float divisor, b_;
-    bool avg, sc, v;
-    __device__ ScaleCvtUnpackOp(const char *flat, const SegDesc &sd, int seg, float dv, const float *__restrict__ scl)
-        : fl(reinterpret_cast<const T *>(flat + sd.off)), tp(reinterpret_cast<float *>(sd.ptr)), divisor(dv),
-          avg((sd.vec & kSegAvg) != 0), sc((sd.vec & kSegScale) != 0), v((sd.vec & kSegVec) != 0) {
-        b_ = sc ? scl[seg] : 1.0f;
-    }
-    __device__ float y(float x) const {
-        if (avg) x = x / divisor;
-        if (sc) x = mul_rn(x, b_);
-        return x;
-    }
-    __device__ bool vector() const { return v; }
-    __device__ void vec(uint64_t b) const {
-        Wire8<T> x;
-        x.v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(fl) + b));
-        F32x4 lo, hi;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            lo.e[k] = y(Tr::widen(x.e[k]));
-            hi.e[k] = y(Tr::widen(x.e[4 + k]));
-        }
-        u32x4 *dst = reinterpret_cast<u32x4 *>(tp + b / sizeof(T));
-        __builtin_nontemporal_store(lo.v, dst);
-        __builtin_nontemporal_store(hi.v, dst + 1);
-    }
-    __device__ void elem(uint64_t e) const { tp[e] = y(Tr::widen(fl[e])); }
-};
-
 // ---- the unpacks with the sum of squares (DDL_ALLREDUCE_SUMSQ) -----------------------------
 // k_seg_sumsq: the plain, the dividing (WIRE < 0: fp32 flat buffer, DivOp<kDivF32>'s quotient) and the
 // converting scatter (WIRE = kWireF16 / kWireBF16: CvtUnpackOp's widening and quotient) of fp32
 // tensors that also leave, for every tile of a segment flagged kSegStat, the fp64 sum of the squares
 // of the fp32 values the tile stored in partials[tile]. Launched only when some segment of the launch
-// carries the flag; a segment without it is stored as k_seg stores it and writes no partial.
+// carries the flag; a segment without it is stored as k_seg stores it and writes no partial. SCALE: the
+// factor of a kSegScale segment behind the quotient, ahead of the store and the squares (the statistic is
+// of what is stored); the factor table is the launch's one extra argument. Scatters only (flat != nullptr).
 // The order of the additions (include/ddl_amd.h, tests/_sumsq_helpers.py): T = 256 elements per tile
 // and E = 4 per lane (WIRE < 0), or T = 512 and E = 8. Lane l of tile t owns elements
 // t*T + l*E .. + E-1 of the segment WHATEVER the tensor's alignment: acc = +0.0, acc += x*x left to
@@ -566,10 +491,10 @@ __device__ inline double wave_sum(double s) {
     return s;
 }
 
-template <int WIRE, bool NARROW, bool SCALE>
+template <int WIRE, bool NARROW, bool SCALE, class... A>
 __device__ __forceinline__ void seg_sumsq(const char *flat, const SegDesc *__restrict__ d,
                                           const uint32_t *__restrict__ blk_base, const void *__restrict__ map,
-                                          float divisor, double *__restrict__ partials, const float *__restrict__ scl) {
+                                          float divisor, double *__restrict__ partials, A... a) {
     constexpr int E = WIRE < 0 ? 4 : 8;
     constexpr uint64_t kUnit = WIRE < 0 ? 4 : 2;  // bytes of SegDesc::len per element
     const unsigned tile = blockIdx.x;
@@ -597,17 +522,7 @@ __device__ __forceinline__ void seg_sumsq(const char *flat, const SegDesc *__res
 #pragma unroll
                 for (int k = 0; k < E; ++k) x[k] = WireTraits<WIRE>::widen(w.e[k]);
             }
-            if (sd.vec & kSegAvg) {
-#pragma unroll
-                for (int k = 0; k < E; ++k) x[k] = x[k] / divisor;
-            }
-            if constexpr (SCALE) {
-                if (sd.vec & kSegScale) {
-                    const float b = scl[seg];
-#pragma unroll
-                    for (int k = 0; k < E; ++k) x[k] = mul_rn(x[k], b);
-                }
-            }
+            Chain<kDivF32, SCALE>(sd, seg, divisor, a...)(x);
             if (whole) {
 #pragma unroll
                 for (int h = 0; h < E / 4; ++h) {
@@ -646,21 +561,13 @@ __device__ __forceinline__ void seg_sumsq(const char *flat, const SegDesc *__res
     if (threadIdx.x == 0) partials[tile] = acc;
 }
 
-template <int WIRE, bool NARROW>
+// (the walk stays a function inlined into its kernel: written as the kernel itself, hipcc emits the
+// same additions with their operands swapped, and the unscaled code objects are to stay as they are)
+template <int WIRE, bool NARROW, bool SCALE, class... A>
 __global__ void __launch_bounds__(64) k_seg_sumsq(const char *flat, const SegDesc *__restrict__ d,
                                                   const uint32_t *__restrict__ blk_base, const void *__restrict__ map,
-                                                  float divisor, double *__restrict__ partials) {
-    seg_sumsq<WIRE, NARROW, false>(flat, d, blk_base, map, divisor, partials, nullptr);
-}
-
-// k_seg_sumsq with the postscale: the factor of a kSegScale segment behind the quotient, ahead of the
-// store and the squares (the statistic is of what is stored). Scatters only (flat != nullptr).
-template <int WIRE, bool NARROW>
-__global__ void __launch_bounds__(64) k_seg_sumsq_scale(const char *flat, const SegDesc *__restrict__ d,
-                                                        const uint32_t *__restrict__ blk_base,
-                                                        const void *__restrict__ map, float divisor,
-                                                        double *__restrict__ partials, const float *__restrict__ scl) {
-    seg_sumsq<WIRE, NARROW, true>(flat, d, blk_base, map, divisor, partials, scl);
+                                                  float divisor, double *__restrict__ partials, A... a) {
+    seg_sumsq<WIRE, NARROW, SCALE>(flat, d, blk_base, map, divisor, partials, a...);
 }
 
 // The finishing kernels: a segment's tile partials (nt of them, contiguous from tile0) into out[seg], in a
@@ -707,41 +614,31 @@ __global__ void __launch_bounds__(64) k_sumsq_finish2(const SegDesc *__restrict_
     if (threadIdx.x == 0) out[seg] = acc;
 }
 
-template <int WIRE>
+template <int WIRE, bool SCALE, class... A>
 void launch_sumsq(bool narrow, dim3 g, hipStream_t stream, const char *fl, const SegDesc *dd, const uint32_t *db,
-                  const void *map, float divisor, double *partials) {
-    if (narrow) hipLaunchKernelGGL((k_seg_sumsq<WIRE, true>), g, dim3(64), 0, stream, fl, dd, db, map, divisor, partials);
-    else hipLaunchKernelGGL((k_seg_sumsq<WIRE, false>), g, dim3(64), 0, stream, fl, dd, db, map, divisor, partials);
+                  const void *map, float divisor, double *partials, A... a) {
+    const auto k = narrow ? k_seg_sumsq<WIRE, true, SCALE, A...> : k_seg_sumsq<WIRE, false, SCALE, A...>;
+    hipLaunchKernelGGL(k, g, dim3(64), 0, stream, fl, dd, db, map, divisor, partials, a...);
 }
 
-template <int WIRE>
-void launch_sumsq_scale(bool narrow, dim3 g, hipStream_t stream, const char *fl, const SegDesc *dd, const uint32_t *db,
-                        const void *map, float divisor, double *partials, const float *scl) {
-    if (narrow)
-        hipLaunchKernelGGL((k_seg_sumsq_scale<WIRE, true>), g, dim3(64), 0, stream, fl, dd, db, map, divisor, partials, scl);
-    else
-        hipLaunchKernelGGL((k_seg_sumsq_scale<WIRE, false>), g, dim3(64), 0, stream, fl, dd, db, map, divisor, partials, scl);
+// A run-time fact of a launch as a compile-time constant: f(std::integral_constant), so that each
+// choice between two instances is written once.
+template <class F> void with_bool(bool b, F f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <class F> void with_wire(int wire, F f) {  // of the converting copies: float16, else bfloat16 (run_cvt)
+    if (wire == DDL_HALF) f(std::integral_constant<int, kWireF16>{});
+    else f(std::integral_constant<int, kWireBF16>{});
 }
 
-// What one run_ is, decided once: its kernel, its tables, its happens-before spans and its label.
-// kCvtUnpack and kCvtUnpackAvg share a kernel (the AVG segments carry kSegAvg).
-// kUnpackStat / kCvtUnpackStat / kSumsq: k_seg_sumsq (fp32 flat, wire flat, in place) and its finishing kernel.
-// The k*Scale ops: the scaled kernels (ScaleGatherOp ... k_seg_sumsq_scale), with the factor table.
-enum SegOp : int {
-    kPack, kUnpack, kUnpackAvg, kDivide, kCvtPack, kCvtPackFb, kCvtUnpack, kCvtUnpackAvg, kUnpackStat, kCvtUnpackStat, kSumsq,
-    kPackScale, kCvtPackScale, kCvtPackFbScale, kUnpackScale, kScaleInPlace, kCvtUnpackScale, kUnpackStatScale,
-    kCvtUnpackStatScale
-};
-struct SegOpInfo {
-    const char *label;  // of the happens-before trace
-    bool gather;        // segments read, flat buffer written; else the segments written
-};
-constexpr SegOpInfo kSegOps[] = {{"pack", true},     {"unpack", false},     {"unpack avg", false}, {"divide", false},
-                                 {"pack cvt", true}, {"pack cvt fb", true}, {"unpack cvt", false}, {"unpack cvt avg", false},
-                                 {"unpack sumsq", false}, {"unpack cvt sumsq", false}, {"sumsq", true},
-                                 {"pack scale", true}, {"pack cvt scale", true}, {"pack cvt fb scale", true},
-                                 {"unpack scale", false}, {"scale", false}, {"unpack cvt scale", false},
-                                 {"unpack scale sumsq", false}, {"unpack cvt scale sumsq", false}};
+// fp32 tensors: every segment whole elements (`unit` bytes each in `bytes`: 4, or 2 for wire-side
+// lengths) at a 4-byte aligned address. Null tables are run_'s to report.
+void require_f32_segments(void *const *segs, const size_t *bytes, int count, size_t unit) {
+    for (int i = 0; i < count && segs && bytes; ++i)
+        DDL_REQUIRE(bytes[i] % unit == 0 && reinterpret_cast<uintptr_t>(segs[i]) % 4 == 0, DDL_STATUS_INVALID_ARGUMENT,
+                    "segment " << i << " is not whole, aligned float32 elements");
+}
 
 }  // namespace
 
@@ -803,9 +700,7 @@ void SegmentCopier::run_cvt(int dir, void *flat, void *const *segs, const size_t
                 "wire dtype " << wire_dtype << " is neither float16 nor bfloat16");
     DDL_REQUIRE(dir == 0 || dir == 1 || dir == kSumsqInPlace, DDL_STATUS_INVALID_ARGUMENT, "copier direction " << dir);
     DDL_REQUIRE(divisor >= 1, DDL_STATUS_INVALID_ARGUMENT, "divisor " << divisor);
-    for (int i = 0; i < count && segs && wire_bytes; ++i)
-        DDL_REQUIRE(wire_bytes[i] % 2 == 0 && reinterpret_cast<uintptr_t>(segs[i]) % 4 == 0, DDL_STATUS_INVALID_ARGUMENT,
-                    "segment " << i << " is not whole, aligned float32 elements");
+    require_f32_segments(segs, wire_bytes, count, 2);
     // error feedback only where some non-empty segment of a pack has a residual: every other launch
     // is the plain converting copy, its kernel and tables exactly as before
     bool fb = false;
@@ -841,10 +736,7 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
     if (sc) {
         DDL_REQUIRE(dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
                     "scale factors are defined for float32 tensors, not " << dtype_name(dtype));
-        const size_t unit = wire ? 2 : 4;
-        for (int i = 0; i < count; ++i)
-            DDL_REQUIRE(bytes[i] % unit == 0 && reinterpret_cast<uintptr_t>(segs[i]) % 4 == 0, DDL_STATUS_INVALID_ARGUMENT,
-                        "segment " << i << " is not whole, aligned float32 elements");
+        require_f32_segments(segs, bytes, count, wire ? 2 : 4);
     }
     // the statistic only where some non-empty segment of a scatter asks for it: every other launch
     // is the kernel it was, its tables exactly as before
@@ -863,10 +755,7 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
     if (stat) {
         DDL_REQUIRE(dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
                     "the sum of squares is defined for float32 tensors, not " << dtype_name(dtype));
-        const size_t unit = wire ? 2 : 4;
-        for (int i = 0; i < count; ++i)
-            DDL_REQUIRE(bytes[i] % unit == 0 && reinterpret_cast<uintptr_t>(segs[i]) % 4 == 0, DDL_STATUS_INVALID_ARGUMENT,
-                        "segment " << i << " is not whole, aligned float32 elements");
+        require_f32_segments(segs, bytes, count, wire ? 2 : 4);
     }
     // the quotient only where some segment asks for it and it is not the identity: every other
     // launch is the plain copy, its kernels and tables exactly as before
@@ -882,43 +771,26 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
         DDL_REQUIRE(dir == 0 || dir == 1, DDL_STATUS_INVALID_ARGUMENT, "copier direction " << dir);
         DDL_REQUIRE(!div || dir == 1, DDL_STATUS_INVALID_ARGUMENT, "the quotient belongs to the unpack");
     }
-    DDL_REQUIRE((flat || dir == kDivInPlace || dir == kSumsqInPlace) && segs && bytes, DDL_STATUS_INVALID_ARGUMENT,
-                "null pack arguments");
-    const SegOp op = sc ? (dir == kDivInPlace ? kScaleInPlace
-                           : stat ? (wire ? kCvtUnpackStatScale : kUnpackStatScale)
-                           : wire ? (dir == 0 ? (residuals ? kCvtPackFbScale : kCvtPackScale) : kCvtUnpackScale)
-                           : dir == 0 ? kPackScale : kUnpackScale)
-                     : dir == kDivInPlace ? kDivide
-                     : dir == kSumsqInPlace ? kSumsq
-                     : stat ? (wire ? kCvtUnpackStat : kUnpackStat)
-                     : wire ? (dir == 0 ? (residuals ? kCvtPackFb : kCvtPack) : div ? kCvtUnpackAvg : kCvtUnpack)
-                     : dir == 0 ? kPack : div ? kUnpackAvg : kUnpack;
+    const bool in_place = dir == kDivInPlace || dir == kSumsqInPlace, fbk = wire && dir == 0 && residuals;
+    DDL_REQUIRE((flat || in_place) && segs && bytes, DDL_STATUS_INVALID_ARGUMENT, "null pack arguments");
     const size_t es = div ? dtype_size(dtype) : 1;
-    if (op == kUnpackAvg || op == kDivide) {
+    if (div && !sc && !stat && !wire) {  // DivOp over `dtype`
         DDL_REQUIRE(dtype == DDL_FLOAT || dtype == DDL_DOUBLE || dtype == DDL_HALF || dtype == DDL_BFLOAT16,
                     DDL_STATUS_UNSUPPORTED_DTYPE, "AVG is not defined for dtype " << dtype);
         for (int i = 0; i < count; ++i)
             DDL_REQUIRE(bytes[i] % es == 0 && reinterpret_cast<uintptr_t>(segs[i]) % es == 0, DDL_STATUS_INVALID_ARGUMENT,
                         "segment " << i << " is not whole, aligned " << dtype_name(dtype) << " elements");
     }
-    // in place only the AVG segments have tiles (a SUM segment already is its result)
+    // in place only the segments the launch works on have tiles: the wanted ones of the sum of squares
+    // (nothing else is read), else the AVG and the scaled ones (a SUM segment already is its result)
     std::vector<size_t> own;
-    if (op == kDivide) {
+    if (in_place) {
         own.assign(bytes, bytes + count);
-        for (int i = 0; i < count; ++i)
-            if (ops[i] != DDL_ALLREDUCE_OP_AVG) own[i] = 0;
-        bytes = own.data();
-    }
-    if (op == kScaleInPlace) {  // in place only the AVG and the scaled segments have tiles
-        own.assign(bytes, bytes + count);
-        for (int i = 0; i < count; ++i)
-            if (!(div && ops[i] == DDL_ALLREDUCE_OP_AVG) && scale[i] == 1.0f) own[i] = 0;
-        bytes = own.data();
-    }
-    if (op == kSumsq) {  // in place only the wanted segments have tiles (nothing else is read)
-        own.assign(bytes, bytes + count);
-        for (int i = 0; i < count; ++i)
-            if (!want[i]) own[i] = 0;
+        for (int i = 0; i < count; ++i) {
+            const bool work = dir == kSumsqInPlace ? want[i] != 0
+                                                   : (div && ops[i] == DDL_ALLREDUCE_OP_AVG) || (sc && scale[i] != 1.0f);
+            if (!work) own[i] = 0;
+        }
         bytes = own.data();
     }
     Slot &sl = free_slot_();
@@ -931,7 +803,6 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
     const size_t table = (size_t)count * sizeof(SegDesc);
     // descriptors, then the block bases, then (feedback pack) one residual address per segment, then
     // (scaled launch) one factor per segment
-    const bool fbk = op == kCvtPackFb || op == kCvtPackFbScale;
     const size_t rtab = (table + nblk * sizeof(uint32_t) + 7) & ~size_t(7);
     const size_t stab = fbk ? rtab + (size_t)count * sizeof(uint64_t) : table + nblk * sizeof(uint32_t);
     const size_t need = sc ? stab + (size_t)count * sizeof(float) : stab;
@@ -991,7 +862,6 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
         const dim3 ig((unsigned)((tiles + 255) / 256)), g((unsigned)tiles);
         if (narrow) hipLaunchKernelGGL(k_tile_index<true>, ig, dim3(256), 0, stream, dd, count, (uint64_t)tiles, db, sl.idx);
         else hipLaunchKernelGGL(k_tile_index<false>, ig, dim3(256), 0, stream, dd, count, (uint64_t)tiles, db, sl.idx);
-        const bool f16 = wire == DDL_HALF;  // of the converting copies: else bf16 (run_cvt)
         // the statistic's scratch: one partial per tile, the group values, then one result per segment
         double *partials = nullptr;
         uint64_t fin_groups = 0;  // of the longest wanted segment
@@ -1013,66 +883,52 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
         }
         const uint64_t *res = reinterpret_cast<const uint64_t *>(static_cast<char *>(sl.dev) + rtab);  // (fbk)
         const float *scl = reinterpret_cast<const float *>(static_cast<char *>(sl.dev) + stab);        // (sc)
-        switch (op) {
-            case kPack: launch<CopyOp<0>>(narrow, g, stream, fl, dd, db, sl.idx); break;
-            case kUnpack: launch<CopyOp<1>>(narrow, g, stream, fl, dd, db, sl.idx); break;
-            case kUnpackAvg:
-            case kDivide: {
+        // The instance, from the launch's facts. SCALE: the scaled twin of the same Op, the factor table
+        // behind its other arguments; an unscaled launch passes no table.
+        with_bool(sc, [&](auto scaled) {
+            constexpr bool SCALE = decltype(scaled)::value;
+            const auto go = [&](auto launcher, auto... a) {
+                if constexpr (SCALE) launcher(a..., scl);
+                else launcher(a...);
+            };
+            const auto seg = [&](auto op, auto... a) {  // k_seg<Op>; op: a null pointer of the Op's type
+                using Op = std::remove_pointer_t<decltype(op)>;
+                go([&](auto... x) { launch<Op>(narrow, g, stream, fl, dd, db, sl.idx, x...); }, a...);
+            };
+            const auto sumsq = [&](auto w) {  // k_seg_sumsq: fp32 flat (-1), wire flat, in place
+                constexpr int W = decltype(w)::value;
+                go([&](auto... x) {
+                    launch_sumsq<W, SCALE>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor, partials, x...);
+                });
+            };
+            if (stat) {
+                if (wire) with_wire(wire, sumsq);
+                else sumsq(std::integral_constant<int, -1>{});
+            } else if (wire) {
+                with_wire(wire, [&](auto w) {
+                    constexpr int W = decltype(w)::value;
+                    if (dir != 0) seg((CvtUnpackOp<W, SCALE> *)nullptr, (float)divisor);  // AVG or not: kSegAvg
+                    else if (fbk) seg((CvtPackOp<W, true, SCALE> *)nullptr, res);
+                    else seg((CvtPackOp<W, false, SCALE> *)nullptr);
+                });
+            } else if constexpr (SCALE) {  // fp32 (checked above); the scatter also in place
+                if (dir == 0) seg((ScaleGatherOp *)nullptr);
+                else seg((DivOp<kDivF32, true> *)nullptr, (double)divisor);
+            } else if (dir == 0) {
+                seg((CopyOp<0> *)nullptr);
+            } else if (!div) {
+                seg((CopyOp<1> *)nullptr);
+            } else {
                 const double dv = (double)divisor;
                 switch (dtype) {
-                    case DDL_FLOAT: launch<DivOp<kDivF32>>(narrow, g, stream, fl, dd, db, sl.idx, dv); break;
-                    case DDL_DOUBLE: launch<DivOp<kDivF64>>(narrow, g, stream, fl, dd, db, sl.idx, dv); break;
-                    case DDL_HALF: launch<DivOp<kDivF16>>(narrow, g, stream, fl, dd, db, sl.idx, dv); break;
-                    case DDL_BFLOAT16: launch<DivOp<kDivBF16>>(narrow, g, stream, fl, dd, db, sl.idx, dv); break;
+                    case DDL_FLOAT: seg((DivOp<kDivF32> *)nullptr, dv); break;
+                    case DDL_DOUBLE: seg((DivOp<kDivF64> *)nullptr, dv); break;
+                    case DDL_HALF: seg((DivOp<kDivF16> *)nullptr, dv); break;
+                    case DDL_BFLOAT16: seg((DivOp<kDivBF16> *)nullptr, dv); break;
                     default: fail(DDL_STATUS_UNSUPPORTED_DTYPE, std::string("AVG is not defined for ") + dtype_name(dtype));
                 }
-                break;
             }
-            case kCvtPack:
-                if (f16) launch<CvtPackOp<kWireF16, false>>(narrow, g, stream, fl, dd, db, sl.idx);
-                else launch<CvtPackOp<kWireBF16, false>>(narrow, g, stream, fl, dd, db, sl.idx);
-                break;
-            case kCvtPackFb: {
-                if (f16) launch<CvtPackOp<kWireF16, true>>(narrow, g, stream, fl, dd, db, sl.idx, res);
-                else launch<CvtPackOp<kWireBF16, true>>(narrow, g, stream, fl, dd, db, sl.idx, res);
-                break;
-            }
-            case kCvtUnpack:
-            case kCvtUnpackAvg:
-                if (f16) launch<CvtUnpackOp<kWireF16>>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor);
-                else launch<CvtUnpackOp<kWireBF16>>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor);
-                break;
-            case kUnpackStat:
-            case kCvtUnpackStat:
-            case kSumsq:
-                if (!wire) launch_sumsq<-1>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor, partials);
-                else if (f16) launch_sumsq<kWireF16>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor, partials);
-                else launch_sumsq<kWireBF16>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor, partials);
-                break;
-            case kPackScale: launch<ScaleGatherOp>(narrow, g, stream, fl, dd, db, sl.idx, scl); break;
-            case kCvtPackScale:
-                if (f16) launch<ScaleCvtPackOp<kWireF16, false>>(narrow, g, stream, fl, dd, db, sl.idx, scl);
-                else launch<ScaleCvtPackOp<kWireBF16, false>>(narrow, g, stream, fl, dd, db, sl.idx, scl);
-                break;
-            case kCvtPackFbScale:
-                if (f16) launch<ScaleCvtPackOp<kWireF16, true>>(narrow, g, stream, fl, dd, db, sl.idx, res, scl);
-                else launch<ScaleCvtPackOp<kWireBF16, true>>(narrow, g, stream, fl, dd, db, sl.idx, res, scl);
-                break;
-            case kUnpackScale:
-            case kScaleInPlace:
-                launch<ScaleScatterOp>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor, scl);
-                break;
-            case kCvtUnpackScale:
-                if (f16) launch<ScaleCvtUnpackOp<kWireF16>>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor, scl);
-                else launch<ScaleCvtUnpackOp<kWireBF16>>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor, scl);
-                break;
-            case kUnpackStatScale:
-            case kCvtUnpackStatScale:
-                if (!wire) launch_sumsq_scale<-1>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor, partials, scl);
-                else if (f16) launch_sumsq_scale<kWireF16>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor, partials, scl);
-                else launch_sumsq_scale<kWireBF16>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor, partials, scl);
-                break;
-        }
+        });
         if (stat) {  // the segments' values, then to the caller's host memory ahead of whatever it records next
             double *lvl = partials + tiles, *res = lvl + lvl_n;
             hipLaunchKernelGGL(k_sumsq_finish, dim3((unsigned)count, (unsigned)fin_groups), dim3(64), 0, stream, dd, partials,
@@ -1085,8 +941,8 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
     DDL_HIP(hipEventRecord(sl.ready, stream));
     if (dep::on()) {  // happens-before trace (deptrace.h): the segments and the flat buffer
         std::vector<dep::Access> acc;
-        const bool gather = kSegOps[op].gather;
-        if (op != kDivide && op != kSumsq && op != kScaleInPlace) acc.push_back(gather ? dep::wr(flat, off) : dep::rd(flat, off));
+        const bool gather = dir == 0 || dir == kSumsqInPlace;  // segments read (and the flat buffer written)
+        if (!in_place) acc.push_back(gather ? dep::wr(flat, off) : dep::rd(flat, off));
         const size_t widen = wire ? dtype_size(dtype) / dtype_size(wire) : 1;  // the tensor side in its own bytes
         for (int i = 0; i < count; ++i)
             if (bytes[i])
@@ -1096,7 +952,11 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
                 acc.push_back(dep::rd(residuals[i], bytes[i] * widen));
                 acc.push_back(dep::wr(residuals[i], bytes[i] * widen));
             }
-        dep::op(stream, kSegOps[op].label, std::move(acc));
+        const std::string label =
+            in_place ? (dir == kSumsqInPlace ? "sumsq" : sc ? "scale" : "divide")
+                     : std::string(dir == 0 ? "pack" : "unpack") + (wire ? " cvt" : "") + (fbk ? " fb" : "") +
+                           (div && !sc && !stat ? " avg" : "") + (sc ? " scale" : "") + (stat ? " sumsq" : "");
+        dep::op(stream, label, std::move(acc));
     }
 }
 

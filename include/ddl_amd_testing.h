@@ -163,8 +163,8 @@ int ddl_unpack_ops_sumsq(void *const *dsts, const void *src, const size_t *bytes
                          int divisor, void *hip_stream, const unsigned char *want, double *sumsq_out);
 int ddl_unpack_cvt_sumsq(void *const *dsts, const void *src, const size_t *elements, const int *ops, int count,
                          int wire_dtype, int divisor, void *hip_stream, const unsigned char *want, double *sumsq_out);
-/* The scaled copies (ddl_amd.h "Scale factors"; csrc/pack.hip ScaleGatherOp, ScaleCvtPackOp, ScaleScatterOp,
- * ScaleCvtUnpackOp, k_seg_sumsq_scale): fp32 tensors of elements[i] values, scale[i] one fp32 factor per
+/* The scaled copies (ddl_amd.h "Scale factors"; csrc/pack.hip ScaleGatherOp and the SCALE instances of
+ * CvtPackOp, DivOp, CvtUnpackOp and k_seg_sumsq): fp32 tensors of elements[i] values, scale[i] one fp32 factor per
  * segment (finite, > 0; 1.0f = the segment is moved as the unscaled kernel moves it; with every factor of
  * the non-empty segments 1 the launch IS the unscaled kernel's).
  * ddl_pack_scale = ddl_pack (wire_dtype 0, segments of 4 * elements[i] bytes), ddl_pack_cvt (wire_dtype

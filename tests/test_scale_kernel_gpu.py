@@ -1,5 +1,5 @@
-"""The scaled fusion copies (csrc/pack.hip ScaleGatherOp, ScaleCvtPackOp, ScaleScatterOp, ScaleCvtUnpackOp,
-k_seg_sumsq_scale) on their own, through ddl_pack_scale / ddl_unpack_scale.
+"""The scaled fusion copies (csrc/pack.hip: ScaleGatherOp and the SCALE instances of CvtPackOp, DivOp,
+CvtUnpackOp and k_seg_sumsq) on their own, through ddl_pack_scale / ddl_unpack_scale.
 
 A scaled pack must write what the UNSCALED pack writes for inputs multiplied in NumPy; a scaled unpack
 what NumPy makes of the unscaled unpack's output; a segment with factor 1 inside a scaled launch the plain
@@ -24,6 +24,18 @@ WIRES = [0, DT_HALF, DT_BFLOAT16]
 WIRE_IDS = ['fp32', 'fp16', 'bf16']
 P = 3
 THIRD = np.float32(1.0 / 3.0)
+# (element counts, segments on a pointer that is only 4-byte aligned, shift of the factors, segments
+# without a residual in the feedback test). wide_map, as in test_wire_kernel_gpu.py: more than 255 empty
+# segments inside one 128-tile index block, so the int32 tile map (the NARROW = false instances); its
+# shift deals a factor of 1 to one of its four non-empty segments at every shift the tests use.
+WIDE = [3000, 17] + [0] * 300 + [5, 2048]
+GEOMETRIES = {'edges': (LENS, MISALIGNED, 0, {1, 4, 7}), 'wide_map': (WIDE, {1}, 3, {1, 303})}
+
+
+def _cases(wires, ids):
+    """Every wire on every geometry; the 'edges' cases keep the wire alone as their id."""
+    return pytest.mark.parametrize('wire,geo', [(w, g) for g in GEOMETRIES for w in wires],
+                                   ids=[i if g == 'edges' else f'{i}-{g}' for g in GEOMETRIES for i in ids])
 
 
 def _stream():
@@ -152,8 +164,8 @@ def _same_double(a, b):
     return (math.isnan(a) and math.isnan(b)) or struct.pack('<d', a) == struct.pack('<d', b)
 
 
-def _inputs(factors, seed):
-    return [scale_input(n, seed + i, f) for i, (n, f) in enumerate(zip(LENS, factors))]
+def _inputs(factors, seed, lens=LENS):
+    return [scale_input(n, seed + i, f) for i, (n, f) in enumerate(zip(lens, factors))]
 
 
 def _wire_data(xs, wire):
@@ -163,18 +175,19 @@ def _wire_data(xs, wire):
     return [narrow(wire, x).view(np.uint16) for x in xs]
 
 
-@pytest.mark.parametrize('wire', WIRES, ids=WIRE_IDS)
-def test_scaled_packs(lib, gpu, wire):
+@_cases(WIRES, WIRE_IDS)
+def test_scaled_packs(lib, gpu, wire, geo):
     """Every scaled pack's flat buffer is the unscaled pack's of NumPy-premultiplied inputs — the 0x5A
     padding between the segments included — and a factor-1 segment in the launch has the plain bytes."""
+    lens, misaligned, fshift, _ = GEOMETRIES[geo]
     for shift in (0, 1, 3):
-        fs = mixed_factors(len(LENS), shift)
-        assert any(f == 1 for f in fs) and any(f != 1 for f in fs)
-        xs = _inputs(fs, 100 * shift)
-        got, _ = _pack(lib, gpu, xs, wire, fs, misaligned=MISALIGNED)
-        ref, _ = _pack(lib, gpu, [mul(x, f) for x, f in zip(xs, fs)], wire, None, misaligned=MISALIGNED)
+        fs = mixed_factors(len(lens), shift + fshift)
+        assert any(f == 1 and n for f, n in zip(fs, lens)) and any(f != 1 and n for f, n in zip(fs, lens))
+        xs = _inputs(fs, 100 * shift, lens)
+        got, _ = _pack(lib, gpu, xs, wire, fs, misaligned=misaligned)
+        ref, _ = _pack(lib, gpu, [mul(x, f) for x, f in zip(xs, fs)], wire, None, misaligned=misaligned)
         assert same_bits(_flat_values(got, wire), _flat_values(ref, wire)), (wire, shift)
-        plain, _ = _pack(lib, gpu, xs, wire, None, misaligned=MISALIGNED)
+        plain, _ = _pack(lib, gpu, xs, wire, None, misaligned=misaligned)
         off, es = 0, 2 if wire else 4
         for x, f in zip(xs, fs):
             if f == 1:
@@ -197,20 +210,21 @@ def test_all_factors_one_is_the_plain_launch(lib, gpu):
         assert got.tobytes() == ref.tobytes()
 
 
-@pytest.mark.parametrize('wire', [DT_HALF, DT_BFLOAT16], ids=['fp16', 'bf16'])
-def test_feedback_three_steps(lib, gpu, wire):
+@_cases([DT_HALF, DT_BFLOAT16], ['fp16', 'bf16'])
+def test_feedback_three_steps(lib, gpu, wire, geo):
     """Three consecutive steps of the scaled feedback pack: wire values and residual bits are the model's;
     segments without a residual and segments without a factor ride in the same launches."""
-    fs = mixed_factors(len(LENS), 2)
+    lens, misaligned, fshift, no_res = GEOMETRIES[geo]
+    fs = mixed_factors(len(lens), 2 + fshift)
     fs[0] = np.float32(1)  # (a second factor-1 segment, this one with a residual)
-    has_res = [i % 3 != 1 for i in range(len(LENS))]
-    assert {(f == 1, h) for f, h, n in zip(fs, has_res, LENS) if n} == {(True, True), (True, False), (False, True),
+    has_res = [i not in no_res for i in range(len(lens))]
+    assert {(f == 1, h) for f, h, n in zip(fs, has_res, lens) if n} == {(True, True), (True, False), (False, True),
                                                                          (False, False)}
-    res = [np.zeros(n, np.float32) if h else None for n, h in zip(LENS, has_res)]
+    res = [np.zeros(n, np.float32) if h else None for n, h in zip(lens, has_res)]
     model = [None if r is None else r.copy() for r in res]
     for stepno in range(3):
-        xs = _inputs(fs, 1000 + 50 * stepno)
-        got, res = _pack(lib, gpu, xs, wire, fs, residuals=res, misaligned=MISALIGNED)
+        xs = _inputs(fs, 1000 + 50 * stepno, lens)
+        got, res = _pack(lib, gpu, xs, wire, fs, residuals=res, misaligned=misaligned)
         off = 0
         for i, (x, f) in enumerate(zip(xs, fs)):
             if model[i] is None:
@@ -224,31 +238,32 @@ def test_feedback_three_steps(lib, gpu, wire):
     assert any(m is not None and np.any(m != 0) for m in model)
 
 
-@pytest.mark.parametrize('wire', WIRES, ids=WIRE_IDS)
-def test_scaled_unpacks_and_sumsq(lib, gpu, wire):
+@_cases(WIRES, WIRE_IDS)
+def test_scaled_unpacks_and_sumsq(lib, gpu, wire, geo):
     """SUM and AVG segments at P = 3 with mixed factors: the scaled unpack stores NumPy's product of the
     unscaled unpack's output; the sumsq form stores the same bytes and its doubles are mirror(out)."""
+    lens, misaligned, fshift, _ = GEOMETRIES[geo]
     for shift in (0, 2):
-        fs = mixed_factors(len(LENS), shift)
-        ops = [OP_AVG if (i + shift) % 2 else OP_SUM for i in range(len(LENS))]
-        data = _wire_data(_inputs(fs, 300 + shift), wire)
-        ref, offs, _ = _unpack(lib, gpu, data, wire, ops, None, misaligned=MISALIGNED)
-        got, offs2, _ = _unpack(lib, gpu, data, wire, ops, fs, misaligned=MISALIGNED)
+        fs = mixed_factors(len(lens), shift + fshift)
+        ops = [OP_AVG if (i + shift) % 2 else OP_SUM for i in range(len(lens))]
+        data = _wire_data(_inputs(fs, 300 + shift, lens), wire)
+        ref, offs, _ = _unpack(lib, gpu, data, wire, ops, None, misaligned=misaligned)
+        got, offs2, _ = _unpack(lib, gpu, data, wire, ops, fs, misaligned=misaligned)
         assert offs == offs2
-        for i, (r, g, f) in enumerate(zip(_segments(ref, offs, LENS), _segments(got, offs, LENS), fs)):
+        for i, (r, g, f) in enumerate(zip(_segments(ref, offs, lens), _segments(got, offs, lens), fs)):
             assert same_bits(g, mul(r, f)), (wire, shift, i)
             if f == 1:
                 assert g.tobytes() == r.tobytes(), 'a factor-1 segment differs from the plain kernel'
-        want = [0 if i % 3 == 2 else 1 for i in range(len(LENS))]
-        got2, _, sq = _unpack(lib, gpu, data, wire, ops, fs, want=want, misaligned=MISALIGNED)
-        for i, seg in enumerate(_segments(got2, offs, LENS)):
-            assert same_bits(seg, _segments(got, offs, LENS)[i])
+        want = [0 if i % 3 == 2 else 1 for i in range(len(lens))]
+        got2, _, sq = _unpack(lib, gpu, data, wire, ops, fs, want=want, misaligned=misaligned)
+        for i, seg in enumerate(_segments(got2, offs, lens)):
+            assert same_bits(seg, _segments(got, offs, lens)[i])
             m = mirror(seg, bool(wire)) if want[i] else 0.0
             assert _same_double(sq[i], m), (wire, shift, i, sq[i], m)
         # finite data: the doubles are finite and compared as bits
-        clean = _wire_data([np.random.default_rng(i).standard_normal(n).astype(np.float32) for i, n in enumerate(LENS)], wire)
-        out, _, sq = _unpack(lib, gpu, clean, wire, ops, fs, want=[1] * len(LENS), misaligned=MISALIGNED)
-        for i, seg in enumerate(_segments(out, offs, LENS)):
+        clean = _wire_data([np.random.default_rng(i).standard_normal(n).astype(np.float32) for i, n in enumerate(lens)], wire)
+        out, _, sq = _unpack(lib, gpu, clean, wire, ops, fs, want=[1] * len(lens), misaligned=misaligned)
+        for i, seg in enumerate(_segments(out, offs, lens)):
             m = mirror(seg, bool(wire))
             assert math.isfinite(m) and struct.pack('<d', sq[i]) == struct.pack('<d', m), (i, sq[i], m)
 

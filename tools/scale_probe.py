@@ -7,9 +7,11 @@ On bench.py's C5 segment set as fp32 tensors (4096 segments, log-uniform 4 KiB .
 as bench.fusion_c5), every segment with the factor 1/3 (and AVG's divisor 3 where a quotient is taken):
 
   a  plain pack (ddl_pack: k_seg<CopyOp<0>>)              against the scaled gather (ScaleGatherOp)
-  b  dividing unpack, all AVG (ddl_unpack_ops: DivOp)       against the scaled scatter (AVG + factor)
-  c  converting pack / unpack, fp16 and bf16 (CvtPackOp / CvtUnpackOp, all AVG) against their scaled forms
-  d  unpack with sums of squares (k_seg_sumsq, all AVG)      against k_seg_sumsq_scale
+  b  dividing unpack, all AVG (ddl_unpack_ops: DivOp)       against the scaled scatter (DivOp's SCALE instance)
+  c  converting pack / unpack, fp16 and bf16 (CvtPackOp / CvtUnpackOp, all AVG) against their SCALE instances
+  d  unpack with sums of squares (k_seg_sumsq, all AVG)      against its SCALE instance
+  g  feedback pack, fp16 and bf16 (ddl_pack_cvt_fb: CvtPackOp with FB) against the scaled feedback pack
+     (ddl_pack_scale with residuals), every segment with a residual
   e  b's unpack followed by torch._foreach_mul_ over the outputs (the unscale pass the feature removes)
      against the scaled scatter
   f  torch._foreach_mul_ over the inputs followed by the plain pack against the scaled gather
@@ -148,6 +150,14 @@ def main():
             lambda: ck(lib.ddl_unpack_scale(ptrs, flat.data_ptr(), elems, avg, k, wire, P, third, sh, None, None),
                        'ddl_unpack_scale'),
             R, I, total * 3 // 2)
+    # g: the feedback packs, both wires (14 bytes moved per element: the residual is read and written)
+    resid = [torch.zeros(s // 4, device=dev) for s in sizes]
+    rptrs = (ctypes.c_void_p * k)(*[t.data_ptr() for t in resid])
+    for name, wire in (('fp16', cb.DT_HALF), ('bf16', cb.DT_BFLOAT16)):
+        res[f'g_pack_cvt_fb_{name}'] = pair(
+            lambda: ck(lib.ddl_pack_cvt_fb(flat.data_ptr(), ptrs, rptrs, elems, k, wire, sh), 'ddl_pack_cvt_fb'),
+            lambda: ck(lib.ddl_pack_scale(flat.data_ptr(), ptrs, rptrs, elems, k, wire, third, sh), 'ddl_pack_scale'),
+            R, I, total * 7 // 2)
     text = json.dumps(res, indent=1)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
