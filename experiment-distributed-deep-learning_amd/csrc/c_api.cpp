@@ -150,6 +150,7 @@ int ddl_set_config(const char *key, long long value) {
             c.fusion_pipeline_bytes = value;
         } else if (k == "one_rank_shortcut") c.one_rank_shortcut = value ? 1 : 0;
         else if (k == "wire_feedback_epoch") c.wire_feedback_epoch = value;
+        else if (k == "wire_stochastic_seed") c.wire_stochastic_seed = value;
         else if (k == "pipeline_rounds") c.pipeline_rounds = value ? 1 : 0;
         else if (k == "reference_order") c.reference_order = value ? 1 : 0;
         else if (k == "capture_mode") {
@@ -215,6 +216,7 @@ long long ddl_get_config(const char *key) {
     if (k == "fusion_pipeline_bytes") return c.fusion_pipeline_bytes;
     if (k == "one_rank_shortcut") return c.one_rank_shortcut;
     if (k == "wire_feedback_epoch") return c.wire_feedback_epoch;
+    if (k == "wire_stochastic_seed") return c.wire_stochastic_seed;
     if (k == "pipeline_rounds") return c.pipeline_rounds;
     if (k == "reference_order") return c.reference_order;
     if (k == "capture_mode") return c.capture_mode;
@@ -381,7 +383,7 @@ int ddl_allreduce_submit_mem(ddl_communicator_id id, const char *key, const void
         r.dtype = dtype;
         r.host = memory == DDL_MEMORY_HOST;
         take_sumsq(&op, &user, &r.sumsq, &r.prescale, &r.postscale);
-        r.wire = decode_keyed_op(op, dtype, r.host, &r.op, &r.feedback);  // refusals before anything is posted
+        r.wire = decode_keyed_op(op, dtype, r.host, &r.op, &r.feedback, &r.stochastic);  // refusals before anything is posted
         check_sumsq(r.sumsq, dtype, r.op, r.host);
         check_scale(r.prescale, r.postscale, dtype, r.op, r.host);
         r.done = done;
@@ -479,7 +481,7 @@ int ddl_allreduce_submit_batch_mem(ddl_communicator_id id, int count, const char
             int opi = op;
             rs[i].user = users ? users[i] : nullptr;
             take_sumsq(&opi, &rs[i].user, &rs[i].sumsq, &rs[i].prescale, &rs[i].postscale);  // (sumsq entries may be NULL)
-            rs[i].wire = decode_keyed_op(opi, dtypes[i], rs[i].host, &rs[i].op, &rs[i].feedback);
+            rs[i].wire = decode_keyed_op(opi, dtypes[i], rs[i].host, &rs[i].op, &rs[i].feedback, &rs[i].stochastic);
             check_sumsq(rs[i].sumsq, dtypes[i], rs[i].op, rs[i].host);
             check_scale(rs[i].prescale, rs[i].postscale, dtypes[i], rs[i].op, rs[i].host);
             rs[i].done = done;

@@ -584,6 +584,30 @@ int ddl_pack_cvt_fb(void *dst, const void *const *srcs, void *const *residuals, 
     });
 }
 
+int ddl_pack_cvt_sr(void *dst, const void *const *srcs, void *const *residuals, const size_t *elements, int count,
+                    const unsigned char *want, const unsigned long long *streams, const unsigned long long *firsts, const float *scale,
+                    void *hip_stream) {
+    return guarded([&] {
+        DDL_REQUIRE(count >= 0 && (count == 0 || (dst && srcs && elements && want && streams && firsts)),
+                    DDL_STATUS_INVALID_ARGUMENT, "bad pack_cvt_sr args");
+        const std::vector<size_t> b = wire_bytes(elements, count, DDL_BFLOAT16);
+        std::vector<WireStream> st((size_t)count);
+        for (int i = 0; i < count; ++i)
+            if (want[i]) st[(size_t)i] = WireStream{streams[i], firsts[i], 1};
+        std::lock_guard<std::mutex> g(abi_copier_mu());
+        abi_copier().run_cvt(0, dst, const_cast<void *const *>(srcs), b.data(), count, as_stream(hip_stream), DDL_FLOAT,
+                             DDL_BFLOAT16, 1, nullptr, residuals, nullptr, nullptr, scale, st.data());
+    });
+}
+
+int ddl_testing_stochastic_stream(unsigned long long seed, int rank, const char *key, unsigned long long n,
+                                  unsigned long long *S) {
+    return guarded([&] {
+        DDL_REQUIRE(key && S && rank >= 0, DDL_STATUS_INVALID_ARGUMENT, "bad stochastic_stream args");
+        *S = stochastic_stream(seed, (uint64_t)rank, key, std::strlen(key), n);
+    });
+}
+
 int ddl_unpack_cvt(void *const *dsts, const void *src, const size_t *elements, const int *ops, int count,
                    int wire_dtype, int divisor, void *hip_stream) {
     return guarded([&] {
@@ -815,6 +839,43 @@ int ddl_testing_thread_fused_allreduce_scale(int nranks, int count, const void *
             srcs, dsts, b.data(), count, wire_dtype ? wire_dtype : DDL_FLOAT, as_stream(hip_stream), config().ring(),
             (size_t)config().fusion_pipeline_bytes.load(), ops, wire_dtype ? DDL_FLOAT : 0, residuals, want, sumsq_out, &cuts,
             prescale, postscale);
+        if (subplans) *subplans = j;
+        if (ncuts) *ncuts = (int)cuts.size();
+        for (int k = 0; k < max_cuts && k < (int)cuts.size() && cut_segs && cut_elems; ++k) {
+            cut_segs[k] = cuts[k].first;
+            cut_elems[k] = cuts[k].second;
+        }
+    });
+}
+
+int ddl_testing_thread_fused_allreduce_wire_sr(int nranks, int count, const void *const *srcs, void *const *dsts,
+                                               const size_t *elements, const int *ops, const unsigned char *sr_want,
+                                               const unsigned long long *streams, const float *prescale,
+                                               const float *postscale, void *hip_stream, size_t *subplans,
+                                               const unsigned char *want, double *sumsq_out, size_t *cut_segs,
+                                               size_t *cut_elems, int max_cuts, int *ncuts) {
+    return guarded([&] {
+        DDL_REQUIRE(nranks >= 1 && nranks <= 64 && count >= 1 && srcs && dsts && elements && sr_want && streams &&
+                        (!want || sumsq_out),
+                    DDL_STATUS_INVALID_ARGUMENT, "bad thread fused allreduce");
+        for (int i = 0; ops && i < count; ++i) {
+            check_allreduce_op(ops[i], DDL_FLOAT);
+            DDL_REQUIRE(!op_is_minmax(ops[i]), DDL_STATUS_INVALID_ARGUMENT, "MIN / MAX take no wire");
+        }
+        for (int i = 0; i < count; ++i)
+            for (const float *f : {prescale, postscale})
+                DDL_REQUIRE(!f || (std::isfinite(f[i]) && f[i] > 0.0f), DDL_STATUS_INVALID_ARGUMENT,
+                            "scale factors must be finite and positive");
+        const std::vector<size_t> b = wire_bytes(elements, count, DDL_BFLOAT16);
+        std::vector<WireStream> st((size_t)nranks * count);
+        for (int r = 0; r < nranks; ++r)
+            for (int i = 0; i < count; ++i)
+                if (sr_want[i]) st[(size_t)r * count + i] = WireStream{streams[(size_t)r * count + i], 0, 1};
+        std::vector<std::pair<size_t, size_t>> cuts;
+        const size_t j = thread_world(nranks).fused_allreduce(
+            srcs, dsts, b.data(), count, DDL_BFLOAT16, as_stream(hip_stream), config().ring(),
+            (size_t)config().fusion_pipeline_bytes.load(), ops, DDL_FLOAT, nullptr, want, sumsq_out, &cuts, prescale,
+            postscale, st.data());
         if (subplans) *subplans = j;
         if (ncuts) *ncuts = (int)cuts.size();
         for (int k = 0; k < max_cuts && k < (int)cuts.size() && cut_segs && cut_elems; ++k) {

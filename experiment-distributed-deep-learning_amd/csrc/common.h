@@ -92,28 +92,58 @@ inline void check_allreduce_op(int op, int dtype) {
 }
 
 // The `op` of a keyed allreduce request: SUM / AVG / MIN / MAX in the low bits, with SUM / AVG
-// optionally one ddl_allreduce_wire format flag, optionally DDL_ALLREDUCE_WIRE_FEEDBACK with it.
-// Returns the wire dtype (DDL_HALF / DDL_BFLOAT16; 0 = uncompressed), leaves the op in *base and
-// the feedback bit in *feedback. Refusals as ddl_amd.h lists them, before anything is registered.
-inline int decode_keyed_op(int op, int dtype, bool host, int *base, bool *feedback) {
+// optionally one ddl_allreduce_wire format flag, optionally DDL_ALLREDUCE_WIRE_FEEDBACK with it, or
+// DDL_ALLREDUCE_WIRE_STOCHASTIC with WIRE_BF16. Returns the wire dtype (DDL_HALF / DDL_BFLOAT16; 0 =
+// uncompressed), leaves the op in *base, the feedback bit in *feedback and the stochastic bit in
+// *stochastic. Refusals as ddl_amd.h lists them, before anything is registered.
+inline int decode_keyed_op(int op, int dtype, bool host, int *base, bool *feedback, bool *stochastic) {
     constexpr int kWire = DDL_ALLREDUCE_WIRE_FP16 | DDL_ALLREDUCE_WIRE_BF16;
-    *base = op & ~(kWire | DDL_ALLREDUCE_WIRE_FEEDBACK);
+    *base = op & ~(kWire | DDL_ALLREDUCE_WIRE_FEEDBACK | DDL_ALLREDUCE_WIRE_STOCHASTIC);
     *feedback = (op & DDL_ALLREDUCE_WIRE_FEEDBACK) != 0;
+    *stochastic = (op & DDL_ALLREDUCE_WIRE_STOCHASTIC) != 0;
     const int w = op & kWire;
     DDL_REQUIRE(w != kWire, DDL_STATUS_INVALID_ARGUMENT, "both wire flags in allreduce op " << op);
     DDL_REQUIRE(*base == DDL_ALLREDUCE_OP_SUM || *base == DDL_ALLREDUCE_OP_AVG || op_is_minmax(*base),
                 DDL_STATUS_INVALID_ARGUMENT,
                 "unknown allreduce op " << op << " (SUM = 0, AVG = 1, | WIRE_FP16 = 0x100 or WIRE_BF16 = 0x200, "
-                                                 "| WIRE_FEEDBACK = 0x1000 with one of them; MIN = 3, MAX = 4)");
-    DDL_REQUIRE(!op_is_minmax(*base) || (!w && !*feedback), DDL_STATUS_INVALID_ARGUMENT,
+                                                 "| WIRE_FEEDBACK = 0x1000 with one of them, | WIRE_STOCHASTIC = "
+                                                 "0x8000 with WIRE_BF16; MIN = 3, MAX = 4)");
+    DDL_REQUIRE(!op_is_minmax(*base) || (!w && !*feedback && !*stochastic), DDL_STATUS_INVALID_ARGUMENT,
                 "MIN / MAX take no wire flag (allreduce op " << op << ")");
     DDL_REQUIRE(w || !*feedback, DDL_STATUS_INVALID_ARGUMENT,
                 "WIRE_FEEDBACK without WIRE_FP16 or WIRE_BF16 in allreduce op " << op);
+    DDL_REQUIRE(!*stochastic || w == DDL_ALLREDUCE_WIRE_BF16, DDL_STATUS_INVALID_ARGUMENT,
+                "WIRE_STOCHASTIC takes WIRE_BF16 and no other wire flag (allreduce op " << op << ")");
+    DDL_REQUIRE(!*stochastic || !*feedback, DDL_STATUS_INVALID_ARGUMENT,
+                "WIRE_STOCHASTIC and WIRE_FEEDBACK are alternatives (allreduce op " << op << ")");
     if (!w) return 0;
     DDL_REQUIRE(!host, DDL_STATUS_INVALID_ARGUMENT, "wire compression is for device requests only");
     DDL_REQUIRE(dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
                 "wire compression is defined for float32 only, not " << dtype_name(dtype));
     return w == DDL_ALLREDUCE_WIRE_FP16 ? DDL_HALF : DDL_BFLOAT16;
+}
+
+// Stochastic rounding of the bf16 wire (DDL_ALLREDUCE_WIRE_STOCHASTIC; the rule, R and the host mix are
+// fixed in ddl_amd.h and restated in tests/_stochastic_helpers.py). One per segment of a converting pack:
+// the stream key S of the segment's request, the index in that request of the segment's first element
+// (a piece of a cut request does not start at 0) and whether the segment is rounded stochastically at all.
+struct WireStream {
+    uint64_t key = 0;
+    uint64_t first = 0;
+    uint64_t on = 0;
+};
+// mix64: one splitmix64 step (add the golden-ratio increment, then its finaliser).
+inline uint64_t sr_mix64(uint64_t z) {
+    z += 0x9e3779b97f4a7c15ull;
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+// S = mix64(mix64(mix64(mix64(seed) ^ rank) ^ fnv1a64(key bytes)) ^ n)
+inline uint64_t stochastic_stream(uint64_t seed, uint64_t rank, const void *key, size_t len, uint64_t n) {
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (size_t i = 0; i < len; ++i) h = (h ^ static_cast<const unsigned char *>(key)[i]) * 0x100000001b3ull;
+    return sr_mix64(sr_mix64(sr_mix64(sr_mix64(seed) ^ rank) ^ h) ^ n);
 }
 
 // Logging (the reference logs per rank to log-<rank>.txt, GlobalLog.cc:17-49; here
@@ -297,13 +327,18 @@ public:
                  const unsigned char *want = nullptr, double *sumsq = nullptr,
                  // dir 0: the prescale ahead of the narrowing (and of the residual's addition); dir 1: the
                  // postscale behind the widening and the quotient — as in run()
-                 const float *scale = nullptr);
+                 const float *scale = nullptr,
+                 // dir 0, bf16 wire: stochastic rounding (DDL_ALLREDUCE_WIRE_STOCHASTIC) — one WireStream per
+                 // segment; segment i with streams[i].on (and no residual) is narrowed by the rule of ddl_amd.h
+                 // (k_seg<CvtPackSrOp>), every other segment as CvtPackOp<kWireBF16, .> packs it. With no
+                 // stochastic non-empty segment the launch is the converting pack it was, unchanged.
+                 const WireStream *streams = nullptr);
     static size_t flat_bytes(const size_t *bytes, int count);
 
 private:
     void run_(int dir, void *flat, void *const *segs, const size_t *bytes, int count, hipStream_t stream, int dtype,
               int divisor, const int *ops, int wire, void *const *residuals, const unsigned char *want, double *sumsq,
-              const float *scale);
+              const float *scale, const WireStream *streams = nullptr);
     struct Slot {
         void *host = nullptr, *dev = nullptr;
         size_t cap = 0;

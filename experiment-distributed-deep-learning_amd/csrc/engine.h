@@ -104,6 +104,10 @@ struct Config {
     // loading a checkpoint or a large change of the loss scale). Per process, not in shared_hash:
     // the residuals are rank-local and change nothing that is communicated.
     std::atomic<long long> wire_feedback_epoch{0};
+    // stochastic rounding of the bf16 wire (DDL_ALLREDUCE_WIRE_STOCHASTIC): the seed every stream key S
+    // of this process starts from (ddl_amd.h; read as its 64 bits when a request's S is computed). Per
+    // process, not in shared_hash: the random bits are rank-local and change nothing that is communicated.
+    std::atomic<long long> wire_stochastic_seed{0};
     // keyed rounds: 1 — a completion thread waits for a round's data plane and fires its done()
     // calls while the engine thread negotiates and enqueues the next round; 0 — the engine
     // thread waits for each round before negotiating the next (as the reference's recv thread
@@ -151,7 +155,8 @@ struct Config {
     // fusion_threshold_bytes, tune, fusion_pipeline_bytes, reference_order, host_chunk_bytes,
     // rccl_min_ctas, rccl_max_ctas.
     // Never 0 or kCfgMismatch. Local tunables (log_level, cycle_time_us, host_copy_threads,
-    // host_zero_copy, pipeline_rounds, one_rank_shortcut, wire_feedback_epoch) are not in it.
+    // host_zero_copy, pipeline_rounds, one_rank_shortcut, wire_feedback_epoch, wire_stochastic_seed) are not
+    // in it.
     uint64_t shared_hash() const;
     RingConfig ring() const {
         RingConfig c;

@@ -42,7 +42,8 @@ hipEvent_t FusionPipe::event_(size_t i) {
 void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<void *> &dsts,
                      const std::vector<size_t> &bytes, int dt, size_t cap, hipStream_t stream, const Allreduce &ar,
                      const std::vector<int> *ops, int divisor, int src_dt, const std::vector<void *> *residuals,
-                     PlanSumsq *sumsq, const std::vector<float> *prescale, const std::vector<float> *postscale) {
+                     PlanSumsq *sumsq, const std::vector<float> *prescale, const std::vector<float> *postscale,
+                     const std::vector<WireStream> *streams) {
     const size_t es = dtype_size(dt);
     DDL_REQUIRE(es != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported dtype " << dt);
     const bool cvt = src_dt != 0 && src_dt != dt;
@@ -51,11 +52,13 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
     // gather (dir 0) / scatter (dir 1) of one (sub-)plan: the converting kernels with a wire dtype
     // (`res`: the pack's residuals of a plan with error feedback)
     // (`want`, `sq`: the unpack's sums of squares, SegmentCopier::run; `scl`: the pack's prescale
-    // factors, the unpack's postscale factors)
+    // factors, the unpack's postscale factors; `sts`: the pack's stochastic-rounding streams)
     auto copy = [&](int dir, void *fb, void *const *segs, const size_t *b, int n, hipStream_t s, const int *o,
                     void *const *res = nullptr, const unsigned char *want = nullptr, double *sq = nullptr,
-                    const float *scl = nullptr) {
-        if (cvt) copier.run_cvt(dir, fb, segs, b, n, s, src_dt, dt, divisor, o, dir == 0 ? res : nullptr, want, sq, scl);
+                    const float *scl = nullptr, const WireStream *sts = nullptr) {
+        if (cvt)
+            copier.run_cvt(dir, fb, segs, b, n, s, src_dt, dt, divisor, o, dir == 0 ? res : nullptr, want, sq, scl,
+                           dir == 0 ? sts : nullptr);
         else if (dir == 0) copier.run(0, fb, segs, b, n, s, dt, 1, nullptr, nullptr, nullptr, scl);
         else copier.run(1, fb, segs, b, n, s, dt, divisor, o, want, sq, scl);
     };
@@ -68,6 +71,8 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
     DDL_REQUIRE(!ops || ops->size() == bytes.size(), DDL_STATUS_INVALID_ARGUMENT, "fusion plan: one op per segment");
     DDL_REQUIRE(!residuals || (cvt && residuals->size() == bytes.size()), DDL_STATUS_INVALID_ARGUMENT,
                 "fusion plan: one residual per segment of a compressed plan");
+    DDL_REQUIRE(!streams || (cvt && streams->size() == bytes.size()), DDL_STATUS_INVALID_ARGUMENT,
+                "fusion plan: one stochastic-rounding stream per segment of a compressed plan");
     DDL_REQUIRE(srcs.size() == bytes.size() && dsts.size() == bytes.size(), DDL_STATUS_INVALID_ARGUMENT,
                 "fusion plan: " << srcs.size() << " sources, " << dsts.size() << " destinations, " << bytes.size()
                                 << " sizes");
@@ -82,7 +87,7 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
         void *fb = ensure(0, total, stream);
         copy(0, fb, const_cast<void *const *>(reinterpret_cast<const void *const *>(srcs.data())), bytes.data(),
              (int)srcs.size(), stream, nullptr, residuals ? residuals->data() : nullptr, nullptr, nullptr,
-             prescale ? prescale->data() : nullptr);
+             prescale ? prescale->data() : nullptr, streams ? streams->data() : nullptr);
         ar(fb, total / es, message);
         double *sq = stat ? sumsq->pinned(bytes.size()) : nullptr;
         copy(1, fb, dsts.data(), bytes.data(), (int)dsts.size(), stream, ops ? ops->data() : nullptr, nullptr,
@@ -101,6 +106,7 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
         std::vector<size_t> seg, elem;    //   and the piece's segment and first element in it
         bool stat = false;
         std::vector<float> pre, post;  // of each piece: its segment's factors (only with `prescale` / `postscale`)
+        std::vector<WireStream> sts;   // of each piece: its segment's stream from the piece's first element (only with `streams`)
         size_t flat = 0;
     };
     std::vector<Sub> subs(1);
@@ -123,6 +129,8 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
             // the residual is indexed like the tensor: the same fp32 element offset at a cut
             if (residuals)
                 cur->res.push_back((*residuals)[i] ? static_cast<char *>((*residuals)[i]) + off / es * ses : nullptr);
+            // the random bits are indexed like the tensor: the piece starts at its element offset in the request
+            if (streams) cur->sts.push_back(WireStream{(*streams)[i].key, (*streams)[i].first + off / es, (*streams)[i].on});
             if (prescale) cur->pre.push_back((*prescale)[i]);
             if (postscale) cur->post.push_back((*postscale)[i]);
             if (stat) {
@@ -162,7 +170,7 @@ void FusionPipe::run(const std::vector<const void *> &srcs, const std::vector<vo
         Sub &sb = subs[j];
         copy(0, buf[j % 2], const_cast<void *const *>(reinterpret_cast<const void *const *>(sb.src.data())),
              sb.bytes.data(), (int)sb.src.size(), side_, nullptr, residuals ? sb.res.data() : nullptr, nullptr, nullptr,
-             prescale ? sb.pre.data() : nullptr);
+             prescale ? sb.pre.data() : nullptr, streams ? sb.sts.data() : nullptr);
         DDL_HIP(hipEventRecord(events_[1 + 2 * j], side_));
         dep::record(events_[1 + 2 * j], side_);
         DDL_HIP(hipStreamWaitEvent(stream, events_[1 + 2 * j], 0));

@@ -81,7 +81,13 @@ public:
              // piece of a segment is packed with the segment's prescale and unpacked with its postscale
              // (SegmentCopier::run: a launch without a factor other than 1 is the kernel it was); cuts and
              // allreduces do not depend on them
-             const std::vector<float> *prescale = nullptr, const std::vector<float> *postscale = nullptr);
+             const std::vector<float> *prescale = nullptr, const std::vector<float> *postscale = nullptr,
+             // stochastic rounding (DDL_ALLREDUCE_WIRE_STOCHASTIC; a compressed bf16 plan), one
+             // WireStream per segment, null = none: `first` is the index in its request of the segment's first
+             // element, and a sub-plan's piece starts where it is cut, so every element keeps the random bits of
+             // its index in the request whatever the cuts; a launch without a stochastic segment is the pack it
+             // was; cuts, allreduces and unpacks do not depend on them
+             const std::vector<WireStream> *streams = nullptr);
     size_t subplans() const { return last_subplans_; }  // of the last run
 
     SegmentCopier copier;

@@ -127,6 +127,8 @@ void validate(const Request &r, int size) {
             DDL_REQUIRE(r.wire == 0 || (r.dtype == DDL_FLOAT && !r.host && (r.wire == DDL_HALF || r.wire == DDL_BFLOAT16)),
                         DDL_STATUS_INVALID_ARGUMENT, "wire dtype " << r.wire << " on a " << dtype_name(r.dtype) << " request");
             DDL_REQUIRE(!r.feedback || r.wire != 0, DDL_STATUS_INVALID_ARGUMENT, "error feedback without a wire dtype");
+            DDL_REQUIRE(!r.stochastic || (r.wire == DDL_BFLOAT16 && !r.feedback), DDL_STATUS_INVALID_ARGUMENT,
+                        "stochastic rounding takes the bfloat16 wire and no error feedback");
             DDL_REQUIRE(r.n == 0 || (r.in && r.out), DDL_STATUS_INVALID_ARGUMENT, "null buffer");
             DDL_REQUIRE(!r.sumsq || r.dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
                         "the sum of squares is defined for float32 requests, not " << dtype_name(r.dtype));
@@ -511,6 +513,12 @@ void *RequestHandler::residual_(const Request &r) {
     return res.ptr;
 }
 
+uint64_t RequestHandler::stochastic_stream_(const Request &r) {
+    const uint64_t n = stochastic_seq_[r.key]++;
+    return stochastic_stream((uint64_t)config().wire_stochastic_seed.load(), (uint64_t)data_->rank(), r.key.data(),
+                             r.key.size(), n);
+}
+
 double *RequestHandler::stat_take_(size_t n) {
     if (round_stat_blocks_.empty() || round_stat_blocks_.back().cap - round_stat_blocks_.back().used < n) {
         StatBlock b;
@@ -622,6 +630,19 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
                     if (reqs[g.second[q]].feedback) resid[q] = residual_(reqs[g.second[q]]);
             }
         }
+        // stochastic rounding (Request::stochastic, rank-local too): the stream key of every request of a
+        // compressed group that asks for it, once per round, so all plans and pieces of a request share it;
+        // none (and no sequence number spent) where the one-rank shortcut skips the data plane
+        std::vector<WireStream> stoch;
+        if (comp && !(data_->size() == 1 && config().one_rank_shortcut.load())) {
+            bool any = false;
+            for (size_t i : g.second) any = any || reqs[i].stochastic;
+            if (any) {
+                stoch.assign(g.second.size(), WireStream{});
+                for (size_t q = 0; q < g.second.size(); ++q)
+                    if (reqs[g.second[q]].stochastic) stoch[q] = WireStream{stochastic_stream_(reqs[g.second[q]]), 0, 1};
+            }
+        }
         for (const Plan &p : make_plans(elems, esz, (size_t)config().fusion_threshold_bytes.load())) {
             for (size_t q = p.req_begin; q <= p.req_end; ++q) wait_inputs_(reqs[g.second[q]], waited);
             if (host) {
@@ -712,6 +733,14 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
                 for (size_t q = p.req_begin; q <= p.req_end && !resid.empty(); ++q)
                     res.push_back(resid[q] ? static_cast<char *>(resid[q]) + (q == p.req_begin ? p.elem_begin : 0) * ses
                                            : nullptr);
+                // the plan's slices of the stochastic streams: the same S, the slice's first element index.
+                // A plan that fails has already spent its requests' sequence numbers: that is not undone.
+                std::vector<WireStream> sts;
+                bool any_sts = false;
+                for (size_t q = p.req_begin; q <= p.req_end && !stoch.empty(); ++q) {
+                    sts.push_back(WireStream{stoch[q].key, q == p.req_begin ? p.elem_begin : 0, stoch[q].on});
+                    any_sts = any_sts || stoch[q].on;
+                }
                 // the sums of squares (Request::sumsq, rank-local like the op): taken by the unpack
                 std::vector<unsigned char> want;
                 PlanSumsq ps;
@@ -735,7 +764,7 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
                             data_->allreduce(buf, buf, elems, dt, kind, stream_, message);
                         },
                         &ops, data_->size(), sdt, resid.empty() ? nullptr : &res, stat ? &ps : nullptr,
-                        any_pre ? &pre : nullptr, any_post ? &post : nullptr);
+                        any_pre ? &pre : nullptr, any_post ? &post : nullptr, any_sts ? &sts : nullptr);
                 for (const PlanSumsq::Piece &pc : ps.pieces) round_stat_.emplace_back(g.second[p.req_begin + pc.seg], pc.value);
             }
             finish_plan_(p, reqs, g.second, dones, nplans);

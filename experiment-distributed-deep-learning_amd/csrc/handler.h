@@ -57,6 +57,7 @@ struct Request {
     int op = 0;                       // allreduce: SUM / AVG / MIN / MAX (the wire flag decoded into `wire`)
     int wire = 0;                     // allreduce: wire dtype of a compressed fp32 request (0: its own dtype)
     bool feedback = false;            // allreduce: DDL_ALLREDUCE_WIRE_FEEDBACK (only with `wire`; rank-local)
+    bool stochastic = false;          // allreduce: DDL_ALLREDUCE_WIRE_STOCHASTIC (only with the bf16 `wire`; rank-local)
     double *sumsq = nullptr;          // allreduce: where the sum of squares of `out` goes before done() (host; rank-local)
     // allreduce: DDL_ALLREDUCE_SCALE's factors (1 = absent; fp32 device SUM / AVG requests). Rank-local like
     // the op and `sumsq`: in no group key, plan cut, pipeline cut or negotiation.
@@ -195,6 +196,13 @@ private:
     // the residual of request r for a pack posted on stream_: made, or restarted from zero (another
     // element count, another epoch), by work posted on stream_ ahead of that pack
     void *residual_(const Request &r);
+    // Stochastic rounding (DDL_ALLREDUCE_WIRE_STOCHASTIC): a key's sequence number n — how many requests of
+    // the key with the bit this handler has packed before — one of the four things a request's stream key S
+    // is mixed from (ddl_amd.h). One entry per key that ever carried the bit, kept until the handler goes.
+    // Touched by the engine thread only.
+    std::unordered_map<std::string, uint64_t> stochastic_seq_;
+    // the stream key of request r's next pack; advances the key's sequence number
+    uint64_t stochastic_stream_(const Request &r);
     // host-resident requests: made once stream_ exists, destroyed (both threads joined) before it
     std::unique_ptr<HostStager> host_;
     void *gather_ = nullptr;  // allgather receive side

@@ -399,6 +399,132 @@ template <int WIRE, bool FB, bool SCALE = false> struct CvtPackOp {
     }
 };
 
+// ---- the converting pack with stochastic rounding (DDL_ALLREDUCE_WIRE_STOCHASTIC) -----------------
+// CvtPackSrOp: the bf16 converting pack plus one table of WireStream, st[seg]. A segment whose entry is
+// not `on` is converted as CvtPackOp<kWireBF16, false> converts it. Per element i of a stochastic
+// segment's REQUEST (i = st[seg].first + the element's index in the segment), with u the bits of c:
+//     c NaN or inf:  w = narrow(c)                       round to nearest even, as the plain pack
+//     otherwise:     w = (u + R(S, i)) >> 16             R: 16 bits, below
+// The sign never changes, +-0 stays +-0, subnormals need no case of their own, and a finite c above the
+// largest bf16 value carries into inf with the probability its low half gives. Integer arithmetic only.
+// R(S, i): one 32-bit word per element pair j = i >> 1,
+//     x = fmix32(lo32(j) ^ lo32(S));  x = fmix32(x + hi32(S) + hi32(j) * 0x9e3779b9)
+// (fmix32: MurmurHash3's finaliser), element i taking bits 16 (i & 1) .. + 15. Four 32-bit multiplies per
+// word, two per element: the vector path computes the lane's 4 words (5 where the piece starts at an odd
+// index of its request — uniform over the segment), 16-20 multiplies for 48 bytes moved, against the
+// ~10 B/clk/CU the HBM-bound stream sustains. hi32(j) * 0x9e3779b9 is one multiply per lane: the words
+// behind a carry of lo32(j) take that product plus the constant. Same loads and stores as the plain
+// pack: two 16-byte non-temporal loads, one 16-byte non-temporal store; 6 bytes per element.
+__device__ inline uint32_t fmix32(uint32_t x) {
+    x ^= x >> 16;
+    x *= 0x85ebca6bu;
+    x ^= x >> 13;
+    x *= 0xc2b2ae35u;
+    x ^= x >> 16;
+    return x;
+}
+constexpr uint32_t kSrGolden = 0x9e3779b9u;
+// the word of pair j: lo = lo32(j), c = hi32(S) + hi32(j) * kSrGolden
+__device__ inline uint32_t sr_word(uint32_t s_lo, uint32_t lo, uint32_t c) { return fmix32(fmix32(lo ^ s_lo) + c); }
+__device__ inline uint16_t sr_narrow(float c, uint32_t r16) {
+    const uint32_t u = __float_as_uint(c);
+    if ((u & 0x7f800000u) == 0x7f800000u) return __builtin_bit_cast(uint16_t, (__bf16)c);
+    return (uint16_t)((u + r16) >> 16);
+}
+
+// FB: the launch also holds error-feedback segments (a plan may mix requests of both kinds; a segment is
+// never both): the residual table ahead of the streams, a segment with a residual packed as
+// CvtPackOp<kWireBF16, true> packs it.
+template <bool SCALE = false, bool FB = false> struct CvtPackSrOp {
+    using Tr = WireTraits<kWireBF16>;
+    using T = typename Tr::T;
+    static constexpr uint32_t kUnit = sizeof(T);
+    T *fl;
+    const float *tp;
+    float *rs = nullptr;
+    bool v, on;
+    uint64_t S, first;
+    Factor<SCALE> fac;
+    template <class... A>
+    __device__ CvtPackSrOp(char *flat, const SegDesc &sd, int seg, A... a)
+        : fl(reinterpret_cast<T *>(flat + sd.off)), tp(reinterpret_cast<const float *>(sd.ptr)),
+          v((sd.vec & kSegVec) != 0), fac(sd, seg, a...) {
+        const WireStream st = arg_of<const WireStream *>(a...)[seg];
+        on = st.on != 0;
+        S = st.key;
+        first = st.first;
+        if constexpr (FB) {  // tensor or residual only 4-byte aligned: elements
+            const uint64_t r = arg_of<const uint64_t *>(a...)[seg];
+            rs = reinterpret_cast<float *>(r);
+            v = v && (r & 15u) == 0;
+            on = on && !rs;
+        }
+    }
+    __device__ bool vector() const { return v; }
+    __device__ void vec(uint64_t b) const {
+        const u32x4 *src = reinterpret_cast<const u32x4 *>(tp + b / sizeof(T));
+        F32x4 lo, hi;
+        lo.v = __builtin_nontemporal_load(src);
+        hi.v = __builtin_nontemporal_load(src + 1);
+        fac(lo.e);
+        fac(hi.e);
+        union {
+            u32x4 v;
+            uint16_t e[8];
+        } o;
+        if (FB && rs) {
+            u32x4 *rv = reinterpret_cast<u32x4 *>(rs + b / sizeof(T));
+            F32x4 rlo, rhi;
+            rlo.v = rv[0];
+            rhi.v = rv[1];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                o.e[k] = __builtin_bit_cast(uint16_t, feedback<kWireBF16>(lo.e[k], rlo.e[k]));
+                o.e[4 + k] = __builtin_bit_cast(uint16_t, feedback<kWireBF16>(hi.e[k], rhi.e[k]));
+            }
+            __builtin_nontemporal_store(rlo.v, rv);
+            __builtin_nontemporal_store(rhi.v, rv + 1);
+        } else if (on) {
+            const uint64_t i0 = first + b / sizeof(T), j0 = i0 >> 1;
+            const bool odd = (i0 & 1u) != 0;  // uniform: b / 2 is a multiple of 8
+            const uint32_t s_lo = (uint32_t)S, l0 = (uint32_t)j0;
+            const uint32_t c0 = (uint32_t)(S >> 32) + (uint32_t)(j0 >> 32) * kSrGolden, c1 = c0 + kSrGolden;
+            uint32_t w[5];
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) w[k] = sr_word(s_lo, l0 + k, l0 + k < l0 ? c1 : c0);
+            w[4] = odd ? sr_word(s_lo, l0 + 4, l0 + 4 < l0 ? c1 : c0) : 0u;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                // element k is half (k & 1) of word k / 2, or with an odd start half ((k + 1) & 1) of word (k + 1) / 2
+                const uint32_t even = (w[k >> 1] >> (16 * (k & 1))) & 0xffffu;
+                const uint32_t shifted = (w[(k + 1) >> 1] >> (16 * ((k + 1) & 1))) & 0xffffu;
+                o.e[k] = sr_narrow(k < 4 ? lo.e[k] : hi.e[k - 4], odd ? shifted : even);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                o.e[k] = __builtin_bit_cast(uint16_t, Tr::narrow(lo.e[k]));
+                o.e[4 + k] = __builtin_bit_cast(uint16_t, Tr::narrow(hi.e[k]));
+            }
+        }
+        __builtin_nontemporal_store(o.v, reinterpret_cast<u32x4 *>(reinterpret_cast<char *>(fl) + b));
+    }
+    __device__ void elem(uint64_t e) const {
+        const float c = fac(tp[e]);
+        if (FB && rs) {
+            float r = rs[e];
+            fl[e] = feedback<kWireBF16>(c, r);
+            rs[e] = r;
+        } else if (on) {
+            const uint64_t i = first + e, j = i >> 1;
+            const uint32_t x = sr_word((uint32_t)S, (uint32_t)j, (uint32_t)(S >> 32) + (uint32_t)(j >> 32) * kSrGolden);
+            reinterpret_cast<uint16_t *>(fl)[e] = sr_narrow(c, (x >> (16 * (uint32_t)(i & 1u))) & 0xffffu);
+        } else {
+            fl[e] = Tr::narrow(c);
+        }
+    }
+};
+
 // SCALE: the factor behind the quotient; the factor table behind the divisor.
 template <int WIRE, bool SCALE = false> struct CvtUnpackOp {
     using Tr = WireTraits<WIRE>;
@@ -693,7 +819,8 @@ void SegmentCopier::run(int dir, void *flat, void *const *segs, const size_t *by
 
 void SegmentCopier::run_cvt(int dir, void *flat, void *const *segs, const size_t *wire_bytes, int count,
                             hipStream_t stream, int src_dtype, int wire_dtype, int divisor, const int *ops,
-                            void *const *residuals, const unsigned char *want, double *sumsq, const float *scale) {
+                            void *const *residuals, const unsigned char *want, double *sumsq, const float *scale,
+                            const WireStream *streams) {
     DDL_REQUIRE(src_dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
                 "wire compression is defined for float32 sources, not " << dtype_name(src_dtype));
     DDL_REQUIRE(wire_dtype == DDL_HALF || wire_dtype == DDL_BFLOAT16, DDL_STATUS_UNSUPPORTED_DTYPE,
@@ -710,8 +837,17 @@ void SegmentCopier::run_cvt(int dir, void *flat, void *const *segs, const size_t
                     "residual " << i << " is not aligned float32 elements");
         fb = true;
     }
+    // stochastic rounding only where some non-empty segment of a pack asks for it: every other launch
+    // is the converting pack it was, its kernel and tables exactly as before
+    bool sr = false;
+    for (int i = 0; i < count && streams && wire_bytes && dir == 0; ++i) sr = sr || (streams[i].on && wire_bytes[i]);
+    DDL_REQUIRE(!sr || wire_dtype == DDL_BFLOAT16, DDL_STATUS_INVALID_ARGUMENT,
+                "stochastic rounding is defined for the bfloat16 wire");
+    for (int i = 0; i < count && sr && fb; ++i)
+        DDL_REQUIRE(!(streams[i].on && residuals[i]), DDL_STATUS_INVALID_ARGUMENT,
+                    "segment " << i << " asks for error feedback and stochastic rounding");
     run_(dir, flat, segs, wire_bytes, count, stream, src_dtype, divisor, dir == 1 ? ops : nullptr, wire_dtype,
-         fb ? residuals : nullptr, dir == 0 ? nullptr : want, sumsq, scale);
+         fb ? residuals : nullptr, dir == 0 ? nullptr : want, sumsq, scale, sr ? streams : nullptr);
 }
 
 // wire == 0: the plain copies and the dividing scatter over `bytes` of `dtype`; else the converting
@@ -720,7 +856,7 @@ void SegmentCopier::run_cvt(int dir, void *flat, void *const *segs, const size_t
 // (a pack's prescale, a scatter's or kDivInPlace's postscale)
 void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *bytes, int count, hipStream_t stream,
                          int dtype, int divisor, const int *ops, int wire, void *const *residuals,
-                         const unsigned char *want, double *sumsq, const float *scale) {
+                         const unsigned char *want, double *sumsq, const float *scale, const WireStream *streams) {
     if (count <= 0) return;
     // a scaled kernel only where some non-empty segment has a factor other than 1: every other launch
     // is the kernel it was, its tables exactly as before
@@ -772,6 +908,7 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
         DDL_REQUIRE(!div || dir == 1, DDL_STATUS_INVALID_ARGUMENT, "the quotient belongs to the unpack");
     }
     const bool in_place = dir == kDivInPlace || dir == kSumsqInPlace, fbk = wire && dir == 0 && residuals;
+    const bool srk = wire && dir == 0 && streams;  // (run_cvt: bf16 only)
     DDL_REQUIRE((flat || in_place) && segs && bytes, DDL_STATUS_INVALID_ARGUMENT, "null pack arguments");
     const size_t es = div ? dtype_size(dtype) : 1;
     if (div && !sc && !stat && !wire) {  // DivOp over `dtype`
@@ -801,10 +938,11 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
     DDL_REQUIRE(tiles < (1ull << 31), DDL_STATUS_INVALID_ARGUMENT, "fusion buffer too large");
     const uint64_t nblk = (tiles + kIdxBlock - 1) / kIdxBlock;
     const size_t table = (size_t)count * sizeof(SegDesc);
-    // descriptors, then the block bases, then (feedback pack) one residual address per segment, then
-    // (scaled launch) one factor per segment
+    // descriptors, then the block bases, then (feedback pack) one residual address per segment or
+    // (stochastic pack) one WireStream per segment, then (scaled launch) one factor per segment
     const size_t rtab = (table + nblk * sizeof(uint32_t) + 7) & ~size_t(7);
-    const size_t stab = fbk ? rtab + (size_t)count * sizeof(uint64_t) : table + nblk * sizeof(uint32_t);
+    const size_t wtab = fbk ? rtab + (size_t)count * sizeof(uint64_t) : rtab;
+    const size_t stab = srk ? wtab + (size_t)count * sizeof(WireStream) : fbk ? wtab : table + nblk * sizeof(uint32_t);
     const size_t need = sc ? stab + (size_t)count * sizeof(float) : stab;
     if (need > sl.cap) {  // outgrown tables kept until ddl_finalize: no hipFree on a data path (engine.h)
         retire_host(sl.host);
@@ -835,6 +973,7 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
         uint64_t *rt = reinterpret_cast<uint64_t *>(static_cast<char *>(sl.host) + rtab);
         for (int i = 0; i < count; ++i) rt[i] = bytes[i] ? reinterpret_cast<uint64_t>(residuals[i]) : 0;
     }
+    if (srk) std::memcpy(static_cast<char *>(sl.host) + wtab, streams, (size_t)count * sizeof(WireStream));
     if (sc) std::memcpy(static_cast<char *>(sl.host) + stab, scale, (size_t)count * sizeof(float));
     // block b's base: the segment of tile b * 128 (the last one with tile0 <= it, as
     // k_tile_index resolves); narrow when no block spans more than 255 segments
@@ -882,6 +1021,7 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
             partials = static_cast<double *>(sl.stat);
         }
         const uint64_t *res = reinterpret_cast<const uint64_t *>(static_cast<char *>(sl.dev) + rtab);  // (fbk)
+        const WireStream *sts = reinterpret_cast<const WireStream *>(static_cast<char *>(sl.dev) + wtab);  // (srk)
         const float *scl = reinterpret_cast<const float *>(static_cast<char *>(sl.dev) + stab);        // (sc)
         // The instance, from the launch's facts. SCALE: the scaled twin of the same Op, the factor table
         // behind its other arguments; an unscaled launch passes no table.
@@ -908,6 +1048,8 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
                 with_wire(wire, [&](auto w) {
                     constexpr int W = decltype(w)::value;
                     if (dir != 0) seg((CvtUnpackOp<W, SCALE> *)nullptr, (float)divisor);  // AVG or not: kSegAvg
+                    else if (srk && fbk) seg((CvtPackSrOp<SCALE, true> *)nullptr, res, sts);
+                    else if (srk) seg((CvtPackSrOp<SCALE> *)nullptr, sts);
                     else if (fbk) seg((CvtPackOp<W, true, SCALE> *)nullptr, res);
                     else seg((CvtPackOp<W, false, SCALE> *)nullptr);
                 });
@@ -954,7 +1096,7 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
             }
         const std::string label =
             in_place ? (dir == kSumsqInPlace ? "sumsq" : sc ? "scale" : "divide")
-                     : std::string(dir == 0 ? "pack" : "unpack") + (wire ? " cvt" : "") + (fbk ? " fb" : "") +
+                     : std::string(dir == 0 ? "pack" : "unpack") + (wire ? " cvt" : "") + (fbk ? " fb" : "") + (srk ? " sr" : "") +
                            (div && !sc && !stat ? " avg" : "") + (sc ? " scale" : "") + (stat ? " sumsq" : "");
         dep::op(stream, label, std::move(acc));
     }

@@ -286,7 +286,7 @@ size_t ThreadWorld::fused_allreduce(const void *const *srcs, void *const *dsts, 
                                     int dtype, hipStream_t user, const RingConfig &cfg, size_t cap, const int *ops,
                                     int src_dtype, void *const *residuals, const unsigned char *want,
                                     double *sumsq_out, std::vector<std::pair<size_t, size_t>> *cuts,
-                                    const float *prescale, const float *postscale) {
+                                    const float *prescale, const float *postscale, const WireStream *streams) {
     // the plan's kind: MIN / MAX plans hold one kind only (the keyed handler's groups)
     const int kind = ops && count > 0 ? reduce_kind(ops[0]) : DDL_ALLREDUCE_OP_SUM;
     for (int i = 0; ops && i < count; ++i)
@@ -323,12 +323,14 @@ size_t ThreadWorld::fused_allreduce(const void *const *srcs, void *const *dsts, 
         const std::vector<void *> dst(dsts + (size_t)r * count, dsts + (size_t)(r + 1) * count);
         std::vector<void *> res;
         if (residuals) res.assign(residuals + (size_t)r * count, residuals + (size_t)(r + 1) * count);
+        std::vector<WireStream> sts;
+        if (streams) sts.assign(streams + (size_t)r * count, streams + (size_t)(r + 1) * count);
         pipes_[r]->run(src, dst, b, dtype, cap, s, [&](void *buf, size_t elems, size_t message) {
             RingConfig c = cfg;
             c.order_bytes = message;
             ex_[r]->allreduce(buf, buf, elems, dtype, s, c, kind);
         }, ops ? &o : nullptr, P_, src_dtype, residuals ? &res : nullptr, stats.empty() ? nullptr : &stats[r],
-           prescale ? &pre : nullptr, postscale ? &post : nullptr);
+           prescale ? &pre : nullptr, postscale ? &post : nullptr, streams ? &sts : nullptr);
     });
     if (!stats.empty()) {
         DDL_HIP(hipStreamSynchronize(user));

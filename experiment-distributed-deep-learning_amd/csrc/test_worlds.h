@@ -186,7 +186,10 @@ public:
                            const unsigned char *want = nullptr, double *sumsq_out = nullptr,
                            std::vector<std::pair<size_t, size_t>> *cuts = nullptr,
                            // the scale factors (FusionPipe::run), one per segment, the same on every rank
-                           const float *prescale = nullptr, const float *postscale = nullptr);
+                           const float *prescale = nullptr, const float *postscale = nullptr,
+                           // stochastic rounding (FusionPipe::run's `streams`): rank r's segment i is
+                           // streams[r * count + i], null = none
+                           const WireStream *streams = nullptr);
 
 private:
     void run_(hipStream_t user, const std::function<void(int, hipStream_t)> &body);

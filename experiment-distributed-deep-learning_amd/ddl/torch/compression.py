@@ -28,6 +28,17 @@ When to reset: the residuals belong to the gradients' recent past. Call `reset_e
 after loading a checkpoint, and after a change of the loss scale by a large factor (the residuals
 were scaled by the old one) — unless the requests carry prescale = 1 / loss scale: the residual is
 kept in prescaled units, which are then the true gradient's and survive a change of the scale.
+
+Stochastic rounding: `Compression.bf16_stochastic`, the cheap cure for the same bias on the bf16 wire.
+Every rank chooses between the two bf16 neighbours of each value with probability proportional to the
+distance (include/ddl_amd.h, DDL_ALLREDUCE_WIRE_STOCHASTIC), so the expected value of what it sends is
+exactly its gradient: the constant 1 + 2**-10 reads 1.0 most steps and 1 + 2**-7 one step in eight, and
+its mean over the steps is 1 + 2**-10. The random bits are a stateless function of a per-process seed
+(`set_stochastic_seed`), the rank, the request name, how often that name was sent before and the element's
+index, so the ranks round independently and the noise of the sum averages down with the size. It keeps no
+residual, has nothing to reset, moves the plain bf16 pack's 6 bytes per element, and unlike feedback it
+removes the bias but not the per-step noise. The engine keeps one 8-byte counter per name, so — as with
+feedback — only for names that are stable from step to step. bf16 only: fp16's limit is range.
 """
 from ddl.torch import cpp_backend as cb
 
@@ -42,6 +53,10 @@ class _Wire:
     def feedback(self) -> bool:
         return bool(self.flag & cb.WIRE_FEEDBACK)
 
+    @property
+    def stochastic(self) -> bool:
+        return bool(self.flag & cb.WIRE_STOCHASTIC)
+
     def __repr__(self):
         return f'Compression.{self.name}'
 
@@ -51,12 +66,15 @@ class Compression:
     data-parallel optimizer wrapper. The `_feedback` kinds keep an error-feedback residual per
     request name (module docstring: one fp32 copy of every compressed gradient in device memory, a
     14-byte-per-element pack instead of 6; `reset_error_feedback()` after loading a checkpoint or
-    a large change of the loss scale); allreduce_gradient does not take them."""
+    a large change of the loss scale). `bf16_stochastic` rounds onto the bf16 wire stochastically
+    (module docstring: unbiased, no residual, nothing to reset, the plain 6-byte pack; one 8-byte
+    counter per request name). allreduce_gradient takes neither the `_feedback` kinds nor it."""
     none = _Wire('none', 0)
     fp16 = _Wire('fp16', cb.WIRE_FP16)
     bf16 = _Wire('bf16', cb.WIRE_BF16)
     fp16_feedback = _Wire('fp16_feedback', cb.WIRE_FP16 | cb.WIRE_FEEDBACK)
     bf16_feedback = _Wire('bf16_feedback', cb.WIRE_BF16 | cb.WIRE_FEEDBACK)
+    bf16_stochastic = _Wire('bf16_stochastic', cb.WIRE_BF16 | cb.WIRE_STOCHASTIC)
 
 
 def wire_flag(compression) -> int:
@@ -64,8 +82,8 @@ def wire_flag(compression) -> int:
     if compression is None:
         return 0
     if not isinstance(compression, _Wire):
-        raise TypeError('compression must be Compression.none, .fp16, .bf16, .fp16_feedback or .bf16_feedback, '
-                        f'not {compression!r}')
+        raise TypeError('compression must be Compression.none, .fp16, .bf16, .fp16_feedback, .bf16_feedback or '
+                        f'.bf16_stochastic, not {compression!r}')
     return compression.flag
 
 
@@ -77,3 +95,14 @@ def reset_error_feedback() -> None:
     lib = cb.CPPBackend.c_api()
     cb.check(lib.ddl_set_config(b'wire_feedback_epoch', int(lib.ddl_get_config(b'wire_feedback_epoch')) + 1),
              'ddl_set_config(wire_feedback_epoch)')
+
+
+def set_stochastic_seed(seed: int) -> None:
+    """Set this process's seed of `Compression.bf16_stochastic`'s random bits (the engine's per-process
+    `wire_stochastic_seed`, default 0; any integer, taken mod 2**64). The rank is mixed in by the
+    engine, so every rank may pass the same seed. Rank-local: nothing is communicated, and requests
+    packed from now on follow the new seed."""
+    seed = int(seed) & 0xffffffffffffffff
+    lib = cb.CPPBackend.c_api()
+    cb.check(lib.ddl_set_config(b'wire_stochastic_seed', seed - (1 << 64) if seed >= 1 << 63 else seed),
+             'ddl_set_config(wire_stochastic_seed)')

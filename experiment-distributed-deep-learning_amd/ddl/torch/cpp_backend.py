@@ -43,6 +43,7 @@ OP_SUM, OP_AVG = 0, 1  # enum ddl_allreduce_op
 OP_MIN, OP_MAX = 3, 4  # element-wise IEEE 754-2019 minimum / maximum (integers: their order); 2 is not an op
 WIRE_FP16, WIRE_BF16 = 0x100, 0x200  # enum ddl_allreduce_wire: OR-ed into a keyed fp32 device request's op
 WIRE_FEEDBACK = 0x1000  # error feedback: only together with exactly one of the two wire flags
+WIRE_STOCHASTIC = 0x8000  # stochastic rounding: only together with WIRE_BF16, never with WIRE_FEEDBACK
 SUMSQ = 0x2000  # enum ddl_allreduce_stat: `user` points to a SumsqArg (struct ddl_sumsq_arg)
 SCALE = 0x4000  # enum ddl_allreduce_scale: `user` points to a ScaleArg (struct ddl_scale_arg)
 MEMORY_DEVICE, MEMORY_HOST = 0, 1  # enum ddl_memory
@@ -218,6 +219,14 @@ class CPPBackend:
         sig('ddl_pack_cvt_fb', ci, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(sz), ci, ci, vp)
         sig('ddl_testing_thread_fused_allreduce_wire_fb', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp),
             ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(ci), ci, vp, ctypes.POINTER(sz))
+        u64p = ctypes.POINTER(ctypes.c_ulonglong)
+        # (testing library: the stochastic-rounding pack, the thread world with streams, the host mix)
+        sig('ddl_pack_cvt_sr', ci, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(sz), ci, ub, u64p, u64p, fp,
+            vp)
+        sig('ddl_testing_thread_fused_allreduce_wire_sr', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp),
+            ctypes.POINTER(sz), ctypes.POINTER(ci), ub, u64p, fp, fp, vp, ctypes.POINTER(sz), ub, dp,
+            ctypes.POINTER(sz), ctypes.POINTER(sz), ci, ctypes.POINTER(ci))
+        sig('ddl_testing_stochastic_stream', ci, ctypes.c_ulonglong, ci, ctypes.c_char_p, ctypes.c_ulonglong, u64p)
         sig('ddl_unpack_cvt', ci, ctypes.POINTER(vp), vp, ctypes.POINTER(sz), ctypes.POINTER(ci), ci, ci, ci, vp)
         sig('ddl_testing_thread_fused_allreduce_wire', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp),
             ctypes.POINTER(sz), ctypes.POINTER(ci), ci, vp, ctypes.POINTER(sz))

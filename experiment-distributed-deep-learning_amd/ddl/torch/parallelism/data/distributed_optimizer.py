@@ -47,6 +47,13 @@ bytes per element instead of 6; what travels between the ranks is unchanged. Cal
 `ddl.torch.compression.reset_error_feedback()` after loading a checkpoint and after a change of the
 loss scale by a large factor.
 
+`compression=Compression.bf16_stochastic`: the bf16 wire with stochastic rounding — every rank rounds
+each gradient element to one of its two bf16 neighbours with probability proportional to the distance,
+so what it sends is unbiased and a slowly changing gradient is not rounded the same way at every step.
+No residual, nothing to reset, the plain 6-byte pack; the stable per-parameter names of both paths
+(step() and the `overlap_backward` hooks) are what the engine's per-name sequence numbers need.
+`ddl.torch.compression.set_stochastic_seed(seed)` chooses the random bits (the rank is mixed in).
+
 `track_grad_norm=True` (implied by `max_grad_norm` and `skip_nonfinite`): after
 `allreduce_gradients()`, `optimizer.grad_norm` is the global L2 norm of the averaged gradients (a
 float) and `optimizer.found_nonfinite` is `not math.isfinite(grad_norm)`. Every dense fp32 device
@@ -392,7 +399,9 @@ def data_parallelism_distributed_optimizer_wrapper(
     feedback (module docstring): it costs one fp32 copy of every compressed gradient in device
     memory and a pack of 14 instead of 6 bytes per element; reset it with
     ddl.torch.compression.reset_error_feedback() after loading a checkpoint or a change of the loss
-    scale by a large factor. `track_grad_norm`: `optimizer.grad_norm` / `optimizer.found_nonfinite`
+    scale by a large factor. Compression.bf16_stochastic rounds onto the bf16 wire stochastically
+    (module docstring): unbiased, no residual, nothing to reset, the plain pack's 6 bytes per element;
+    ddl.torch.compression.set_stochastic_seed() seeds it. `track_grad_norm`: `optimizer.grad_norm` / `optimizer.found_nonfinite`
     after every allreduce_gradients(), from the engine's sums of squares (module docstring);
     `max_grad_norm`: clip the averaged gradients to that global L2 norm before the step;
     `skip_nonfinite`: skip the wrapped step() when a gradient holds an inf or NaN. The last two imply

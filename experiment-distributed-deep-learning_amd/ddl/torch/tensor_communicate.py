@@ -113,7 +113,9 @@ def allreduce_gradient(tensor: torch.Tensor, communicator: Communicator = None,
     gradient is reduced as without it. The error-feedback kinds (Compression.fp16_feedback /
     .bf16_feedback) raise ValueError: the compressed path here makes a fresh request name per call,
     and the engine keeps one residual per name, so every call would leak one — use
-    allreduce_async[_batch] or the optimizer wrapper, whose names are stable.
+    allreduce_async[_batch] or the optimizer wrapper, whose names are stable. Compression.bf16_stochastic
+    raises ValueError for the same reason: the engine keeps one sequence counter per name, and a fresh
+    name per call would grow that map for ever (and every call would draw from sequence number 0).
 
     Sparse gradient (torch sparse COO, the counterpart of TF's IndexedSlices, :26-30): the
     values and the indices are allgathered — every rank's rows in rank order — and the mean
@@ -124,6 +126,10 @@ def allreduce_gradient(tensor: torch.Tensor, communicator: Communicator = None,
         raise ValueError(f'allreduce_gradient does not take {compression!r}: its compressed requests get a fresh '
                          'name per call, which would leak one error-feedback residual per call; use allreduce_async '
                          'with a stable name')
+    if wire_flag(compression) & cb.WIRE_STOCHASTIC:
+        raise ValueError(f'allreduce_gradient does not take {compression!r}: its compressed requests get a fresh '
+                         'name per call, which would grow the engine\'s per-name sequence map by one entry per call; '
+                         'use allreduce_async with a stable name')
     if tensor.is_sparse:
         values = allgather(tensor._values(), communicator)
         if return_mean:
@@ -506,6 +512,8 @@ def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator 
     `compression` (Compression.fp16 / .bf16): a dense fp32 device tensor at size > 1 is sent and
     summed as 16-bit values and comes back as fp32 (ddl.torch.compression; every rank must pass the
     same compression for a name); any other tensor is submitted as without it. With
+    Compression.bf16_stochastic the bf16 rounding is stochastic and unbiased (the engine keeps one
+    8-byte sequence counter under `name`, so keep `name` stable from step to step). With
     Compression.fp16_feedback / .bf16_feedback the engine also keeps what the rounding removed under
     `name` and adds it to the next tensor submitted under that name (error feedback: one fp32 copy
     of the tensor in device memory per distinct name until the communicator goes, so keep the names

@@ -87,6 +87,9 @@ enum ddl_allreduce_op { DDL_ALLREDUCE_OP_SUM = 0, DDL_ALLREDUCE_OP_AVG = 1, DDL_
 enum ddl_allreduce_wire { DDL_ALLREDUCE_WIRE_FP16 = 0x100, DDL_ALLREDUCE_WIRE_BF16 = 0x200,
                           /* error feedback: only OR-ed with exactly one of the two above */
                           DDL_ALLREDUCE_WIRE_FEEDBACK = 0x1000 };
+/* Stochastic rounding onto the bf16 wire (MI355X extension; the data-plane section): one more bit of the
+ * same `op`, valid only OR-ed with DDL_ALLREDUCE_WIRE_BF16 and never with DDL_ALLREDUCE_WIRE_FEEDBACK. */
+enum ddl_allreduce_wire_rounding { DDL_ALLREDUCE_WIRE_STOCHASTIC = 0x8000 };
 /* Sum of squares of a keyed device allreduce of DDL_FLOAT tensors (MI355X extension; the data-plane
  * section): OR-ed into the `op` of ddl_allreduce_submit / _submit_batch (and _submit_mem /
  * _submit_batch_mem with DDL_MEMORY_DEVICE), SUM or AVG, with or without a wire flag. With the bit
@@ -203,7 +206,10 @@ int ddl_is_initialized(void);
  * one-rank world skips the keyed data plane; 0: runs it, for tests), "wire_feedback_epoch" (0,
  * default; per process: a key's error-feedback residual — DDL_ALLREDUCE_WIRE_FEEDBACK, the data-plane
  * section — restarts from zero when this differs from the value it was last written under: raise it
- * after loading a checkpoint or after a change of the loss scale by a large factor), "pipeline_rounds" (1,
+ * after loading a checkpoint or after a change of the loss scale by a large factor),
+ * "wire_stochastic_seed" (0, default; per process: the seed of the random bits of
+ * DDL_ALLREDUCE_WIRE_STOCHASTIC, the data-plane section; its 64 bits are read when a request is packed;
+ * rank-local like "wire_feedback_epoch", not a shared tunable), "pipeline_rounds" (1,
  * default: a completion thread fires a keyed round's done() calls as its plans land while the
  * engine thread negotiates the next round; 0: each round is waited for first), "reference_order" (1,
  * default: every allreduce sum equals the reference's MPI_Allreduce — MPICH 3.3.2 — bit for
@@ -321,6 +327,63 @@ void py_error(const char *log_str);
  * flag's own refusals apply.
  * P = 1: with "one_rank_shortcut" 1 nothing is touched and no residual is made; with 0 the data
  * plane runs and the feedback applies.
+ *
+ * Stochastic rounding: DDL_ALLREDUCE_WIRE_STOCHASTIC, valid only OR-ed with DDL_ALLREDUCE_WIRE_BF16, with
+ * op SUM or AVG, on a keyed DDL_FLOAT device request (ddl_allreduce_submit, _submit_batch, and _submit_mem /
+ * _submit_batch_mem with DDL_MEMORY_DEVICE), optionally together with DDL_ALLREDUCE_SUMSQ and
+ * DDL_ALLREDUCE_SCALE. Round-to-nearest onto bf16's 8 bits is biased for a gradient that changes slowly
+ * (a constant 1 + 2^-10 reads 1.0 for ever); with the bit every rank chooses between the two neighbouring
+ * bf16 values with probability proportional to the distance, so the expected value of what it sends is
+ * exactly its contribution. Against error feedback it keeps no residual, has nothing to reset and moves
+ * the plain converting pack's 6 bytes per element; it removes the bias, not the noise.
+ * Per element i of the request — i counts from the start of the tensor, never from the start of a piece —
+ * with c = g (x) a the contribution behind the prescale (as under "Scale factors"), u the 32 bits of c and
+ * r = R(S, i) a 16-bit integer:
+ *     c a NaN or an infinity:  w = narrow(c)                       today's round-to-nearest-even rule
+ *     otherwise:               w = the upper 16 bits of (u + r) mod 2^32
+ * Consequences: the sign never changes and +-0 stays +-0; bf16 subnormals are handled by the same formula;
+ * the magnitude goes to the neighbour away from zero with probability (u & 0xffff) / 65536, so for r
+ * uniform E[widen(w)] = c exactly; a finite c above the largest bf16 value becomes +-inf with that same
+ * probability. From w on the request is today's bf16 request: the same bytes, fusion group, plan cuts,
+ * bf16 summation in MPICH's order, widening, AVG quotient, postscale and sum of squares of the final values.
+ * R(S, i), the random bits: a stateless function of the 64-bit stream key S and the 64-bit element index i,
+ * integer arithmetic only (all 32-bit operations mod 2^32). One 32-bit word per element pair j = i >> 1:
+ *     x = fmix32(lo32(j) ^ lo32(S))
+ *     x = fmix32(x + hi32(S) + hi32(j) * 0x9e3779b9)
+ *     R(S, i) = bits 16 (i & 1) .. 16 (i & 1) + 15 of x
+ * with fmix32 MurmurHash3's finaliser: x ^= x >> 16; x *= 0x85ebca6b; x ^= x >> 13; x *= 0xc2b2ae35;
+ * x ^= x >> 16. Streams whose S differ only in low bits are permutations of each other under R, which is why
+ * S comes out of a 64-bit mix:
+ * S, the stream key: computed on the host once per request and round from the per-process config
+ * "wire_stochastic_seed", the rank in the communicator (the ranks round independently, so the noise of the
+ * sum averages down over P), the 64-bit FNV-1a hash h of the key's bytes (offset basis 0xcbf29ce484222325,
+ * prime 0x100000001b3) and the key's sequence number n — how many requests of this key with the bit this
+ * communicator has packed before (0, 1, 2, ...):
+ *     S = mix64(mix64(mix64(mix64(seed) ^ rank) ^ h) ^ n)
+ *     mix64(z): z += 0x9e3779b97f4a7c15; z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9;
+ *               z = (z ^ (z >> 27)) * 0x94d049bb133111eb; z ^ (z >> 31)          (one splitmix64 step)
+ * tests/_stochastic_helpers.py restates R, the rule and the mix in NumPy, bit for bit.
+ * n is kept per key by the communicator until the communicator is destroyed. EVERY DISTINCT KEY THAT EVER
+ * CARRIED THE BIT HOLDS ITS NAME AND 8 BYTES UNTIL THEN: a caller that makes fresh key names per step
+ * should not set the bit. A plan that fails may already have advanced n; that is not undone.
+ * All pieces of a request (plan cuts, pipeline sub-plans) use the same S with their own first element
+ * index, and the vector and the element path of the pack (csrc/pack.hip k_seg<CvtPackSrOp>) give the same
+ * bits, so the wire values do not depend on "fusion_threshold_bytes" or "fusion_pipeline_bytes", on the
+ * tensor's alignment or on what else shares the plan or the launch.
+ * The bit changes nothing that is communicated, so it is rank-local like the feedback bit: it is in no
+ * fusion group key, plan cut or negotiation, one pack launch may mix bf16 segments with and without it (a
+ * segment without it is converted exactly as the plain pack converts it), a launch with no stochastic
+ * segment is the kernel it was before, with the same tables and arguments, and ranks that disagree about
+ * it get different numbers, never a hang.
+ * Refusals, before anything is registered (the communicator works afterwards): the bit without WIRE_BF16,
+ * with WIRE_FP16, with WIRE_FEEDBACK, with MIN / MAX, with DDL_MEMORY_HOST, or on ddl_allreduce,
+ * ddl_allreduce_batch or ddl_allreduce_host returns DDL_STATUS_INVALID_ARGUMENT; on a dtype other than
+ * DDL_FLOAT the wire flag's own refusal applies (DDL_STATUS_UNSUPPORTED_DTYPE). fp16 is deliberately out:
+ * its subnormal range needs a different rule (the bit trick does not cross a change of format exponent
+ * range), and its practical limit is range, not precision. Feedback and stochastic rounding are
+ * alternatives; a request with both has no defined meaning here.
+ * P = 1: with "one_rank_shortcut" 1 nothing is rounded and n does not advance; with 0 the data plane runs
+ * and the rule applies.
  *
  * MIN / MAX: DDL_ALLREDUCE_OP_MIN = 3 and DDL_ALLREDUCE_OP_MAX = 4, on every dtype and every
  * allreduce entry point. Per element over the P inputs: DDL_INT32 / DDL_INT64 in signed order,

@@ -185,6 +185,23 @@ int ddl_unpack_scale(void *const *dsts, const void *src, const size_t *elements,
  * ddl_pack_cvt converts it. With every residual NULL the launch is ddl_pack_cvt's. */
 int ddl_pack_cvt_fb(void *dst, const void *const *srcs, void *const *residuals, const size_t *elements, int count,
                     int wire_dtype, void *hip_stream);
+/* ddl_pack_cvt onto the bf16 wire with stochastic rounding (DDL_ALLREDUCE_WIRE_STOCHASTIC; ddl_amd.h
+ * "Stochastic rounding"; k_seg<CvtPackSrOp>): segment i with want[i] != 0 is narrowed by that rule with the
+ * stream key streams[i], its element e being element firsts[i] + e of its request; want[i] == 0: segment i
+ * is converted as ddl_pack_cvt converts it (streams[i] / firsts[i] unused). residuals: NULL, or as in
+ * ddl_pack_cvt_fb — a keyed plan may mix requests with the feedback bit and with this one, so one launch may
+ * hold segments of both kinds (a segment with a residual must have want[i] == 0). scale: NULL, or one
+ * prescale factor per segment as in ddl_pack_scale. With no wanted non-empty segment the launch is
+ * ddl_pack_cvt's (ddl_pack_cvt_fb's, ddl_pack_scale's). */
+int ddl_pack_cvt_sr(void *dst, const void *const *srcs, void *const *residuals, const size_t *elements, int count,
+                    const unsigned char *want,
+                    const unsigned long long *streams, const unsigned long long *firsts, const float *scale,
+                    void *hip_stream);
+/* The host mix of a keyed request's stream key (ddl_amd.h "Stochastic rounding"): *S for the config
+ * "wire_stochastic_seed" value `seed`, the rank in the communicator, the request key (a C string) and the
+ * key's sequence number n. */
+int ddl_testing_stochastic_stream(unsigned long long seed, int rank, const char *key, unsigned long long n,
+                                  unsigned long long *S);
 
 /* ---- single-GPU rehearsal of the ring schedule --------------------------------------- */
 /* Runs the exact per-rank ring schedule for `nranks` virtual ranks inside this process on
@@ -275,6 +292,16 @@ int ddl_testing_thread_fused_allreduce_scale(int nranks, int count, const void *
                                              void *hip_stream, size_t *subplans, const unsigned char *want,
                                              double *sumsq_out, size_t *cut_segs, size_t *cut_elems, int max_cuts,
                                              int *ncuts);
+/* ddl_testing_thread_fused_allreduce_scale over the bf16 wire with stochastic rounding and no residuals:
+ * sr_want[i] != 0 = segment i is rounded stochastically on every virtual rank, rank r with the stream key
+ * streams[r * count + i] and first element index 0, handed to the plan as the keyed handler hands over its
+ * own (FusionPipe::run's `streams`: a sub-plan's piece starts at its element offset). */
+int ddl_testing_thread_fused_allreduce_wire_sr(int nranks, int count, const void *const *srcs, void *const *dsts,
+                                               const size_t *elements, const int *ops, const unsigned char *sr_want,
+                                               const unsigned long long *streams, const float *prescale,
+                                               const float *postscale, void *hip_stream, size_t *subplans,
+                                               const unsigned char *want, double *sumsq_out, size_t *cut_segs,
+                                               size_t *cut_elems, int max_cuts, int *ncuts);
 /* Data movement of the thread worlds made from now on: rccl = 0 device copies (default); 1 every
  * matched send / receive pair goes through RcclTransport::group as a self send + self receive on
  * the RCCL loopback communicator (ddl_rccl_loopback_init first), posted on the receiver's stream
