@@ -155,14 +155,27 @@ struct RegisterFinalize {
     RegisterFinalize() { add_finalize_hook(&testing_finalize); }
 } g_register_finalize;
 
-// wire-side byte lengths of `elements` fp32 values sent as wire_dtype (ddl_pack_cvt, ...)
-std::vector<size_t> wire_bytes(const size_t *elements, int count, int wire_dtype) {
+// flat-side bytes of one fp32 value sent as wire_dtype (ddl_pack_cvt, ...); `fp32`: 0 = no wire, its own 4
+size_t wire_unit(int wire_dtype, bool fp32 = false) {
+    if (fp32 && !wire_dtype) return sizeof(float);
     DDL_REQUIRE(wire_dtype == DDL_HALF || wire_dtype == DDL_BFLOAT16, DDL_STATUS_UNSUPPORTED_DTYPE,
                 "wire dtype " << wire_dtype << " is neither float16 nor bfloat16");
-    std::vector<size_t> b(count);
-    for (int i = 0; i < count; ++i) b[i] = elements[i] * dtype_size(wire_dtype);
-    return b;
+    return dtype_size(wire_dtype);
 }
+
+// The segments of a copier export from its C arrays: ptrs[i] with n[i] * unit flat-side bytes; a null
+// array = the CopySeg default. One grow-only vector (under abi_copier_mu, as the copier): no allocation per call.
+std::vector<CopySeg> &copy_segs(int count, void *const *ptrs, const size_t *n, size_t unit, const int *ops = nullptr,
+                                const float *scale = nullptr, void *const *residuals = nullptr,
+                                const unsigned char *want = nullptr) {
+    static std::vector<CopySeg> v;
+    v.resize((size_t)std::max(count, 0));
+    for (int i = 0; i < count; ++i)
+        v[(size_t)i] = CopySeg{ptrs[i], n[i] * unit, ops ? ops[i] : DDL_ALLREDUCE_OP_SUM, scale ? scale[i] : 1.0f,
+                               residuals ? residuals[i] : nullptr, WireStream{}, want && want[i]};
+    return v;
+}
+void *const *unconst(const void *const *p) { return const_cast<void *const *>(p); }
 
 // ddl_unpack_ops_sumsq / ddl_unpack_cvt_sumsq: the piece values through pinned memory, waited for here.
 // One grow-only pinned buffer (under abi_copier_mu, as the copier): no allocation per call, so the
@@ -193,6 +206,63 @@ void unpack_sumsq(int count, void *hip_stream, double *sumsq_out, const Run &run
     }
     DDL_HIP(hipStreamSynchronize(as_stream(hip_stream)));
     std::copy(buf, buf + count, sumsq_out);
+}
+// One ddl_testing_thread_fused_allreduce* call: its C arrays (null = none) as PlanSegs through the thread
+// world, then `subplans` and the cuts. Segment i has n[i] * unit wire bytes on every rank; srcs, dsts,
+// residuals and keys are [r * count + i], the other arrays [i].
+struct FusedCall {
+    int nranks, count;
+    const void *const *srcs;
+    void *const *dsts;
+    const size_t *n;
+    size_t unit;
+    int dtype, src_dtype;
+    void *hip_stream;
+    size_t *subplans;
+    const int *ops = nullptr;
+    void *const *residuals = nullptr;
+    const float *prescale = nullptr, *postscale = nullptr;
+    const unsigned char *sr_want = nullptr;  // stochastic rounding with the stream keys `keys`, from element 0
+    const unsigned long long *keys = nullptr;
+    const unsigned char *want = nullptr;  // the sums of squares into sumsq_out
+    double *sumsq_out = nullptr;
+    size_t *cut_segs = nullptr, *cut_elems = nullptr;
+    int max_cuts = 0, *ncuts = nullptr;
+};
+void thread_fused(const FusedCall &c) {
+    std::vector<PlanSeg> segs;
+    for (int r = 0; r < c.nranks; ++r)
+        for (int i = 0; i < c.count; ++i) {
+            const size_t k = (size_t)r * c.count + i;
+            segs.push_back(PlanSeg{c.srcs[k], c.dsts[k], c.n[i] * c.unit, c.ops ? c.ops[i] : DDL_ALLREDUCE_OP_SUM,
+                                   c.prescale ? c.prescale[i] : 1.0f, c.postscale ? c.postscale[i] : 1.0f,
+                                   c.residuals ? c.residuals[k] : nullptr,
+                                   c.sr_want && c.sr_want[i] ? WireStream{c.keys[k], 0, 1} : WireStream{},
+                                   c.want && c.want[i]});
+        }
+    std::vector<std::pair<size_t, size_t>> cuts;
+    const size_t j = thread_world(c.nranks).fused_allreduce(
+        segs.data(), c.count, c.dtype, c.src_dtype, (size_t)config().fusion_pipeline_bytes.load(), as_stream(c.hip_stream),
+        config().ring(), c.want ? c.sumsq_out : nullptr, &cuts);
+    if (c.subplans) *c.subplans = j;
+    if (c.ncuts) *c.ncuts = (int)cuts.size();
+    for (int k = 0; k < c.max_cuts && k < (int)cuts.size() && c.cut_segs && c.cut_elems; ++k) {
+        c.cut_segs[k] = cuts[(size_t)k].first;
+        c.cut_elems[k] = cuts[(size_t)k].second;
+    }
+}
+// the ops of a fused fp32 plan with a wire, a statistic or factors: SUM or AVG
+void check_float_ops(const int *ops, int count, const char *minmax) {
+    for (int i = 0; ops && i < count; ++i) {
+        check_allreduce_op(ops[i], DDL_FLOAT);
+        DDL_REQUIRE(!op_is_minmax(ops[i]), DDL_STATUS_INVALID_ARGUMENT, minmax);
+    }
+}
+void check_factors(const float *prescale, const float *postscale, int count) {
+    for (int i = 0; i < count; ++i)
+        for (const float *f : {prescale, postscale})
+            DDL_REQUIRE(!f || (std::isfinite(f[i]) && f[i] > 0.0f), DDL_STATUS_INVALID_ARGUMENT,
+                        "scale factors must be finite and positive");
 }
 }  // namespace
 
@@ -454,7 +524,7 @@ int ddl_pack(void *dst, const void *const *srcs, const size_t *bytes, int count,
     return guarded([&] {
         DDL_REQUIRE(count >= 0 && (count == 0 || (dst && srcs && bytes)), DDL_STATUS_INVALID_ARGUMENT, "bad pack args");
         std::lock_guard<std::mutex> g(abi_copier_mu());
-        abi_copier().run(0, dst, const_cast<void *const *>(srcs), bytes, count, as_stream(hip_stream));
+        abi_copier().copy(0, dst, unconst(srcs), bytes, count, as_stream(hip_stream));
     });
 }
 
@@ -462,7 +532,7 @@ int ddl_unpack(void *const *dsts, const void *src, const size_t *bytes, int coun
     return guarded([&] {
         DDL_REQUIRE(count >= 0 && (count == 0 || (src && dsts && bytes)), DDL_STATUS_INVALID_ARGUMENT, "bad unpack args");
         std::lock_guard<std::mutex> g(abi_copier_mu());
-        abi_copier().run(1, const_cast<void *>(src), dsts, bytes, count, as_stream(hip_stream));
+        abi_copier().copy(1, const_cast<void *>(src), dsts, bytes, count, as_stream(hip_stream));
     });
 }
 
@@ -472,8 +542,10 @@ int ddl_unpack_ops(void *const *dsts, const void *src, const size_t *bytes, cons
         DDL_REQUIRE(count >= 0 && (count == 0 || (dsts && bytes && ops)) && divisor >= 1, DDL_STATUS_INVALID_ARGUMENT,
                     "bad unpack_ops args");
         std::lock_guard<std::mutex> g(abi_copier_mu());
-        abi_copier().run(src ? 1 : SegmentCopier::kDivInPlace, const_cast<void *>(src), dsts, bytes, count,
-                         as_stream(hip_stream), dtype, divisor, ops);
+        const std::vector<CopySeg> &segs = copy_segs(count, dsts, bytes, 1, ops);
+        abi_copier().run(CopyLaunch{src ? 1 : SegmentCopier::kDivInPlace, const_cast<void *>(src), as_stream(hip_stream),
+                                    dtype, 0, divisor},
+                         segs.data(), count);
     });
 }
 
@@ -484,9 +556,11 @@ int ddl_unpack_ops_sumsq(void *const *dsts, const void *src, const size_t *bytes
                     DDL_STATUS_INVALID_ARGUMENT, "bad unpack_ops_sumsq args");
         if (count == 0) return;
         std::lock_guard<std::mutex> g(abi_copier_mu());
+        const std::vector<CopySeg> &segs = copy_segs(count, dsts, bytes, 1, ops, nullptr, nullptr, want);
         unpack_sumsq(count, hip_stream, sumsq_out, [&](double *sq) {
-            abi_copier().run(src ? 1 : SegmentCopier::kSumsqInPlace, const_cast<void *>(src), dsts, bytes, count,
-                             as_stream(hip_stream), dtype, divisor, ops, want, sq);
+            abi_copier().run(CopyLaunch{src ? 1 : SegmentCopier::kSumsqInPlace, const_cast<void *>(src),
+                                        as_stream(hip_stream), dtype, 0, divisor, sq},
+                             segs.data(), count);
         });
     });
 }
@@ -497,15 +571,13 @@ int ddl_unpack_cvt_sumsq(void *const *dsts, const void *src, const size_t *eleme
         DDL_REQUIRE(count >= 0 && (count == 0 || (dsts && elements && want && sumsq_out)) && divisor >= 1,
                     DDL_STATUS_INVALID_ARGUMENT, "bad unpack_cvt_sumsq args");
         if (count == 0) return;
-        for (int i = 0; ops && i < count; ++i) {
-            check_allreduce_op(ops[i], DDL_FLOAT);
-            DDL_REQUIRE(!op_is_minmax(ops[i]), DDL_STATUS_INVALID_ARGUMENT, "MIN / MAX take no wire");
-        }
-        const std::vector<size_t> b = wire_bytes(elements, count, wire_dtype);
+        check_float_ops(ops, count, "MIN / MAX take no wire");
         std::lock_guard<std::mutex> g(abi_copier_mu());
+        const std::vector<CopySeg> &segs = copy_segs(count, dsts, elements, wire_unit(wire_dtype), ops, nullptr, nullptr, want);
         unpack_sumsq(count, hip_stream, sumsq_out, [&](double *sq) {
-            abi_copier().run_cvt(src ? 1 : SegmentCopier::kSumsqInPlace, const_cast<void *>(src), dsts, b.data(), count,
-                                 as_stream(hip_stream), DDL_FLOAT, wire_dtype, divisor, ops, nullptr, want, sq);
+            abi_copier().run(CopyLaunch{src ? 1 : SegmentCopier::kSumsqInPlace, const_cast<void *>(src),
+                                        as_stream(hip_stream), DDL_FLOAT, wire_dtype, divisor, sq},
+                             segs.data(), count);
         });
     });
 }
@@ -517,16 +589,9 @@ int ddl_pack_scale(void *dst, const void *const *srcs, void *const *residuals, c
         DDL_REQUIRE(count >= 0 && (count == 0 || (dst && srcs && elements && scale)) && (!residuals || wire_dtype),
                     DDL_STATUS_INVALID_ARGUMENT, "bad pack_scale args");
         std::lock_guard<std::mutex> g(abi_copier_mu());
-        if (wire_dtype) {
-            const std::vector<size_t> b = wire_bytes(elements, count, wire_dtype);
-            abi_copier().run_cvt(0, dst, const_cast<void *const *>(srcs), b.data(), count, as_stream(hip_stream), DDL_FLOAT,
-                                 wire_dtype, 1, nullptr, residuals, nullptr, nullptr, scale);
-        } else {
-            std::vector<size_t> b((size_t)count);
-            for (int i = 0; i < count; ++i) b[(size_t)i] = elements[i] * sizeof(float);
-            abi_copier().run(0, dst, const_cast<void *const *>(srcs), b.data(), count, as_stream(hip_stream), DDL_FLOAT, 1,
-                             nullptr, nullptr, nullptr, scale);
-        }
+        const std::vector<CopySeg> &segs =
+            copy_segs(count, unconst(srcs), elements, wire_unit(wire_dtype, true), nullptr, scale, residuals);
+        abi_copier().run(CopyLaunch{0, dst, as_stream(hip_stream), DDL_FLOAT, wire_dtype}, segs.data(), count);
     });
 }
 
@@ -538,22 +603,13 @@ int ddl_unpack_scale(void *const *dsts, const void *src, const size_t *elements,
                         (!want || sumsq_out) && (src || (!wire_dtype && !want)),
                     DDL_STATUS_INVALID_ARGUMENT, "bad unpack_scale args");
         if (count == 0) return;
-        for (int i = 0; i < count; ++i) {
-            check_allreduce_op(ops[i], DDL_FLOAT);
-            DDL_REQUIRE(!op_is_minmax(ops[i]), DDL_STATUS_INVALID_ARGUMENT, "scale factors take SUM or AVG");
-        }
-        std::vector<size_t> b((size_t)count);
-        if (wire_dtype) b = wire_bytes(elements, count, wire_dtype);
-        else
-            for (int i = 0; i < count; ++i) b[(size_t)i] = elements[i] * sizeof(float);
+        check_float_ops(ops, count, "scale factors take SUM or AVG");
         std::lock_guard<std::mutex> g(abi_copier_mu());
+        const std::vector<CopySeg> &segs = copy_segs(count, dsts, elements, wire_unit(wire_dtype, true), ops, scale, nullptr, want);
         auto run = [&](double *sq) {
-            if (wire_dtype)
-                abi_copier().run_cvt(1, const_cast<void *>(src), dsts, b.data(), count, as_stream(hip_stream), DDL_FLOAT,
-                                     wire_dtype, divisor, ops, nullptr, want, sq, scale);
-            else
-                abi_copier().run(src ? 1 : SegmentCopier::kDivInPlace, const_cast<void *>(src), dsts, b.data(), count,
-                                 as_stream(hip_stream), DDL_FLOAT, divisor, ops, want, sq, scale);
+            abi_copier().run(CopyLaunch{src ? 1 : SegmentCopier::kDivInPlace, const_cast<void *>(src),
+                                        as_stream(hip_stream), DDL_FLOAT, wire_dtype, divisor, sq},
+                             segs.data(), count);
         };
         if (want) unpack_sumsq(count, hip_stream, sumsq_out, run);
         else run(nullptr);
@@ -565,10 +621,9 @@ int ddl_pack_cvt(void *dst, const void *const *srcs, const size_t *elements, int
     return guarded([&] {
         DDL_REQUIRE(count >= 0 && (count == 0 || (dst && srcs && elements)), DDL_STATUS_INVALID_ARGUMENT,
                     "bad pack_cvt args");
-        const std::vector<size_t> b = wire_bytes(elements, count, wire_dtype);
         std::lock_guard<std::mutex> g(abi_copier_mu());
-        abi_copier().run_cvt(0, dst, const_cast<void *const *>(srcs), b.data(), count, as_stream(hip_stream), DDL_FLOAT,
-                             wire_dtype);
+        const std::vector<CopySeg> &segs = copy_segs(count, unconst(srcs), elements, wire_unit(wire_dtype));
+        abi_copier().run(CopyLaunch{0, dst, as_stream(hip_stream), DDL_FLOAT, wire_dtype}, segs.data(), count);
     });
 }
 
@@ -577,10 +632,10 @@ int ddl_pack_cvt_fb(void *dst, const void *const *srcs, void *const *residuals, 
     return guarded([&] {
         DDL_REQUIRE(count >= 0 && (count == 0 || (dst && srcs && residuals && elements)), DDL_STATUS_INVALID_ARGUMENT,
                     "bad pack_cvt_fb args");
-        const std::vector<size_t> b = wire_bytes(elements, count, wire_dtype);
         std::lock_guard<std::mutex> g(abi_copier_mu());
-        abi_copier().run_cvt(0, dst, const_cast<void *const *>(srcs), b.data(), count, as_stream(hip_stream), DDL_FLOAT,
-                             wire_dtype, 1, nullptr, residuals);
+        const std::vector<CopySeg> &segs =
+            copy_segs(count, unconst(srcs), elements, wire_unit(wire_dtype), nullptr, nullptr, residuals);
+        abi_copier().run(CopyLaunch{0, dst, as_stream(hip_stream), DDL_FLOAT, wire_dtype}, segs.data(), count);
     });
 }
 
@@ -590,13 +645,11 @@ int ddl_pack_cvt_sr(void *dst, const void *const *srcs, void *const *residuals, 
     return guarded([&] {
         DDL_REQUIRE(count >= 0 && (count == 0 || (dst && srcs && elements && want && streams && firsts)),
                     DDL_STATUS_INVALID_ARGUMENT, "bad pack_cvt_sr args");
-        const std::vector<size_t> b = wire_bytes(elements, count, DDL_BFLOAT16);
-        std::vector<WireStream> st((size_t)count);
-        for (int i = 0; i < count; ++i)
-            if (want[i]) st[(size_t)i] = WireStream{streams[i], firsts[i], 1};
         std::lock_guard<std::mutex> g(abi_copier_mu());
-        abi_copier().run_cvt(0, dst, const_cast<void *const *>(srcs), b.data(), count, as_stream(hip_stream), DDL_FLOAT,
-                             DDL_BFLOAT16, 1, nullptr, residuals, nullptr, nullptr, scale, st.data());
+        std::vector<CopySeg> &segs = copy_segs(count, unconst(srcs), elements, wire_unit(DDL_BFLOAT16), nullptr, scale, residuals);
+        for (int i = 0; i < count; ++i)
+            if (want[i]) segs[(size_t)i].stream = WireStream{streams[i], firsts[i], 1};
+        abi_copier().run(CopyLaunch{0, dst, as_stream(hip_stream), DDL_FLOAT, DDL_BFLOAT16}, segs.data(), count);
     });
 }
 
@@ -613,14 +666,11 @@ int ddl_unpack_cvt(void *const *dsts, const void *src, const size_t *elements, c
     return guarded([&] {
         DDL_REQUIRE(count >= 0 && (count == 0 || (src && dsts && elements)) && divisor >= 1, DDL_STATUS_INVALID_ARGUMENT,
                     "bad unpack_cvt args");
-        for (int i = 0; ops && i < count; ++i) {
-            check_allreduce_op(ops[i], DDL_FLOAT);
-            DDL_REQUIRE(!op_is_minmax(ops[i]), DDL_STATUS_INVALID_ARGUMENT, "MIN / MAX take no wire");
-        }
-        const std::vector<size_t> b = wire_bytes(elements, count, wire_dtype);
+        check_float_ops(ops, count, "MIN / MAX take no wire");
         std::lock_guard<std::mutex> g(abi_copier_mu());
-        abi_copier().run_cvt(1, const_cast<void *>(src), dsts, b.data(), count, as_stream(hip_stream), DDL_FLOAT,
-                             wire_dtype, divisor, ops);
+        const std::vector<CopySeg> &segs = copy_segs(count, dsts, elements, wire_unit(wire_dtype), ops);
+        abi_copier().run(CopyLaunch{1, const_cast<void *>(src), as_stream(hip_stream), DDL_FLOAT, wire_dtype, divisor},
+                         segs.data(), count);
     });
 }
 
@@ -634,11 +684,11 @@ int ddl_local_ring_allreduce(int nranks, const void *const *sends, void *const *
         local_world(nranks).allreduce(sends, recvs, elements, dtype, as_stream(hip_stream), config().ring(),
                                       reduce_kind(op));
         if (op == DDL_ALLREDUCE_OP_AVG && nranks > 1 && elements) {  // every rank's result, one launch
-            const std::vector<size_t> bytes(nranks, elements * dtype_size(dtype));
-            const std::vector<int> ops(nranks, op);
+            std::vector<CopySeg> segs;
+            for (int r = 0; r < nranks; ++r) segs.push_back(CopySeg{recvs[r], elements * dtype_size(dtype), op});
             std::lock_guard<std::mutex> g(abi_copier_mu());
-            abi_copier().run(SegmentCopier::kDivInPlace, nullptr, recvs, bytes.data(), nranks, as_stream(hip_stream), dtype,
-                             nranks, ops.data());
+            abi_copier().run(CopyLaunch{SegmentCopier::kDivInPlace, nullptr, as_stream(hip_stream), dtype, 0, nranks},
+                             segs.data(), nranks);
         }
     });
 }
@@ -739,10 +789,9 @@ int ddl_testing_thread_fused_allreduce_ops(int nranks, int count, const void *co
         for (int i = 0; i < count; ++i)
             DDL_REQUIRE(bytes[i] % es == 0, DDL_STATUS_INVALID_ARGUMENT, "segment " << i << " is not whole elements");
         for (int i = 0; ops && i < count; ++i) check_allreduce_op(ops[i], dtype);
-        const size_t j = thread_world(nranks).fused_allreduce(srcs, dsts, bytes, count, dtype, as_stream(hip_stream),
-                                                              config().ring(),
-                                                              (size_t)config().fusion_pipeline_bytes.load(), ops);
-        if (subplans) *subplans = j;
+        FusedCall c{nranks, count, srcs, dsts, bytes, 1, dtype, 0, hip_stream, subplans};
+        c.ops = ops;
+        thread_fused(c);
     });
 }
 
@@ -752,16 +801,10 @@ int ddl_testing_thread_fused_allreduce_wire(int nranks, int count, const void *c
     return guarded([&] {
         DDL_REQUIRE(nranks >= 1 && nranks <= 64 && count >= 1 && srcs && dsts && elements, DDL_STATUS_INVALID_ARGUMENT,
                     "bad thread fused allreduce");
-        for (int i = 0; ops && i < count; ++i) {
-            check_allreduce_op(ops[i], DDL_FLOAT);
-            DDL_REQUIRE(!op_is_minmax(ops[i]), DDL_STATUS_INVALID_ARGUMENT, "MIN / MAX take no wire");
-        }
-        const std::vector<size_t> b = wire_bytes(elements, count, wire_dtype);
-        const size_t j = thread_world(nranks).fused_allreduce(srcs, dsts, b.data(), count, wire_dtype,
-                                                              as_stream(hip_stream), config().ring(),
-                                                              (size_t)config().fusion_pipeline_bytes.load(), ops,
-                                                              DDL_FLOAT);
-        if (subplans) *subplans = j;
+        check_float_ops(ops, count, "MIN / MAX take no wire");
+        FusedCall c{nranks, count, srcs, dsts, elements, wire_unit(wire_dtype), wire_dtype, DDL_FLOAT, hip_stream, subplans};
+        c.ops = ops;
+        thread_fused(c);
     });
 }
 
@@ -771,16 +814,11 @@ int ddl_testing_thread_fused_allreduce_wire_fb(int nranks, int count, const void
     return guarded([&] {
         DDL_REQUIRE(nranks >= 1 && nranks <= 64 && count >= 1 && srcs && dsts && residuals && elements,
                     DDL_STATUS_INVALID_ARGUMENT, "bad thread fused allreduce");
-        for (int i = 0; ops && i < count; ++i) {
-            check_allreduce_op(ops[i], DDL_FLOAT);
-            DDL_REQUIRE(!op_is_minmax(ops[i]), DDL_STATUS_INVALID_ARGUMENT, "MIN / MAX take no wire");
-        }
-        const std::vector<size_t> b = wire_bytes(elements, count, wire_dtype);
-        const size_t j = thread_world(nranks).fused_allreduce(srcs, dsts, b.data(), count, wire_dtype,
-                                                              as_stream(hip_stream), config().ring(),
-                                                              (size_t)config().fusion_pipeline_bytes.load(), ops,
-                                                              DDL_FLOAT, residuals);
-        if (subplans) *subplans = j;
+        check_float_ops(ops, count, "MIN / MAX take no wire");
+        FusedCall c{nranks, count, srcs, dsts, elements, wire_unit(wire_dtype), wire_dtype, DDL_FLOAT, hip_stream, subplans};
+        c.ops = ops;
+        c.residuals = residuals;
+        thread_fused(c);
     });
 }
 
@@ -791,24 +829,13 @@ int ddl_testing_thread_fused_allreduce_sumsq(int nranks, int count, const void *
     return guarded([&] {
         DDL_REQUIRE(nranks >= 1 && nranks <= 64 && count >= 1 && srcs && dsts && elements && want && sumsq_out,
                     DDL_STATUS_INVALID_ARGUMENT, "bad thread fused allreduce");
-        for (int i = 0; ops && i < count; ++i) {
-            check_allreduce_op(ops[i], DDL_FLOAT);
-            DDL_REQUIRE(!op_is_minmax(ops[i]), DDL_STATUS_INVALID_ARGUMENT, "the sum of squares takes SUM or AVG");
-        }
-        std::vector<size_t> b(count);
-        if (wire_dtype) b = wire_bytes(elements, count, wire_dtype);
-        else
-            for (int i = 0; i < count; ++i) b[i] = elements[i] * sizeof(float);
-        std::vector<std::pair<size_t, size_t>> cuts;
-        const size_t j = thread_world(nranks).fused_allreduce(
-            srcs, dsts, b.data(), count, wire_dtype ? wire_dtype : DDL_FLOAT, as_stream(hip_stream), config().ring(),
-            (size_t)config().fusion_pipeline_bytes.load(), ops, wire_dtype ? DDL_FLOAT : 0, nullptr, want, sumsq_out, &cuts);
-        if (subplans) *subplans = j;
-        if (ncuts) *ncuts = (int)cuts.size();
-        for (int k = 0; k < max_cuts && k < (int)cuts.size() && cut_segs && cut_elems; ++k) {
-            cut_segs[k] = cuts[k].first;
-            cut_elems[k] = cuts[k].second;
-        }
+        check_float_ops(ops, count, "the sum of squares takes SUM or AVG");
+        FusedCall c{nranks, count, srcs, dsts, elements, wire_unit(wire_dtype, true), wire_dtype ? wire_dtype : DDL_FLOAT,
+                    wire_dtype ? DDL_FLOAT : 0, hip_stream, subplans};
+        c.ops = ops;
+        c.want = want, c.sumsq_out = sumsq_out;
+        c.cut_segs = cut_segs, c.cut_elems = cut_elems, c.max_cuts = max_cuts, c.ncuts = ncuts;
+        thread_fused(c);
     });
 }
 
@@ -822,29 +849,16 @@ int ddl_testing_thread_fused_allreduce_scale(int nranks, int count, const void *
         DDL_REQUIRE(nranks >= 1 && nranks <= 64 && count >= 1 && srcs && dsts && elements && (!want || sumsq_out) &&
                         (!residuals || wire_dtype),
                     DDL_STATUS_INVALID_ARGUMENT, "bad thread fused allreduce");
-        for (int i = 0; ops && i < count; ++i) {
-            check_allreduce_op(ops[i], DDL_FLOAT);
-            DDL_REQUIRE(!op_is_minmax(ops[i]), DDL_STATUS_INVALID_ARGUMENT, "scale factors take SUM or AVG");
-        }
-        for (int i = 0; i < count; ++i)
-            for (const float *f : {prescale, postscale})
-                DDL_REQUIRE(!f || (std::isfinite(f[i]) && f[i] > 0.0f), DDL_STATUS_INVALID_ARGUMENT,
-                            "scale factors must be finite and positive");
-        std::vector<size_t> b(count);
-        if (wire_dtype) b = wire_bytes(elements, count, wire_dtype);
-        else
-            for (int i = 0; i < count; ++i) b[i] = elements[i] * sizeof(float);
-        std::vector<std::pair<size_t, size_t>> cuts;
-        const size_t j = thread_world(nranks).fused_allreduce(
-            srcs, dsts, b.data(), count, wire_dtype ? wire_dtype : DDL_FLOAT, as_stream(hip_stream), config().ring(),
-            (size_t)config().fusion_pipeline_bytes.load(), ops, wire_dtype ? DDL_FLOAT : 0, residuals, want, sumsq_out, &cuts,
-            prescale, postscale);
-        if (subplans) *subplans = j;
-        if (ncuts) *ncuts = (int)cuts.size();
-        for (int k = 0; k < max_cuts && k < (int)cuts.size() && cut_segs && cut_elems; ++k) {
-            cut_segs[k] = cuts[k].first;
-            cut_elems[k] = cuts[k].second;
-        }
+        check_float_ops(ops, count, "scale factors take SUM or AVG");
+        check_factors(prescale, postscale, count);
+        FusedCall c{nranks, count, srcs, dsts, elements, wire_unit(wire_dtype, true), wire_dtype ? wire_dtype : DDL_FLOAT,
+                    wire_dtype ? DDL_FLOAT : 0, hip_stream, subplans};
+        c.ops = ops;
+        c.residuals = residuals;
+        c.prescale = prescale, c.postscale = postscale;
+        c.want = want, c.sumsq_out = sumsq_out;
+        c.cut_segs = cut_segs, c.cut_elems = cut_elems, c.max_cuts = max_cuts, c.ncuts = ncuts;
+        thread_fused(c);
     });
 }
 
@@ -858,30 +872,15 @@ int ddl_testing_thread_fused_allreduce_wire_sr(int nranks, int count, const void
         DDL_REQUIRE(nranks >= 1 && nranks <= 64 && count >= 1 && srcs && dsts && elements && sr_want && streams &&
                         (!want || sumsq_out),
                     DDL_STATUS_INVALID_ARGUMENT, "bad thread fused allreduce");
-        for (int i = 0; ops && i < count; ++i) {
-            check_allreduce_op(ops[i], DDL_FLOAT);
-            DDL_REQUIRE(!op_is_minmax(ops[i]), DDL_STATUS_INVALID_ARGUMENT, "MIN / MAX take no wire");
-        }
-        for (int i = 0; i < count; ++i)
-            for (const float *f : {prescale, postscale})
-                DDL_REQUIRE(!f || (std::isfinite(f[i]) && f[i] > 0.0f), DDL_STATUS_INVALID_ARGUMENT,
-                            "scale factors must be finite and positive");
-        const std::vector<size_t> b = wire_bytes(elements, count, DDL_BFLOAT16);
-        std::vector<WireStream> st((size_t)nranks * count);
-        for (int r = 0; r < nranks; ++r)
-            for (int i = 0; i < count; ++i)
-                if (sr_want[i]) st[(size_t)r * count + i] = WireStream{streams[(size_t)r * count + i], 0, 1};
-        std::vector<std::pair<size_t, size_t>> cuts;
-        const size_t j = thread_world(nranks).fused_allreduce(
-            srcs, dsts, b.data(), count, DDL_BFLOAT16, as_stream(hip_stream), config().ring(),
-            (size_t)config().fusion_pipeline_bytes.load(), ops, DDL_FLOAT, nullptr, want, sumsq_out, &cuts, prescale,
-            postscale, st.data());
-        if (subplans) *subplans = j;
-        if (ncuts) *ncuts = (int)cuts.size();
-        for (int k = 0; k < max_cuts && k < (int)cuts.size() && cut_segs && cut_elems; ++k) {
-            cut_segs[k] = cuts[k].first;
-            cut_elems[k] = cuts[k].second;
-        }
+        check_float_ops(ops, count, "MIN / MAX take no wire");
+        check_factors(prescale, postscale, count);
+        FusedCall c{nranks, count, srcs, dsts, elements, wire_unit(DDL_BFLOAT16), DDL_BFLOAT16, DDL_FLOAT, hip_stream, subplans};
+        c.ops = ops;
+        c.prescale = prescale, c.postscale = postscale;
+        c.sr_want = sr_want, c.keys = streams;
+        c.want = want, c.sumsq_out = sumsq_out;
+        c.cut_segs = cut_segs, c.cut_elems = cut_elems, c.max_cuts = max_cuts, c.ncuts = ncuts;
+        thread_fused(c);
     });
 }
 

@@ -273,6 +273,50 @@ inline std::vector<size_t> host_chunk_cuts(size_t total, size_t chunk) {
     return cut;
 }
 
+// One segment of one SegmentCopier launch. An option's kernel and table are a launch's only where some
+// non-empty segment of it asks for the option: every other launch is the kernel it was, its tables
+// unchanged, and a segment without the option inside such a launch is moved as it was. A launch ignores
+// what it cannot use: a converting pack `op` and `want`; a scatter `residual` and `stream`; kSumsqInPlace
+// `op` and `scale`; a non-converting launch `residual` and `stream`.
+struct CopySeg {
+    void *ptr = nullptr;  // the tensor side: read by a pack, written by a scatter / in place
+    size_t bytes = 0;     // flat-side bytes (wire bytes for a converting copy: elements x 2)
+    // DDL_ALLREDUCE_OP_AVG with CopyLaunch::divisor > 1 (a float dtype): the scatter stores the quotient of
+    // the segment's elements (k_seg<DivOp> in place of k_seg<CopyOp>), kDivInPlace divides them in place
+    int op = DDL_ALLREDUCE_OP_SUM;
+    // DDL_ALLREDUCE_SCALE (finite and > 0; DDL_FLOAT): dir 0 multiplies the elements on their way into the
+    // flat buffer (the prescale, ahead of the narrowing and the residual's addition), dir 1 and kDivInPlace
+    // on their way into the tensors, behind the widening and AVG's quotient (the postscale); the sum of
+    // squares is of the scaled values
+    float scale = 1.0f;
+    // DDL_ALLREDUCE_WIRE_FEEDBACK (a converting pack): the segment packs narrow(tensor + residual) and leaves
+    // what the rounding removed in `residual` (fp32, the segment's element count; CvtPackOp<WIRE, true>)
+    void *residual = nullptr;
+    // DDL_ALLREDUCE_WIRE_STOCHASTIC (a converting bf16 pack): a segment with stream.on (and no residual) is
+    // narrowed by the rule of ddl_amd.h (k_seg<CvtPackSrOp>)
+    WireStream stream{};
+    // DDL_ALLREDUCE_SUMSQ (DDL_FLOAT; dir 1 / kSumsqInPlace): k_seg_sumsq in place of k_seg stores what k_seg
+    // would and leaves one fp64 partial per 1 KiB tile of the wanted segments (with a wire in the compressed
+    // order: 512 elements per tile, 8 per lane), then the finishing kernel and an async copy of the launch's
+    // values into CopyLaunch::sumsq on its stream. The order of the additions: include/ddl_amd.h.
+    bool want = false;
+};
+struct CopyLaunch {  // what is per launch, not per segment
+    int dir;         // 0 gather, 1 scatter, SegmentCopier::kDivInPlace, SegmentCopier::kSumsqInPlace
+    void *flat;      // unused in place
+    hipStream_t stream;
+    int dtype = 0;  // the tensors' dtype
+    // 0: the plain copies. DDL_HALF / DDL_BFLOAT16: the converting copies of the wire compression
+    // (ddl_allreduce_wire; dir 0, 1, kSumsqInPlace) — the tensors hold DDL_FLOAT, the flat buffer `wire`
+    // elements, so offsets, tiles and flat_bytes are the wire stream's. dir 0: round to nearest even
+    // (k_seg<CvtPackOp>); dir 1: widen, AVG segments divided by (float)divisor (k_seg<CvtUnpackOp>).
+    int wire = 0;
+    int divisor = 1;  // the communicator's size
+    // dir 1 / kSumsqInPlace: `count` doubles of PINNED host memory that stay valid until the work posted has
+    // run; +0.0 at return, then every wanted non-empty segment's value
+    double *sumsq = nullptr;
+};
+
 // Gather (dir 0: segments -> flat) / scatter (dir 1: flat -> segments) between tensors and a
 // fusion buffer in one launch (pack.hip). Segment i sits at the running sum of the 256-byte-
 // rounded lengths before it. Not thread-safe: one copier per engine thread.
@@ -282,63 +326,17 @@ public:
     ~SegmentCopier();
     SegmentCopier(const SegmentCopier &) = delete;
     SegmentCopier &operator=(const SegmentCopier &) = delete;
-    // DDL_ALLREDUCE_OP_AVG (`ops[i]` per segment, `divisor` = the communicator's size, `dtype` a
-    // float type): the scatter (dir 1) stores the quotient of the AVG segments' elements and copies
-    // the others — one launch of k_seg<DivOp> in place of k_seg<CopyOp>; dir kDivInPlace divides the AVG
-    // segments where they are (`flat` unused, the other segments untouched). Without an AVG
-    // segment, or with divisor 1, dir 0 / 1 are the plain copies and kDivInPlace posts nothing.
+    // the AVG segments divided and the scaled ones multiplied where they are (nothing else is touched)
     static constexpr int kDivInPlace = 2;
-    // The sum of squares (DDL_ALLREDUCE_SUMSQ; `want` one byte per segment, null = none;
-    // `sumsq` `count` doubles of PINNED host memory that stay valid until the work posted here has
-    // run): a scatter (dir 1) of DDL_FLOAT segments with want[i] != 0 for some non-empty segment is one
-    // launch of k_seg_sumsq in place of k_seg — it stores what k_seg would and leaves one fp64
-    // partial per 1 KiB tile of the wanted segments — followed by the finishing kernel and an async
-    // copy of the `count` results into `sumsq` on `stream` (+0.0 for unwanted and empty segments).
-    // Every other launch is the kernel it was; its `sumsq` entries are +0.0 at return. The order of
-    // the additions: include/ddl_amd.h. dir kSumsqInPlace: the same reduction, read-only, over
-    // segments that already hold their results (`flat` and `ops` unused; nothing posted if nothing
-    // is wanted).
+    // the sums of squares, read-only, over segments that hold their results (nothing wanted: nothing posted)
     static constexpr int kSumsqInPlace = 3;
-    // The scale factors (DDL_ALLREDUCE_SCALE; `scale` one fp32 factor per segment, finite and > 0,
-    // null = none; DDL_FLOAT segments): a launch in which some non-empty segment has a factor other
-    // than 1 is the scaled kernel of its kind — dir 0 multiplies the elements on their way into the flat
-    // buffer (the prescale), dir 1 and kDivInPlace on their way into the tensors, behind AVG's quotient
-    // (the postscale; kDivInPlace then covers the AVG and the scaled segments), and the sum of squares is
-    // of the scaled values. A segment with factor 1 inside such a launch is moved as the unscaled kernel
-    // moves it; every other launch is the kernel it was. kSumsqInPlace ignores `scale`.
-    void run(int dir, void *flat, void *const *segs, const size_t *bytes, int count, hipStream_t stream,
-             int dtype = 0, int divisor = 1, const int *ops = nullptr, const unsigned char *want = nullptr,
-             double *sumsq = nullptr, const float *scale = nullptr);
-    // The converting copies of the wire compression (ddl_allreduce_wire): the tensors hold `src_dtype`
-    // (DDL_FLOAT) elements, the flat buffer `wire_dtype` (DDL_HALF / DDL_BFLOAT16) ones. `wire_bytes[i]`
-    // = segment i's bytes on the FLAT side (elements x 2), so offsets, tiles and flat_bytes are those
-    // of run() on the wire stream; the tensor side is twice as long. dir 0: round to nearest even
-    // into the flat buffer (k_seg<CvtPackOp>); dir 1: widen, AVG segments divided by (float)divisor
-    // (k_seg<CvtUnpackOp>). `residuals` (dir 0 only; parallel to `segs`, null entries allowed): error
-    // feedback (DDL_ALLREDUCE_WIRE_FEEDBACK) — segment i with residuals[i] != null packs
-    // narrow(tensor + residual) and leaves what the rounding removed in residuals[i] (fp32, the
-    // segment's element count; CvtPackOp<WIRE, true>). With no non-null residual of a non-empty
-    // segment the launch is the feedback-free CvtPackOp<WIRE, false>, unchanged.
-    void run_cvt(int dir, void *flat, void *const *segs, const size_t *wire_bytes, int count, hipStream_t stream,
-                 int src_dtype, int wire_dtype, int divisor = 1, const int *ops = nullptr,
-                 void *const *residuals = nullptr,
-                 // dir 1 / kSumsqInPlace: the sums of squares as in run(), in the compressed order
-                 // (512 elements per tile, 8 per lane)
-                 const unsigned char *want = nullptr, double *sumsq = nullptr,
-                 // dir 0: the prescale ahead of the narrowing (and of the residual's addition); dir 1: the
-                 // postscale behind the widening and the quotient — as in run()
-                 const float *scale = nullptr,
-                 // dir 0, bf16 wire: stochastic rounding (DDL_ALLREDUCE_WIRE_STOCHASTIC) — one WireStream per
-                 // segment; segment i with streams[i].on (and no residual) is narrowed by the rule of ddl_amd.h
-                 // (k_seg<CvtPackSrOp>), every other segment as CvtPackOp<kWireBF16, .> packs it. With no
-                 // stochastic non-empty segment the launch is the converting pack it was, unchanged.
-                 const WireStream *streams = nullptr);
+    // Every refusal comes before anything is posted.
+    void run(const CopyLaunch &how, const CopySeg *segs, int count);
+    // The plain copy of ptrs[i] (bytes[i] each) into or out of `flat`.
+    void copy(int dir, void *flat, void *const *ptrs, const size_t *bytes, int count, hipStream_t stream);
     static size_t flat_bytes(const size_t *bytes, int count);
 
 private:
-    void run_(int dir, void *flat, void *const *segs, const size_t *bytes, int count, hipStream_t stream, int dtype,
-              int divisor, const int *ops, int wire, void *const *residuals, const unsigned char *want, double *sumsq,
-              const float *scale, const WireStream *streams = nullptr);
     struct Slot {
         void *host = nullptr, *dev = nullptr;
         size_t cap = 0;
@@ -351,6 +349,7 @@ private:
     Slot &free_slot_();  // a slot whose last table copy has been consumed (grows the pool)
     static constexpr size_t kMaxSlots = 64;
     std::vector<Slot> slots_;
+    std::vector<CopySeg> plain_;  // copy()'s segments, kept between calls
     size_t next_ = 0;
 };
 

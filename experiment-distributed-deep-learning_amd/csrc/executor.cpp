@@ -258,8 +258,8 @@ void RingExecutor::allreduce(const void *in, void *out, size_t n, int dtype, hip
     build_program(prog_, rank_, size_, in, out, staging, n, dtype, cfg);
     run_(dtype, user, reduce_kind(op));
     if (avg) {
-        const size_t bytes = n * es;
-        divider_.run(SegmentCopier::kDivInPlace, nullptr, &out, &bytes, 1, user, dtype, size_, &op);
+        const CopySeg seg{out, n * es, op};
+        divider_.run(CopyLaunch{SegmentCopier::kDivInPlace, nullptr, user, dtype, 0, size_}, &seg, 1);
     }
 }
 
@@ -281,10 +281,9 @@ void RingExecutor::allreduce_batch(const void *const *in, void *const *out, cons
     build_batch_program(prog_, rank_, size_, in, out, n, count, staging, dtype, cfg);
     run_(dtype, user, reduce_kind(op));
     if (avg && count > 0) {  // one launch over every bucket's result
-        std::vector<size_t> bytes(count);
-        for (int b = 0; b < count; ++b) bytes[b] = n[b] * es;
-        const std::vector<int> ops(count, op);
-        divider_.run(SegmentCopier::kDivInPlace, nullptr, out, bytes.data(), count, user, dtype, size_, ops.data());
+        std::vector<CopySeg> segs(count);
+        for (int b = 0; b < count; ++b) segs[b] = CopySeg{out[b], n[b] * es, op};
+        divider_.run(CopyLaunch{SegmentCopier::kDivInPlace, nullptr, user, dtype, 0, size_}, segs.data(), count);
     }
 }
 

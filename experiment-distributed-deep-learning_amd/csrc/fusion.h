@@ -27,14 +27,38 @@
 
 namespace ddl {
 
-// The sums of squares of a plan's results (DDL_ALLREDUCE_SUMSQ). A segment is cut into pieces by
-// the sub-plans (tiles restart at every piece); every piece's value — the canonical sum of
-// include/ddl_amd.h over the piece — lands in pinned host memory by an async copy behind the unpack
-// that computed it, on that unpack's stream. The segment's value is its pieces' values added in
-// increasing offset, starting from the first piece's: `pieces` lists them in that order per segment,
-// readable once the plan's work has run.
+// One segment of a fusion plan: src -> dst through the pack, the allreduce and the unpack. The options are
+// the copier's (common.h CopySeg); cuts and allreduces depend on the bytes alone.
+struct PlanSeg {
+    const void *src; void *dst; size_t bytes;  // bytes on the wire side
+    // AVG: the unpack stores quotients. (A MIN / MAX plan holds that one kind: `ar` reduces with it, the unpack copies.)
+    int op = DDL_ALLREDUCE_OP_SUM;
+    float prescale = 1.0f, postscale = 1.0f;  // every piece is packed with the one, unpacked with the other
+    void *residual = nullptr;  // error feedback (a compressed plan): an fp32 array indexed like the tensor
+    WireStream stream{};  // stochastic rounding (a compressed bf16 plan); `first`: the first element's index in its request
+    bool want = false;  // the sum of squares of the result (PlanSumsq)
+    // `len` wire bytes at wire offset `off` (es / ses: the wire's / the tensors' element size): src, dst, residual, stream there
+    PlanSeg piece(size_t off, size_t len, size_t es, size_t ses) const;
+    CopySeg pack() const { return CopySeg{const_cast<void *>(src), bytes, DDL_ALLREDUCE_OP_SUM, prescale, residual, stream, false}; }
+    CopySeg unpack() const { return CopySeg{dst, bytes, op, postscale, nullptr, WireStream{}, want}; }
+};
+
+// A plan above `cap` bytes (a non-zero multiple of 256) as sub-plans of at most that size: a piece fills its
+// sub-plan up to cap, so every cut is a multiple of 256 bytes from the segment start. seg[k], elem[k]: piece k's
+// segment and first element in it; flat: the sub-plan's fusion-buffer bytes. No HIP call (fusion_cuts.cpp).
+struct SubPlan {
+    std::vector<PlanSeg> segs;
+    std::vector<size_t> seg, elem;
+    size_t flat = 0;
+};
+std::vector<SubPlan> cut_plan(const std::vector<PlanSeg> &segs, size_t cap, size_t es, size_t ses);
+
+// The sums of squares of a plan's wanted segments. A segment is cut into pieces by the sub-plans (tiles restart
+// at every piece); every piece's value — the canonical sum of include/ddl_amd.h over the piece — lands in pinned
+// host memory by an async copy behind the unpack that computed it, on that unpack's stream. The segment's value is
+// its pieces' values added in increasing offset, starting from the first piece's: `pieces` lists them in that
+// order per segment, readable once the plan's work has run.
 struct PlanSumsq {
-    const unsigned char *want = nullptr;     // one per segment: 0 = not wanted
     std::function<double *(size_t)> pinned;  // n doubles of pinned host memory that outlive the plan's work
     struct Piece {
         size_t seg, elem;     // the segment and the piece's first element in it
@@ -50,44 +74,19 @@ public:
     FusionPipe(const FusionPipe &) = delete;
     FusionPipe &operator=(const FusionPipe &) = delete;
 
-    // Fusion buffer i (0 or 1) of at least `need` bytes; an outgrown buffer is retired, not freed
-    // (common.h retire_device): earlier uses of it may still be in flight.
+    // Fusion buffer i (0 or 1) of at least `need` bytes; an outgrown buffer is retired, not freed (common.h
+    // retire_device): earlier uses of it may still be in flight.
     void *ensure(int i, size_t need, hipStream_t stream);
     // elems of the plan's dtype in `buf`, reduced in place on the pipe's stream; `message_bytes`
     // = the whole plan's unpadded bytes (the reference's MPI_Allreduce message)
     using Allreduce = std::function<void(void *buf, size_t elems, size_t message_bytes)>;
-    // pack -> allreduce -> unpack of srcs[i] -> dsts[i] (bytes[i] each) on `stream`, pipelined in
-    // sub-plans above `cap` bytes (0: never). `ops` (one ddl_allreduce_op per segment, or null =
-    // all SUM) with `divisor` = the communicator's size: the unpack of every (sub-)plan holding an
-    // AVG segment is the dividing unpack (pack.hip k_seg<DivOp>), which stores the quotients of those
-    // segments; the cuts, the packs and the allreduces do not depend on the ops. (A MIN / MAX plan
-    // holds one kind only; its caller's `ar` reduces with that kind and the unpack copies.)
-    // `src_dtype` != 0 and != dtype (DDL_FLOAT over a 16-bit `dtype`: wire compression): the tensors
-    // hold src_dtype elements, `bytes`, `cap`, the cuts and the allreduce are those of the WIRE stream
-    // in `dtype` (a tensor's offset at a cut is the wire offset scaled by the element sizes), and
-    // the pack / unpack are the converting kernels (SegmentCopier::run_cvt).
-    // `residuals` (a compressed plan only; one per segment, null entries = no feedback): the error
-    // feedback residuals of DDL_ALLREDUCE_WIRE_FEEDBACK, fp32 arrays indexed like the tensors — a
-    // sub-plan's piece takes its residual at the tensor's own element offset. The pack adds them in
-    // and rewrites them (k_seg<CvtPackOp<WIRE, true>>); cuts, allreduces and unpacks do not depend on them.
-    // `sumsq` (fp32 tensors only; null or no wanted segment: every launch as without it): the unpack of
-    // every (sub-)plan holding a wanted piece is k_seg_sumsq (pack.hip); cuts, packs and allreduces do
-    // not depend on it.
-    void run(const std::vector<const void *> &srcs, const std::vector<void *> &dsts,
-             const std::vector<size_t> &bytes, int dtype, size_t cap, hipStream_t stream, const Allreduce &ar,
-             const std::vector<int> *ops = nullptr, int divisor = 1, int src_dtype = 0,
-             const std::vector<void *> *residuals = nullptr, PlanSumsq *sumsq = nullptr,
-             // the scale factors (DDL_ALLREDUCE_SCALE; fp32 tensors only), one per segment, null = none: every
-             // piece of a segment is packed with the segment's prescale and unpacked with its postscale
-             // (SegmentCopier::run: a launch without a factor other than 1 is the kernel it was); cuts and
-             // allreduces do not depend on them
-             const std::vector<float> *prescale = nullptr, const std::vector<float> *postscale = nullptr,
-             // stochastic rounding (DDL_ALLREDUCE_WIRE_STOCHASTIC; a compressed bf16 plan), one
-             // WireStream per segment, null = none: `first` is the index in its request of the segment's first
-             // element, and a sub-plan's piece starts where it is cut, so every element keeps the random bits of
-             // its index in the request whatever the cuts; a launch without a stochastic segment is the pack it
-             // was; cuts, allreduces and unpacks do not depend on them
-             const std::vector<WireStream> *streams = nullptr);
+    // pack -> allreduce -> unpack of the segments on `stream`, pipelined in sub-plans above `cap` bytes (0: never; an
+    // uncut plan is run from the caller's vector). `divisor`: the communicator's size. `src_dtype` != 0 and != dtype
+    // (DDL_FLOAT over a 16-bit `dtype`: wire compression): the tensors hold src_dtype elements; bytes, `cap`, the cuts
+    // and the allreduce are those of the WIRE stream in `dtype`, and the pack / unpack are the converting kernels.
+    // `sumsq`: where the wanted segments' values go (null: nothing is wanted).
+    void run(const std::vector<PlanSeg> &segs, int dtype, int src_dtype, size_t cap, int divisor, hipStream_t stream,
+             const Allreduce &ar, PlanSumsq *sumsq = nullptr);
     size_t subplans() const { return last_subplans_; }  // of the last run
 
     SegmentCopier copier;
@@ -100,6 +99,7 @@ private:
     size_t cap_[2] = {0, 0};
     hipStream_t side_ = nullptr;
     std::vector<hipEvent_t> events_;
+    std::vector<CopySeg> launch_;  // the segments of the launch being posted, kept between launches
     size_t last_subplans_ = 0;
 };
 

@@ -547,15 +547,16 @@ double *RequestHandler::stat_take_(size_t n) {
 }
 
 void RequestHandler::stat_in_place_(size_t req, void *out, size_t bytes) {
-    const unsigned char want = 1;
     double *sq = stat_take_(1);
-    fp_.copier.run(SegmentCopier::kSumsqInPlace, nullptr, &out, &bytes, 1, stream_, DDL_FLOAT, 1, nullptr, &want, sq);
+    CopySeg seg{out, bytes};
+    seg.want = true;
+    fp_.copier.run(CopyLaunch{SegmentCopier::kSumsqInPlace, nullptr, stream_, DDL_FLOAT, 0, 1, sq}, &seg, 1);
     round_stat_.emplace_back(req, sq);
 }
 
 void RequestHandler::scale_in_place_(void *out, size_t bytes, int op, int divisor, float factor) {
-    fp_.copier.run(SegmentCopier::kDivInPlace, nullptr, &out, &bytes, 1, stream_, DDL_FLOAT, divisor, &op, nullptr, nullptr,
-                   &factor);
+    const CopySeg seg{out, bytes, op, factor};
+    fp_.copier.run(CopyLaunch{SegmentCopier::kDivInPlace, nullptr, stream_, DDL_FLOAT, 0, divisor}, &seg, 1);
 }
 
 std::unique_lock<std::mutex> RequestHandler::lock_host_group_(const std::vector<Request> &reqs,
@@ -617,31 +618,20 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
             esz.push_back(es);
         }
         const std::unique_lock<std::mutex> rg = lock_host_group_(reqs, g.second, es, host);
-        // error feedback (Request::feedback, rank-local like the op): the residual of every request
-        // of a compressed group that asks for it, found or made once per round; none where the
-        // one-rank shortcut skips the data plane
-        std::vector<void *> resid;
-        if (comp && !(data_->size() == 1 && config().one_rank_shortcut.load())) {
-            bool any = false;
-            for (size_t i : g.second) any = any || reqs[i].feedback;
-            if (any) {
-                resid.assign(g.second.size(), nullptr);
-                for (size_t q = 0; q < g.second.size(); ++q)
-                    if (reqs[g.second[q]].feedback) resid[q] = residual_(reqs[g.second[q]]);
-            }
-        }
-        // stochastic rounding (Request::stochastic, rank-local too): the stream key of every request of a
-        // compressed group that asks for it, once per round, so all plans and pieces of a request share it;
-        // none (and no sequence number spent) where the one-rank shortcut skips the data plane
-        std::vector<WireStream> stoch;
-        if (comp && !(data_->size() == 1 && config().one_rank_shortcut.load())) {
-            bool any = false;
-            for (size_t i : g.second) any = any || reqs[i].stochastic;
-            if (any) {
-                stoch.assign(g.second.size(), WireStream{});
-                for (size_t q = 0; q < g.second.size(); ++q)
-                    if (reqs[g.second[q]].stochastic) stoch[q] = WireStream{stochastic_stream_(reqs[g.second[q]]), 0, 1};
-            }
+        // the group's requests as fusion segments (wire bytes), with what is rank-local like the op: the
+        // factors, the sum of squares (taken by the unpack), and in a compressed group the residual of
+        // error feedback (Request::feedback) and the stream key of stochastic rounding
+        // (Request::stochastic) — found or made once per round, so all plans and pieces of a request share
+        // them; none (and no sequence number spent) where the one-rank shortcut skips the data plane
+        const bool fused = !host && !(data_->size() == 1 && config().one_rank_shortcut.load()), wire_opts = comp && fused;
+        std::vector<PlanSeg> whole;
+        whole.reserve(fused ? g.second.size() : 0);
+        for (size_t q = 0; fused && q < g.second.size(); ++q) {
+            const Request &r = reqs[g.second[q]];
+            whole.push_back(PlanSeg{r.in, r.out, r.n * es, r.op, r.prescale, r.postscale});
+            whole.back().want = r.sumsq != nullptr;
+            if (wire_opts && r.feedback) whole.back().residual = residual_(r);
+            if (wire_opts && r.stochastic) whole.back().stream = WireStream{stochastic_stream_(r), 0, 1};
         }
         for (const Plan &p : make_plans(elems, esz, (size_t)config().fusion_threshold_bytes.load())) {
             for (size_t q = p.req_begin; q <= p.req_end; ++q) wait_inputs_(reqs[g.second[q]], waited);
@@ -716,55 +706,28 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
                 // no unpack to take it from: one read-only pass over the finished slice
                 if (r.sumsq && cnt) stat_in_place_(g.second[p.req_begin], static_cast<char *>(r.out) + p.elem_begin * es, cnt * es);
             } else {
-                std::vector<const void *> srcs;
-                std::vector<void *> dsts;
-                std::vector<size_t> bytes;
                 // a compressed plan always comes here, also with one request: the conversion is
-                // the pack's and the unpack's, so the in-place direct path cannot apply
-                plan_slices(p, reqs, g.second, ses, [&](const char *s, char *d, size_t n) {
-                    srcs.push_back(s);
-                    dsts.push_back(d);
-                    bytes.push_back(n / ses * es);  // on the wire
-                });
-                const std::vector<int> ops = plan_ops(p, reqs, g.second);  // AVG segments leave as quotients
-                // the plan's slices of the residuals, at the tensors' own element offsets. A plan
-                // that fails after its pack has already updated them: that is not undone.
-                std::vector<void *> res;
-                for (size_t q = p.req_begin; q <= p.req_end && !resid.empty(); ++q)
-                    res.push_back(resid[q] ? static_cast<char *>(resid[q]) + (q == p.req_begin ? p.elem_begin : 0) * ses
-                                           : nullptr);
-                // the plan's slices of the stochastic streams: the same S, the slice's first element index.
-                // A plan that fails has already spent its requests' sequence numbers: that is not undone.
-                std::vector<WireStream> sts;
-                bool any_sts = false;
-                for (size_t q = p.req_begin; q <= p.req_end && !stoch.empty(); ++q) {
-                    sts.push_back(WireStream{stoch[q].key, q == p.req_begin ? p.elem_begin : 0, stoch[q].on});
-                    any_sts = any_sts || stoch[q].on;
+                // the pack's and the unpack's, so the in-place direct path cannot apply.
+                // The plan's slices of the requests: tensors, residuals and streams at the slice's first
+                // element. A plan that fails after its pack has updated the residuals or has spent its
+                // requests' sequence numbers: that is not undone.
+                // (a plan of the whole group, the usual one, is run from the group's vector)
+                const bool all = p.req_begin == 0 && p.elem_begin == 0 && p.req_end + 1 == whole.size() &&
+                                 p.elem_end == reqs[g.second[p.req_end]].n;
+                std::vector<PlanSeg> slices;
+                slices.reserve(all ? 0 : p.req_end - p.req_begin + 1);
+                for (size_t q = p.req_begin; q <= p.req_end && !all; ++q) {
+                    const size_t b = q == p.req_begin ? p.elem_begin : 0, e = q == p.req_end ? p.elem_end : reqs[g.second[q]].n;
+                    slices.push_back(whole[q].piece(b * es, (e - b) * es, es, ses));
                 }
-                // the sums of squares (Request::sumsq, rank-local like the op): taken by the unpack
-                std::vector<unsigned char> want;
+                const std::vector<PlanSeg> &segs = all ? whole : slices;
                 PlanSumsq ps;
-                for (size_t q = p.req_begin; q <= p.req_end; ++q) want.push_back(reqs[g.second[q]].sumsq ? 1 : 0);
-                const bool stat = std::find(want.begin(), want.end(), 1) != want.end();
-                if (stat) {
-                    ps.want = want.data();
-                    ps.pinned = [this](size_t n) { return stat_take_(n); };
-                }
-                // the scale factors (Request::prescale / postscale, rank-local too): the pack's and the unpack's
-                std::vector<float> pre, post;
-                bool any_pre = false, any_post = false;
-                for (size_t q = p.req_begin; q <= p.req_end; ++q) {
-                    pre.push_back(reqs[g.second[q]].prescale);
-                    post.push_back(reqs[g.second[q]].postscale);
-                    any_pre = any_pre || pre.back() != 1.0f;
-                    any_post = any_post || post.back() != 1.0f;
-                }
-                fp_.run(srcs, dsts, bytes, dt, (size_t)config().fusion_pipeline_bytes.load(), stream_,
+                ps.pinned = [this](size_t n) { return stat_take_(n); };
+                fp_.run(segs, dt, sdt, (size_t)config().fusion_pipeline_bytes.load(), data_->size(), stream_,
                         [&](void *buf, size_t elems, size_t message) {
                             data_->allreduce(buf, buf, elems, dt, kind, stream_, message);
                         },
-                        &ops, data_->size(), sdt, resid.empty() ? nullptr : &res, stat ? &ps : nullptr,
-                        any_pre ? &pre : nullptr, any_post ? &post : nullptr, any_sts ? &sts : nullptr);
+                        &ps);
                 for (const PlanSumsq::Piece &pc : ps.pieces) round_stat_.emplace_back(g.second[p.req_begin + pc.seg], pc.value);
             }
             finish_plan_(p, reqs, g.second, dones, nplans);
@@ -822,10 +785,10 @@ void RequestHandler::broadcast_reqs_(std::vector<Request> &reqs, std::vector<Don
                 const size_t total = SegmentCopier::flat_bytes(bytes.data(), (int)bytes.size());
                 void *fb = fp_.ensure(0, total, stream_);
                 if (me == root)
-                    fp_.copier.run(0, fb, const_cast<void *const *>(srcs.data()), bytes.data(), (int)srcs.size(),
-                                   stream_);
+                    fp_.copier.copy(0, fb, const_cast<void *const *>(srcs.data()), bytes.data(), (int)srcs.size(),
+                                    stream_);
                 data_->broadcast(fb, total / es, dt, root, stream_);
-                fp_.copier.run(1, fb, dsts.data(), bytes.data(), (int)dsts.size(), stream_);
+                fp_.copier.copy(1, fb, dsts.data(), bytes.data(), (int)dsts.size(), stream_);
             }
             finish_plan_(p, reqs, g.second, dones, nplans);
         }
@@ -940,8 +903,8 @@ void RequestHandler::allgather_reqs_(std::vector<Request> &reqs, std::vector<Don
                 ensure_(gather_, gather_bytes_, all);
                 std::vector<const void *> srcs(m);
                 for (size_t j = 0; j < m; ++j) srcs[j] = reqs[g.second[j]].in;
-                fp_.copier.run(0, fb, const_cast<void *const *>(srcs.data()), seg_bytes.data() + me * m, (int)m,
-                               stream_);
+                fp_.copier.copy(0, fb, const_cast<void *const *>(srcs.data()), seg_bytes.data() + me * m, (int)m,
+                                stream_);
                 data_->allgatherv(fb, gather_, cnt.data(), dsp.data(), dt, stream_);
                 std::vector<void *> dsts(P * m);
                 std::vector<size_t> row_off(m, 0);  // rows of request j written so far
@@ -951,7 +914,7 @@ void RequestHandler::allgather_reqs_(std::vector<Request> &reqs, std::vector<Don
                         dsts[q * m + j] = static_cast<char *>(r.out) + row_off[j] * r.row_elems * es;
                         row_off[j] += fd[q * m + j];
                     }
-                fp_.copier.run(1, gather_, dsts.data(), seg_bytes.data(), (int)(P * m), stream_);
+                fp_.copier.copy(1, gather_, dsts.data(), seg_bytes.data(), (int)(P * m), stream_);
             }
         }
         const size_t plan = record_plan_(nplans);

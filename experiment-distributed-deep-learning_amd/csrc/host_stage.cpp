@@ -195,7 +195,6 @@ void HostStager::run(const std::vector<HostSeg> &segs, size_t es, bool upload,
     bool avg = false;
     if (divisor > 1)
         for (const HostSeg &sg : segs) avg = avg || (sg.op == DDL_ALLREDUCE_OP_AVG && sg.bytes);
-    std::vector<int> ops;  // of the pieces handed to the dividing kernel
     std::vector<size_t> starts;
     const size_t total = seg_starts(segs, padded || device_unpack, starts);
     if (total == 0) return;
@@ -249,8 +248,7 @@ void HostStager::run(const std::vector<HostSeg> &segs, size_t es, bool upload,
         lane_->wait(unpacked[j]);
         config().host_unpack_ns.fetch_add(ns_since(t0));
     };
-    std::vector<void *> dst;
-    std::vector<size_t> len;
+    std::vector<CopySeg> dst;  // the pieces handed to the copier
     // no unpack job may outlive the plan: if posting throws midway (a collective, a
     // HIP call, a failed unpack), the lane finishes the jobs already submitted — they write into
     // the requests' outputs — before the error reaches complete_() and done(), after which the
@@ -287,17 +285,14 @@ void HostStager::run(const std::vector<HostSeg> &segs, size_t es, bool upload,
             if (avg && !device_unpack) {
                 // staged outputs: the AVG slices of this chunk become their quotients in the slot
                 dst.clear();
-                len.clear();
                 for (size_t j = (size_t)(std::upper_bound(starts.begin(), starts.end(), off) - starts.begin()) - 1;
                      j < segs.size() && starts[j] < off + n; ++j) {
                     const size_t lo = std::max(off, starts[j]), hi = std::min(off + n, starts[j] + segs[j].bytes);
                     if (hi <= lo || segs[j].op != DDL_ALLREDUCE_OP_AVG) continue;
-                    dst.push_back(static_cast<char *>(dslot_[k]) + (lo - off));
-                    len.push_back(hi - lo);
+                    dst.push_back(CopySeg{static_cast<char *>(dslot_[k]) + (lo - off), hi - lo, DDL_ALLREDUCE_OP_AVG});
                 }
-                ops.assign(dst.size(), DDL_ALLREDUCE_OP_AVG);
-                copier_.run(SegmentCopier::kDivInPlace, nullptr, dst.data(), len.data(), (int)dst.size(), stream_, dtype,
-                            divisor, ops.data());
+                copier_.run(CopyLaunch{SegmentCopier::kDivInPlace, nullptr, stream_, dtype, 0, divisor}, dst.data(),
+                            (int)dst.size());
             }
             config().host_coll_ns.fetch_add(ns_since(t_coll));
             DDL_HIP(hipEventRecord(hev_[3 * k + 1], stream_));
@@ -308,21 +303,16 @@ void HostStager::run(const std::vector<HostSeg> &segs, size_t es, bool upload,
                 // offset in the padded stream (chunks start at multiples of 256, so a cut never
                 // falls inside a segment's padding)
                 dst.clear();
-                len.clear();
-                ops.clear();
                 size_t flat = 0;
                 for (size_t j = (size_t)(std::upper_bound(starts.begin(), starts.end(), off) - starts.begin()) - 1;
                      j < segs.size() && starts[j] < off + n; ++j) {
                     const size_t lo = std::max(off, starts[j]), hi = std::min(off + n, starts[j] + segs[j].bytes);
                     if (hi <= lo) continue;
                     DDL_REQUIRE(flat == lo - off, DDL_STATUS_ERROR_UNKNOWN, "device-unpack chunk layout");
-                    dst.push_back(segs[j].ddst + (lo - starts[j]));  // the device's address of the output
-                    len.push_back(hi - lo);
-                    if (avg) ops.push_back(segs[j].op);
+                    dst.push_back(CopySeg{segs[j].ddst + (lo - starts[j]), hi - lo, segs[j].op});  // the device's address of the output
                     flat += round256(hi - lo);
                 }
-                copier_.run(1, dslot_[k], dst.data(), len.data(), (int)dst.size(), d2h_, dtype, divisor,
-                            avg ? ops.data() : nullptr);
+                copier_.run(CopyLaunch{1, dslot_[k], d2h_, dtype, 0, divisor}, dst.data(), (int)dst.size());
             } else {
                 if (i >= (size_t)kHostSlots) wait_unpack(i - kHostSlots);  // download slot k free again
                 const clk::time_point t_post = clk::now();

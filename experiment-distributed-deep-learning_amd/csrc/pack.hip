@@ -753,17 +753,17 @@ template <class F> void with_bool(bool b, F f) {
     if (b) f(std::true_type{});
     else f(std::false_type{});
 }
-template <class F> void with_wire(int wire, F f) {  // of the converting copies: float16, else bfloat16 (run_cvt)
+template <class F> void with_wire(int wire, F f) {  // of the converting copies: float16, else bfloat16 (CopyLaunch::wire)
     if (wire == DDL_HALF) f(std::integral_constant<int, kWireF16>{});
     else f(std::integral_constant<int, kWireBF16>{});
 }
 
 // fp32 tensors: every segment whole elements (`unit` bytes each in `bytes`: 4, or 2 for wire-side
-// lengths) at a 4-byte aligned address. Null tables are run_'s to report.
-void require_f32_segments(void *const *segs, const size_t *bytes, int count, size_t unit) {
-    for (int i = 0; i < count && segs && bytes; ++i)
-        DDL_REQUIRE(bytes[i] % unit == 0 && reinterpret_cast<uintptr_t>(segs[i]) % 4 == 0, DDL_STATUS_INVALID_ARGUMENT,
-                    "segment " << i << " is not whole, aligned float32 elements");
+// lengths) at a 4-byte aligned address.
+void require_f32_segments(const CopySeg *segs, int count, size_t unit) {
+    for (int i = 0; i < count; ++i)
+        DDL_REQUIRE(segs[i].bytes % unit == 0 && reinterpret_cast<uintptr_t>(segs[i].ptr) % 4 == 0,
+                    DDL_STATUS_INVALID_ARGUMENT, "segment " << i << " is not whole, aligned float32 elements");
 }
 
 }  // namespace
@@ -811,93 +811,82 @@ size_t SegmentCopier::flat_bytes(const size_t *bytes, int count) {
     return off;
 }
 
-void SegmentCopier::run(int dir, void *flat, void *const *segs, const size_t *bytes, int count,
-                        hipStream_t stream, int dtype, int divisor, const int *ops, const unsigned char *want,
-                        double *sumsq, const float *scale) {
-    run_(dir, flat, segs, bytes, count, stream, dtype, divisor, ops, 0, nullptr, want, sumsq, scale);
+void SegmentCopier::copy(int dir, void *flat, void *const *ptrs, const size_t *bytes, int count, hipStream_t stream) {
+    const bool tables = count > 0 && ptrs && bytes;  // null tables are run's to report
+    plain_.resize(tables ? (size_t)count : 0);       // the other fields keep their defaults
+    for (size_t i = 0; i < plain_.size(); ++i) plain_[i].ptr = ptrs[i], plain_[i].bytes = bytes[i];
+    run(CopyLaunch{dir, flat, stream}, tables ? plain_.data() : nullptr, count);
 }
 
-void SegmentCopier::run_cvt(int dir, void *flat, void *const *segs, const size_t *wire_bytes, int count,
-                            hipStream_t stream, int src_dtype, int wire_dtype, int divisor, const int *ops,
-                            void *const *residuals, const unsigned char *want, double *sumsq, const float *scale,
-                            const WireStream *streams) {
-    DDL_REQUIRE(src_dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
-                "wire compression is defined for float32 sources, not " << dtype_name(src_dtype));
-    DDL_REQUIRE(wire_dtype == DDL_HALF || wire_dtype == DDL_BFLOAT16, DDL_STATUS_UNSUPPORTED_DTYPE,
-                "wire dtype " << wire_dtype << " is neither float16 nor bfloat16");
-    DDL_REQUIRE(dir == 0 || dir == 1 || dir == kSumsqInPlace, DDL_STATUS_INVALID_ARGUMENT, "copier direction " << dir);
-    DDL_REQUIRE(divisor >= 1, DDL_STATUS_INVALID_ARGUMENT, "divisor " << divisor);
-    require_f32_segments(segs, wire_bytes, count, 2);
-    // error feedback only where some non-empty segment of a pack has a residual: every other launch
-    // is the plain converting copy, its kernel and tables exactly as before
-    bool fb = false;
-    for (int i = 0; i < count && residuals && wire_bytes && dir == 0; ++i) {
-        if (!residuals[i] || !wire_bytes[i]) continue;
-        DDL_REQUIRE(reinterpret_cast<uintptr_t>(residuals[i]) % 4 == 0, DDL_STATUS_INVALID_ARGUMENT,
-                    "residual " << i << " is not aligned float32 elements");
-        fb = true;
+void SegmentCopier::run(const CopyLaunch &how, const CopySeg *segs, int count) {
+    const int dir = how.dir, dtype = how.dtype, wire = how.wire, divisor = how.divisor;
+    void *flat = how.flat;
+    const hipStream_t stream = how.stream;
+    const int n = segs ? count : 0;  // a null table is reported below, behind the launch's own refusals
+    // What the non-empty segments ask for, in one pass. An option's kernel, table and checks come only
+    // with a segment that asks for it: every other launch is the kernel it was, its tables exactly as before.
+    bool fbk = false, srk = false, sc = false, stat = false, div = false, wanted = false;
+    int bad_scale = -1;  // the first factor that is not finite and positive: refused below, in its turn
+    const uint64_t seg_tile = kSegTile;  // segment-aligned tiles of kSegTile bytes per workgroup
+    uint64_t tiles = 0;
+    const bool plain = segs == plain_.data();  // copy()'s own segments: every option at its default
+    for (int i = 0; i < n; ++i) {
+        const CopySeg &sg = segs[i];
+        wanted |= sg.want;
+        if (!sg.bytes) continue;
+        tiles += (sg.bytes + seg_tile - 1) / seg_tile;
+        if (plain) continue;
+        fbk |= sg.residual != nullptr;
+        srk |= sg.stream.on != 0;
+        stat |= sg.want;
+        div |= sg.op == DDL_ALLREDUCE_OP_AVG;
+        if (sg.scale == 1.0f) continue;
+        sc = true;
+        if (bad_scale < 0 && !(std::isfinite(sg.scale) && sg.scale > 0.0f)) bad_scale = i;
     }
-    // stochastic rounding only where some non-empty segment of a pack asks for it: every other launch
-    // is the converting pack it was, its kernel and tables exactly as before
-    bool sr = false;
-    for (int i = 0; i < count && streams && wire_bytes && dir == 0; ++i) sr = sr || (streams[i].on && wire_bytes[i]);
-    DDL_REQUIRE(!sr || wire_dtype == DDL_BFLOAT16, DDL_STATUS_INVALID_ARGUMENT,
-                "stochastic rounding is defined for the bfloat16 wire");
-    for (int i = 0; i < count && sr && fb; ++i)
-        DDL_REQUIRE(!(streams[i].on && residuals[i]), DDL_STATUS_INVALID_ARGUMENT,
-                    "segment " << i << " asks for error feedback and stochastic rounding");
-    run_(dir, flat, segs, wire_bytes, count, stream, src_dtype, divisor, dir == 1 ? ops : nullptr, wire_dtype,
-         fb ? residuals : nullptr, dir == 0 ? nullptr : want, sumsq, scale, sr ? streams : nullptr);
-}
-
-// wire == 0: the plain copies and the dividing scatter over `bytes` of `dtype`; else the converting
-// copies, `bytes` the wire-side lengths; `residuals` (a converting pack only): the feedback pack;
-// `want` / `sumsq` (a scatter or kSumsqInPlace): the sums of squares (common.h); `scale`: the factors
-// (a pack's prescale, a scatter's or kDivInPlace's postscale)
-void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *bytes, int count, hipStream_t stream,
-                         int dtype, int divisor, const int *ops, int wire, void *const *residuals,
-                         const unsigned char *want, double *sumsq, const float *scale, const WireStream *streams) {
+    fbk = fbk && wire && dir == 0;  // a converting pack's
+    srk = srk && wire && dir == 0;
+    sc = sc && (dir == 0 || dir == 1 || dir == kDivInPlace);
+    stat = stat && (dir == 1 || dir == kSumsqInPlace);
+    // the quotient where it is not the identity (kSumsqInPlace: the segments hold their results, nothing is
+    // divided; a converting pack has no ops)
+    div = div && divisor > 1 && (wire ? dir == 1 : dir != kSumsqInPlace);
+    if (wire) {
+        DDL_REQUIRE(dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
+                    "wire compression is defined for float32 sources, not " << dtype_name(dtype));
+        DDL_REQUIRE(wire == DDL_HALF || wire == DDL_BFLOAT16, DDL_STATUS_UNSUPPORTED_DTYPE,
+                    "wire dtype " << wire << " is neither float16 nor bfloat16");
+        DDL_REQUIRE(dir == 0 || dir == 1 || dir == kSumsqInPlace, DDL_STATUS_INVALID_ARGUMENT, "copier direction " << dir);
+        DDL_REQUIRE(divisor >= 1, DDL_STATUS_INVALID_ARGUMENT, "divisor " << divisor);
+        require_f32_segments(segs, n, 2);
+        for (int i = 0; i < n && fbk; ++i)
+            DDL_REQUIRE(!segs[i].bytes || reinterpret_cast<uintptr_t>(segs[i].residual) % 4 == 0, DDL_STATUS_INVALID_ARGUMENT,
+                        "residual " << i << " is not aligned float32 elements");
+        DDL_REQUIRE(!srk || wire == DDL_BFLOAT16, DDL_STATUS_INVALID_ARGUMENT,
+                    "stochastic rounding is defined for the bfloat16 wire");
+        for (int i = 0; i < n && srk && fbk; ++i)
+            DDL_REQUIRE(!(segs[i].stream.on && segs[i].residual), DDL_STATUS_INVALID_ARGUMENT,
+                        "segment " << i << " asks for error feedback and stochastic rounding");
+    }
     if (count <= 0) return;
-    // a scaled kernel only where some non-empty segment has a factor other than 1: every other launch
-    // is the kernel it was, its tables exactly as before
-    bool sc = false;
-    if (scale && bytes && (dir == 0 || dir == 1 || dir == kDivInPlace)) {
-        for (int i = 0; i < count; ++i) {
-            if (!bytes[i] || scale[i] == 1.0f) continue;
-            DDL_REQUIRE(std::isfinite(scale[i]) && scale[i] > 0.0f, DDL_STATUS_INVALID_ARGUMENT,
-                        "scale factor " << scale[i] << " of segment " << i << " is not finite and positive");
-            sc = true;
-        }
-    }
     if (sc) {
+        DDL_REQUIRE(bad_scale < 0, DDL_STATUS_INVALID_ARGUMENT,
+                    "scale factor " << segs[bad_scale].scale << " of segment " << bad_scale << " is not finite and positive");
         DDL_REQUIRE(dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
                     "scale factors are defined for float32 tensors, not " << dtype_name(dtype));
-        require_f32_segments(segs, bytes, count, wire ? 2 : 4);
+        require_f32_segments(segs, n, wire ? 2 : 4);
     }
-    // the statistic only where some non-empty segment of a scatter asks for it: every other launch
-    // is the kernel it was, its tables exactly as before
-    bool stat = false;
-    if (want && bytes && (dir == 1 || dir == kSumsqInPlace)) {
-        DDL_REQUIRE(sumsq, DDL_STATUS_INVALID_ARGUMENT, "sum of squares without an output");
-        for (int i = 0; i < count; ++i) {
-            sumsq[i] = 0.0;  // a launch that leaves the statistic out, an empty segment (host memory: ours until posted)
-            stat = stat || (want[i] && bytes[i] != 0);
-        }
+    if (dir == 1 || dir == kSumsqInPlace) {
+        DDL_REQUIRE(!wanted || how.sumsq, DDL_STATUS_INVALID_ARGUMENT, "sum of squares without an output");
+        // a launch that leaves the statistic out, an empty segment (host memory: ours until posted)
+        for (int i = 0; i < n && how.sumsq; ++i) how.sumsq[i] = 0.0;
     }
-    if (dir == kSumsqInPlace) {
-        if (!stat) return;  // nothing wanted: the zeros above are the answer
-        ops = nullptr;      // the segments hold their results: nothing is divided
-    }
+    if (dir == kSumsqInPlace && !stat) return;  // nothing wanted: the zeros above are the answer
     if (stat) {
         DDL_REQUIRE(dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
                     "the sum of squares is defined for float32 tensors, not " << dtype_name(dtype));
-        require_f32_segments(segs, bytes, count, wire ? 2 : 4);
+        require_f32_segments(segs, n, wire ? 2 : 4);
     }
-    // the quotient only where some segment asks for it and it is not the identity: every other
-    // launch is the plain copy, its kernels and tables exactly as before
-    bool div = false;
-    if (ops && divisor > 1)
-        for (int i = 0; i < count && !div; ++i) div = ops[i] == DDL_ALLREDUCE_OP_AVG && bytes[i] != 0;
     if (dir == kDivInPlace) {
         if (!div && !sc) return;  // nothing to divide or scale: the segments already hold their results
         flat = nullptr;
@@ -907,34 +896,33 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
         DDL_REQUIRE(dir == 0 || dir == 1, DDL_STATUS_INVALID_ARGUMENT, "copier direction " << dir);
         DDL_REQUIRE(!div || dir == 1, DDL_STATUS_INVALID_ARGUMENT, "the quotient belongs to the unpack");
     }
-    const bool in_place = dir == kDivInPlace || dir == kSumsqInPlace, fbk = wire && dir == 0 && residuals;
-    const bool srk = wire && dir == 0 && streams;  // (run_cvt: bf16 only)
-    DDL_REQUIRE((flat || in_place) && segs && bytes, DDL_STATUS_INVALID_ARGUMENT, "null pack arguments");
+    const bool in_place = dir == kDivInPlace || dir == kSumsqInPlace;
+    DDL_REQUIRE((flat || in_place) && segs, DDL_STATUS_INVALID_ARGUMENT, "null pack arguments");
     const size_t es = div ? dtype_size(dtype) : 1;
     if (div && !sc && !stat && !wire) {  // DivOp over `dtype`
         DDL_REQUIRE(dtype == DDL_FLOAT || dtype == DDL_DOUBLE || dtype == DDL_HALF || dtype == DDL_BFLOAT16,
                     DDL_STATUS_UNSUPPORTED_DTYPE, "AVG is not defined for dtype " << dtype);
         for (int i = 0; i < count; ++i)
-            DDL_REQUIRE(bytes[i] % es == 0 && reinterpret_cast<uintptr_t>(segs[i]) % es == 0, DDL_STATUS_INVALID_ARGUMENT,
+            DDL_REQUIRE(segs[i].bytes % es == 0 && reinterpret_cast<uintptr_t>(segs[i].ptr) % es == 0,
+                        DDL_STATUS_INVALID_ARGUMENT,
                         "segment " << i << " is not whole, aligned " << dtype_name(dtype) << " elements");
     }
     // in place only the segments the launch works on have tiles: the wanted ones of the sum of squares
     // (nothing else is read), else the AVG and the scaled ones (a SUM segment already is its result)
-    std::vector<size_t> own;
+    std::vector<CopySeg> own;
     if (in_place) {
-        own.assign(bytes, bytes + count);
-        for (int i = 0; i < count; ++i) {
-            const bool work = dir == kSumsqInPlace ? want[i] != 0
-                                                   : (div && ops[i] == DDL_ALLREDUCE_OP_AVG) || (sc && scale[i] != 1.0f);
-            if (!work) own[i] = 0;
+        own.assign(segs, segs + count);
+        for (CopySeg &sg : own) {
+            const bool work = dir == kSumsqInPlace ? sg.want
+                                                   : (div && sg.op == DDL_ALLREDUCE_OP_AVG) || (sc && sg.scale != 1.0f);
+            if (!work) sg.bytes = 0;
         }
-        bytes = own.data();
+        segs = own.data();
+        tiles = 0;
+        for (const CopySeg &sg : own) tiles += (sg.bytes + seg_tile - 1) / seg_tile;
     }
     Slot &sl = free_slot_();
-    // segment-aligned tiles of kSegTile bytes per workgroup; tile0 = running tile count
-    const uint64_t seg_tile = kSegTile;
-    uint64_t tiles = 0;
-    for (int i = 0; i < count; ++i) tiles += (bytes[i] + seg_tile - 1) / seg_tile;
+    // tile0 = running tile count
     DDL_REQUIRE(tiles < (1ull << 31), DDL_STATUS_INVALID_ARGUMENT, "fusion buffer too large");
     const uint64_t nblk = (tiles + kIdxBlock - 1) / kIdxBlock;
     const size_t table = (size_t)count * sizeof(SegDesc);
@@ -956,25 +944,26 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
     uint32_t *bases = reinterpret_cast<uint32_t *>(static_cast<char *>(sl.host) + table);
     uint64_t off = 0, tl = 0;
     for (int i = 0; i < count; ++i) {
-        DDL_REQUIRE(bytes[i] == 0 || segs[i], DDL_STATUS_INVALID_ARGUMENT, "null segment " << i);
-        t[i].ptr = reinterpret_cast<uint64_t>(segs[i]);
+        const CopySeg &sg = segs[i];
+        DDL_REQUIRE(sg.bytes == 0 || sg.ptr, DDL_STATUS_INVALID_ARGUMENT, "null segment " << i);
+        t[i].ptr = reinterpret_cast<uint64_t>(sg.ptr);
         t[i].off = off;
-        t[i].len = bytes[i];
-        t[i].vec = (reinterpret_cast<uintptr_t>(segs[i]) & 15u) == 0 ? kSegVec : 0;
-        if (div && ops[i] == DDL_ALLREDUCE_OP_AVG) t[i].vec |= kSegAvg;
-        if (stat && want[i] && bytes[i]) t[i].vec |= kSegStat;
-        if (sc && bytes[i] && scale[i] != 1.0f) t[i].vec |= kSegScale;
+        t[i].len = sg.bytes;
+        t[i].vec = (reinterpret_cast<uintptr_t>(sg.ptr) & 15u) == 0 ? kSegVec : 0;
+        if (div && sg.op == DDL_ALLREDUCE_OP_AVG) t[i].vec |= kSegAvg;
+        if (stat && sg.want && sg.bytes) t[i].vec |= kSegStat;
+        if (sc && sg.bytes && sg.scale != 1.0f) t[i].vec |= kSegScale;
         t[i].tile0 = (uint32_t)tl;
-        off += (bytes[i] + 255) & ~uint64_t(255);
-        tl += (bytes[i] + seg_tile - 1) / seg_tile;
+        off += (sg.bytes + 255) & ~uint64_t(255);
+        tl += (sg.bytes + seg_tile - 1) / seg_tile;
     }
     if (off == 0) return;
     if (fbk) {
         uint64_t *rt = reinterpret_cast<uint64_t *>(static_cast<char *>(sl.host) + rtab);
-        for (int i = 0; i < count; ++i) rt[i] = bytes[i] ? reinterpret_cast<uint64_t>(residuals[i]) : 0;
+        for (int i = 0; i < count; ++i) rt[i] = segs[i].bytes ? reinterpret_cast<uint64_t>(segs[i].residual) : 0;
     }
-    if (srk) std::memcpy(static_cast<char *>(sl.host) + wtab, streams, (size_t)count * sizeof(WireStream));
-    if (sc) std::memcpy(static_cast<char *>(sl.host) + stab, scale, (size_t)count * sizeof(float));
+    for (int i = 0; i < count && srk; ++i) reinterpret_cast<WireStream *>(static_cast<char *>(sl.host) + wtab)[i] = segs[i].stream;
+    for (int i = 0; i < count && sc; ++i) reinterpret_cast<float *>(static_cast<char *>(sl.host) + stab)[i] = segs[i].scale;
     // block b's base: the segment of tile b * 128 (the last one with tile0 <= it, as
     // k_tile_index resolves); narrow when no block spans more than 255 segments
     bool narrow = true;
@@ -1008,7 +997,7 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
         if (stat) {
             for (int i = 0; i < count; ++i)
                 if (t[i].vec & kSegStat)
-                    fin_groups = std::max(fin_groups, ((bytes[i] + seg_tile - 1) / seg_tile + kFinGroup - 1) / kFinGroup);
+                    fin_groups = std::max(fin_groups, ((segs[i].bytes + seg_tile - 1) / seg_tile + kFinGroup - 1) / kFinGroup);
             DDL_REQUIRE(fin_groups <= kFinGroup, DDL_STATUS_INVALID_ARGUMENT,
                         "the sum of squares takes pieces of at most " << kFinGroup * kFinGroup << " tiles");
             const size_t sb = (tiles + lvl_n + (size_t)count) * sizeof(double);
@@ -1076,7 +1065,7 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
             hipLaunchKernelGGL(k_sumsq_finish, dim3((unsigned)count, (unsigned)fin_groups), dim3(64), 0, stream, dd, partials,
                                lvl, res);
             if (fin_groups > 1) hipLaunchKernelGGL(k_sumsq_finish2, dim3((unsigned)count), dim3(64), 0, stream, dd, lvl, res);
-            DDL_HIP(hipMemcpyAsync(sumsq, res, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, stream));
+            DDL_HIP(hipMemcpyAsync(how.sumsq, res, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, stream));
         }
     }
     DDL_HIP(hipGetLastError());
@@ -1087,12 +1076,12 @@ void SegmentCopier::run_(int dir, void *flat, void *const *segs, const size_t *b
         if (!in_place) acc.push_back(gather ? dep::wr(flat, off) : dep::rd(flat, off));
         const size_t widen = wire ? dtype_size(dtype) / dtype_size(wire) : 1;  // the tensor side in its own bytes
         for (int i = 0; i < count; ++i)
-            if (bytes[i])
-                acc.push_back(gather ? dep::rd(segs[i], bytes[i] * widen) : dep::wr(segs[i], bytes[i] * widen));
+            if (segs[i].bytes)
+                acc.push_back(gather ? dep::rd(segs[i].ptr, segs[i].bytes * widen) : dep::wr(segs[i].ptr, segs[i].bytes * widen));
         for (int i = 0; i < count && fbk; ++i)
-            if (bytes[i] && residuals[i]) {  // read and written: both, so the race check sees either side
-                acc.push_back(dep::rd(residuals[i], bytes[i] * widen));
-                acc.push_back(dep::wr(residuals[i], bytes[i] * widen));
+            if (segs[i].bytes && segs[i].residual) {  // read and written: both, so the race check sees either side
+                acc.push_back(dep::rd(segs[i].residual, segs[i].bytes * widen));
+                acc.push_back(dep::wr(segs[i].residual, segs[i].bytes * widen));
             }
         const std::string label =
             in_place ? (dir == kSumsqInPlace ? "sumsq" : sc ? "scale" : "divide")

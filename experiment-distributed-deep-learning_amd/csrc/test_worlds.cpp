@@ -282,24 +282,18 @@ void ThreadWorld::allreduce_batch(const void *const *in, void *const *out, const
     });
 }
 
-size_t ThreadWorld::fused_allreduce(const void *const *srcs, void *const *dsts, const size_t *bytes, int count,
-                                    int dtype, hipStream_t user, const RingConfig &cfg, size_t cap, const int *ops,
-                                    int src_dtype, void *const *residuals, const unsigned char *want,
-                                    double *sumsq_out, std::vector<std::pair<size_t, size_t>> *cuts,
-                                    const float *prescale, const float *postscale, const WireStream *streams) {
+size_t ThreadWorld::fused_allreduce(const PlanSeg *segs, int count, int dtype, int src_dtype, size_t cap,
+                                    hipStream_t user, const RingConfig &cfg, double *sumsq_out,
+                                    std::vector<std::pair<size_t, size_t>> *cuts) {
     // the plan's kind: MIN / MAX plans hold one kind only (the keyed handler's groups)
-    const int kind = ops && count > 0 ? reduce_kind(ops[0]) : DDL_ALLREDUCE_OP_SUM;
-    for (int i = 0; ops && i < count; ++i)
-        DDL_REQUIRE(reduce_kind(ops[i]) == kind, DDL_STATUS_INVALID_ARGUMENT,
-                    "a fusion plan holds one reduction kind: segment " << i << " has op " << ops[i] << ", segment 0 op "
-                                                                       << ops[0]);
+    const int kind = count > 0 ? reduce_kind(segs[0].op) : DDL_ALLREDUCE_OP_SUM;
+    for (int i = 0; i < count; ++i)
+        DDL_REQUIRE(reduce_kind(segs[i].op) == kind, DDL_STATUS_INVALID_ARGUMENT,
+                    "a fusion plan holds one reduction kind: segment " << i << " has op " << segs[i].op
+                                                                       << ", segment 0 op " << segs[0].op);
     while (pipes_.size() < (size_t)P_) pipes_.emplace_back(new FusionPipe);
-    const std::vector<size_t> b(bytes, bytes + count);
-    const std::vector<int> o(ops ? ops : nullptr, ops ? ops + count : nullptr);
-    const std::vector<float> pre(prescale ? prescale : nullptr, prescale ? prescale + count : nullptr);
-    const std::vector<float> post(postscale ? postscale : nullptr, postscale ? postscale + count : nullptr);
     // the piece values: pinned blocks made as the pipes ask for them, freed once `user` has been waited for
-    std::vector<PlanSumsq> stats(want && sumsq_out ? P_ : 0);
+    std::vector<PlanSumsq> stats(sumsq_out ? P_ : 0);
     std::vector<void *> pinned;
     std::mutex pmu;
     struct FreePinned {
@@ -308,8 +302,7 @@ size_t ThreadWorld::fused_allreduce(const void *const *srcs, void *const *dsts, 
             for (void *p : v) (void)hipHostFree(p);
         }
     } free_pinned{pinned};
-    for (PlanSumsq &ps : stats) {
-        ps.want = want;
+    for (PlanSumsq &ps : stats)
         ps.pinned = [&](size_t n) {
             void *m = nullptr;
             DDL_HIP(hipHostMalloc(&m, std::max<size_t>(n, 1) * sizeof(double), hipHostMallocDefault));
@@ -317,20 +310,13 @@ size_t ThreadWorld::fused_allreduce(const void *const *srcs, void *const *dsts, 
             pinned.push_back(m);
             return static_cast<double *>(m);
         };
-    }
     run_(user, [&](int r, hipStream_t s) {
-        const std::vector<const void *> src(srcs + (size_t)r * count, srcs + (size_t)(r + 1) * count);
-        const std::vector<void *> dst(dsts + (size_t)r * count, dsts + (size_t)(r + 1) * count);
-        std::vector<void *> res;
-        if (residuals) res.assign(residuals + (size_t)r * count, residuals + (size_t)(r + 1) * count);
-        std::vector<WireStream> sts;
-        if (streams) sts.assign(streams + (size_t)r * count, streams + (size_t)(r + 1) * count);
-        pipes_[r]->run(src, dst, b, dtype, cap, s, [&](void *buf, size_t elems, size_t message) {
+        const std::vector<PlanSeg> mine(segs + (size_t)r * count, segs + (size_t)(r + 1) * count);
+        pipes_[r]->run(mine, dtype, src_dtype, cap, P_, s, [&](void *buf, size_t elems, size_t message) {
             RingConfig c = cfg;
             c.order_bytes = message;
             ex_[r]->allreduce(buf, buf, elems, dtype, s, c, kind);
-        }, ops ? &o : nullptr, P_, src_dtype, residuals ? &res : nullptr, stats.empty() ? nullptr : &stats[r],
-           prescale ? &pre : nullptr, postscale ? &post : nullptr, streams ? &sts : nullptr);
+        }, stats.empty() ? nullptr : &stats[r]);
     });
     if (!stats.empty()) {
         DDL_HIP(hipStreamSynchronize(user));

@@ -170,26 +170,17 @@ public:
                     int dtype, hipStream_t user);
     // The keyed path's multi-request plan on every rank (FusionPipe::run, what the handler runs:
     // pack -> allreduce -> unpack, sub-plans above `cap` bytes), each sub-plan's allreduce through
-    // the rank's RingExecutor with the whole plan's message size. srcs[r * count + i] /
-    // dsts[r * count + i]: rank r's segment i of bytes[i] bytes; ops[i] (optional) segment i's
-    // ddl_allreduce_op; the allreduces run with the segments' one reduction kind (SUM / AVG, MIN or
-    // MAX: a plan that mixes kinds is refused). Returns the sub-plans per rank.
-    size_t fused_allreduce(const void *const *srcs, void *const *dsts, const size_t *bytes, int count, int dtype,
-                           hipStream_t user, const RingConfig &cfg, size_t cap, const int *ops = nullptr,
-                           int src_dtype = 0,  // != 0: a compressed plan (FusionPipe::run), bytes on the wire
-                           void *const *residuals = nullptr,  // [r * count + i]: error feedback of a compressed plan
-                           // the sums of squares (FusionPipe's PlanSumsq on every rank; fp32 tensors):
-                           // want[i] per segment, sumsq_out[r * count + i] = rank r's pieces of segment i
-                           // added in increasing offset as the keyed handler adds them (+0.0 where not
-                           // wanted); *cuts = rank 0's (segment, first element) of every wanted piece that
-                           // starts inside a segment. Waits for `user` before it returns.
-                           const unsigned char *want = nullptr, double *sumsq_out = nullptr,
-                           std::vector<std::pair<size_t, size_t>> *cuts = nullptr,
-                           // the scale factors (FusionPipe::run), one per segment, the same on every rank
-                           const float *prescale = nullptr, const float *postscale = nullptr,
-                           // stochastic rounding (FusionPipe::run's `streams`): rank r's segment i is
-                           // streams[r * count + i], null = none
-                           const WireStream *streams = nullptr);
+    // the rank's RingExecutor with the whole plan's message size. segs[r * count + i]: rank r's
+    // segment i; bytes, op, factors and want of segment i are rank 0's on every rank. The allreduces
+    // run with the segments' one reduction kind (SUM / AVG, MIN or MAX: a plan that mixes kinds is
+    // refused). `src_dtype` != 0: a compressed plan, bytes on the wire. `sumsq_out` (non-null: waits for
+    // `user` before it returns): sumsq_out[r * count + i] = rank r's pieces of segment i added in
+    // increasing offset as the keyed handler adds them (+0.0 where not wanted); *cuts = rank 0's
+    // (segment, first element) of every wanted piece that starts inside a segment. Returns the
+    // sub-plans per rank.
+    size_t fused_allreduce(const PlanSeg *segs, int count, int dtype, int src_dtype, size_t cap, hipStream_t user,
+                           const RingConfig &cfg, double *sumsq_out = nullptr,
+                           std::vector<std::pair<size_t, size_t>> *cuts = nullptr);
 
 private:
     void run_(hipStream_t user, const std::function<void(int, hipStream_t)> &body);
