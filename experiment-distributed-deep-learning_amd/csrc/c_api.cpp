@@ -352,8 +352,8 @@ static void take_sumsq(int *op, void **user, double **sumsq, float *pre, float *
 // the refusals of a wanted sum of squares, before anything is registered or recorded
 static void check_sumsq(const double *sumsq, int dtype, int op, bool host) {
     if (!sumsq) return;
-    DDL_REQUIRE(dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
-                "the sum of squares is defined for float32 requests, not " << dtype_name(dtype));
+    DDL_REQUIRE(dtype == DDL_FLOAT || dtype == DDL_BFLOAT16, DDL_STATUS_UNSUPPORTED_DTYPE,
+                "the sum of squares is defined for float32 and bfloat16 requests, not " << dtype_name(dtype));
     DDL_REQUIRE(!op_is_minmax(op), DDL_STATUS_INVALID_ARGUMENT, "the sum of squares takes SUM or AVG, not MIN / MAX");
     DDL_REQUIRE(!host, DDL_STATUS_INVALID_ARGUMENT, "the sum of squares takes device memory");
 }
@@ -362,8 +362,8 @@ static void check_scale(float pre, float post, int dtype, int op, bool host) {
     DDL_REQUIRE(std::isfinite(pre) && pre > 0.0f && std::isfinite(post) && post > 0.0f, DDL_STATUS_INVALID_ARGUMENT,
                 "scale factors must be finite and positive, not " << pre << " / " << post);
     if (pre == 1.0f && post == 1.0f) return;
-    DDL_REQUIRE(dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
-                "scale factors are defined for float32 requests, not " << dtype_name(dtype));
+    DDL_REQUIRE(dtype == DDL_FLOAT || dtype == DDL_BFLOAT16, DDL_STATUS_UNSUPPORTED_DTYPE,
+                "scale factors are defined for float32 and bfloat16 requests, not " << dtype_name(dtype));
     DDL_REQUIRE(!op_is_minmax(op), DDL_STATUS_INVALID_ARGUMENT, "scale factors take SUM or AVG, not MIN / MAX");
     DDL_REQUIRE(!host, DDL_STATUS_INVALID_ARGUMENT, "scale factors take device memory");
 }

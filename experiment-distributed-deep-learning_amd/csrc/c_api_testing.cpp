@@ -616,6 +616,46 @@ int ddl_unpack_scale(void *const *dsts, const void *src, const size_t *elements,
     });
 }
 
+// The scaled copies of native tensors (ddl_amd_testing.h): the copier's calls with the tensors' dtype and no wire.
+int ddl_pack_scale_dtype(void *dst, const void *const *srcs, const size_t *elements, int count, int dtype,
+                         const float *scale, void *hip_stream) {
+    return guarded([&] {
+        DDL_REQUIRE(count >= 0 && (count == 0 || (dst && srcs && elements && scale)), DDL_STATUS_INVALID_ARGUMENT,
+                    "bad pack_scale_dtype args");
+        const size_t es = dtype_size(dtype);
+        DDL_REQUIRE(es != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported dtype " << dtype);
+        std::lock_guard<std::mutex> g(abi_copier_mu());
+        const std::vector<CopySeg> &segs = copy_segs(count, unconst(srcs), elements, es, nullptr, scale);
+        abi_copier().run(CopyLaunch{0, dst, as_stream(hip_stream), dtype, 0}, segs.data(), count);
+    });
+}
+
+int ddl_unpack_scale_dtype(void *const *dsts, const void *src, const size_t *elements, const int *ops, int count,
+                           int dtype, int divisor, const float *scale, void *hip_stream, const unsigned char *want,
+                           double *sumsq_out) {
+    return guarded([&] {
+        DDL_REQUIRE(count >= 0 && (count == 0 || (dsts && elements && ops && scale)) && divisor >= 1 &&
+                        (!want || sumsq_out) && (src || !want),
+                    DDL_STATUS_INVALID_ARGUMENT, "bad unpack_scale_dtype args");
+        if (count == 0) return;
+        const size_t es = dtype_size(dtype);
+        DDL_REQUIRE(es != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported dtype " << dtype);
+        for (int i = 0; i < count; ++i) {
+            check_allreduce_op(ops[i], dtype);
+            DDL_REQUIRE(!op_is_minmax(ops[i]), DDL_STATUS_INVALID_ARGUMENT, "scale factors take SUM or AVG");
+        }
+        std::lock_guard<std::mutex> g(abi_copier_mu());
+        const std::vector<CopySeg> &segs = copy_segs(count, dsts, elements, es, ops, scale, nullptr, want);
+        auto run = [&](double *sq) {
+            abi_copier().run(CopyLaunch{src ? 1 : SegmentCopier::kDivInPlace, const_cast<void *>(src),
+                                        as_stream(hip_stream), dtype, 0, divisor, sq},
+                             segs.data(), count);
+        };
+        if (want) unpack_sumsq(count, hip_stream, sumsq_out, run);
+        else run(nullptr);
+    });
+}
+
 int ddl_pack_cvt(void *dst, const void *const *srcs, const size_t *elements, int count, int wire_dtype,
                  void *hip_stream) {
     return guarded([&] {
@@ -855,6 +895,30 @@ int ddl_testing_thread_fused_allreduce_scale(int nranks, int count, const void *
                     wire_dtype ? DDL_FLOAT : 0, hip_stream, subplans};
         c.ops = ops;
         c.residuals = residuals;
+        c.prescale = prescale, c.postscale = postscale;
+        c.want = want, c.sumsq_out = sumsq_out;
+        c.cut_segs = cut_segs, c.cut_elems = cut_elems, c.max_cuts = max_cuts, c.ncuts = ncuts;
+        thread_fused(c);
+    });
+}
+
+int ddl_testing_thread_fused_allreduce_native(int nranks, int count, const void *const *srcs, void *const *dsts,
+                                              const size_t *elements, const int *ops, int dtype, const float *prescale,
+                                              const float *postscale, void *hip_stream, size_t *subplans,
+                                              const unsigned char *want, double *sumsq_out, size_t *cut_segs,
+                                              size_t *cut_elems, int max_cuts, int *ncuts) {
+    return guarded([&] {
+        DDL_REQUIRE(nranks >= 1 && nranks <= 64 && count >= 1 && srcs && dsts && elements && (!want || sumsq_out),
+                    DDL_STATUS_INVALID_ARGUMENT, "bad thread fused allreduce");
+        const size_t es = dtype_size(dtype);
+        DDL_REQUIRE(es != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported dtype " << dtype);
+        for (int i = 0; ops && i < count; ++i) {
+            check_allreduce_op(ops[i], dtype);
+            DDL_REQUIRE(!op_is_minmax(ops[i]), DDL_STATUS_INVALID_ARGUMENT, "scale factors take SUM or AVG");
+        }
+        check_factors(prescale, postscale, count);
+        FusedCall c{nranks, count, srcs, dsts, elements, es, dtype, 0, hip_stream, subplans};
+        c.ops = ops;
         c.prescale = prescale, c.postscale = postscale;
         c.want = want, c.sumsq_out = sumsq_out;
         c.cut_segs = cut_segs, c.cut_elems = cut_elems, c.max_cuts = max_cuts, c.ncuts = ncuts;

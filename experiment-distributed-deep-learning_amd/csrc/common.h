@@ -284,7 +284,8 @@ struct CopySeg {
     // DDL_ALLREDUCE_OP_AVG with CopyLaunch::divisor > 1 (a float dtype): the scatter stores the quotient of
     // the segment's elements (k_seg<DivOp> in place of k_seg<CopyOp>), kDivInPlace divides them in place
     int op = DDL_ALLREDUCE_OP_SUM;
-    // DDL_ALLREDUCE_SCALE (finite and > 0; DDL_FLOAT): dir 0 multiplies the elements on their way into the
+    // DDL_ALLREDUCE_SCALE (finite and > 0; DDL_FLOAT, or DDL_BFLOAT16 without a wire: widened, multiplied in fp32
+    // and narrowed once per kernel — ScaleGather16Op, DivOp<kDivBF16, true>): dir 0 multiplies the elements on their way into the
     // flat buffer (the prescale, ahead of the narrowing and the residual's addition), dir 1 and kDivInPlace
     // on their way into the tensors, behind the widening and AVG's quotient (the postscale); the sum of
     // squares is of the scaled values
@@ -295,7 +296,8 @@ struct CopySeg {
     // DDL_ALLREDUCE_WIRE_STOCHASTIC (a converting bf16 pack): a segment with stream.on (and no residual) is
     // narrowed by the rule of ddl_amd.h (k_seg<CvtPackSrOp>)
     WireStream stream{};
-    // DDL_ALLREDUCE_SUMSQ (DDL_FLOAT; dir 1 / kSumsqInPlace): k_seg_sumsq in place of k_seg stores what k_seg
+    // DDL_ALLREDUCE_SUMSQ (DDL_FLOAT, or DDL_BFLOAT16 without a wire: k_seg_sumsq16, the squares of the stored
+    // bf16 values in the 2-byte order; dir 1 / kSumsqInPlace): k_seg_sumsq in place of k_seg stores what k_seg
     // would and leaves one fp64 partial per 1 KiB tile of the wanted segments (with a wire in the compressed
     // order: 512 elements per tile, 8 per lane), then the finishing kernel and an async copy of the launch's
     // values into CopyLaunch::sumsq on its stream. The order of the additions: include/ddl_amd.h.

@@ -130,15 +130,15 @@ void validate(const Request &r, int size) {
             DDL_REQUIRE(!r.stochastic || (r.wire == DDL_BFLOAT16 && !r.feedback), DDL_STATUS_INVALID_ARGUMENT,
                         "stochastic rounding takes the bfloat16 wire and no error feedback");
             DDL_REQUIRE(r.n == 0 || (r.in && r.out), DDL_STATUS_INVALID_ARGUMENT, "null buffer");
-            DDL_REQUIRE(!r.sumsq || r.dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
-                        "the sum of squares is defined for float32 requests, not " << dtype_name(r.dtype));
+            DDL_REQUIRE(!r.sumsq || r.dtype == DDL_FLOAT || r.dtype == DDL_BFLOAT16, DDL_STATUS_UNSUPPORTED_DTYPE,
+                        "the sum of squares is defined for float32 and bfloat16 requests, not " << dtype_name(r.dtype));
             DDL_REQUIRE(!r.sumsq || (!r.host && !op_is_minmax(r.op)), DDL_STATUS_INVALID_ARGUMENT,
                         "the sum of squares takes a SUM or AVG request in device memory");
             DDL_REQUIRE(std::isfinite(r.prescale) && r.prescale > 0.0f && std::isfinite(r.postscale) && r.postscale > 0.0f,
                         DDL_STATUS_INVALID_ARGUMENT, "scale factors must be finite and positive");
             if (r.prescale != 1.0f || r.postscale != 1.0f) {
-                DDL_REQUIRE(r.dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
-                            "scale factors are defined for float32 requests, not " << dtype_name(r.dtype));
+                DDL_REQUIRE(r.dtype == DDL_FLOAT || r.dtype == DDL_BFLOAT16, DDL_STATUS_UNSUPPORTED_DTYPE,
+                            "scale factors are defined for float32 and bfloat16 requests, not " << dtype_name(r.dtype));
                 DDL_REQUIRE(!r.host && !op_is_minmax(r.op), DDL_STATUS_INVALID_ARGUMENT,
                             "scale factors take a SUM or AVG request in device memory");
             }
@@ -546,17 +546,17 @@ double *RequestHandler::stat_take_(size_t n) {
     return p;
 }
 
-void RequestHandler::stat_in_place_(size_t req, void *out, size_t bytes) {
+void RequestHandler::stat_in_place_(size_t req, void *out, size_t bytes, int dtype) {
     double *sq = stat_take_(1);
     CopySeg seg{out, bytes};
     seg.want = true;
-    fp_.copier.run(CopyLaunch{SegmentCopier::kSumsqInPlace, nullptr, stream_, DDL_FLOAT, 0, 1, sq}, &seg, 1);
+    fp_.copier.run(CopyLaunch{SegmentCopier::kSumsqInPlace, nullptr, stream_, dtype, 0, 1, sq}, &seg, 1);
     round_stat_.emplace_back(req, sq);
 }
 
-void RequestHandler::scale_in_place_(void *out, size_t bytes, int op, int divisor, float factor) {
+void RequestHandler::scale_in_place_(void *out, size_t bytes, int dtype, int op, int divisor, float factor) {
     const CopySeg seg{out, bytes, op, factor};
-    fp_.copier.run(CopyLaunch{SegmentCopier::kDivInPlace, nullptr, stream_, DDL_FLOAT, 0, divisor}, &seg, 1);
+    fp_.copier.run(CopyLaunch{SegmentCopier::kDivInPlace, nullptr, stream_, dtype, 0, divisor}, &seg, 1);
 }
 
 std::unique_lock<std::mutex> RequestHandler::lock_host_group_(const std::vector<Request> &reqs,
@@ -677,9 +677,9 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
                 plan_slices(p, reqs, g.second, ses, [&](const char *s, char *d, size_t n) {
                     const Request &r = reqs[g.second[q]];
                     if (s != d && n) DDL_HIP(hipMemcpyAsync(d, s, n, hipMemcpyDeviceToDevice, stream_));
-                    if (n && r.prescale != 1.0f) scale_in_place_(d, n, DDL_ALLREDUCE_OP_SUM, 1, r.prescale);
-                    if (n && r.postscale != 1.0f) scale_in_place_(d, n, DDL_ALLREDUCE_OP_SUM, 1, r.postscale);
-                    if (reqs[g.second[q]].sumsq && n) stat_in_place_(g.second[q], d, n);
+                    if (n && r.prescale != 1.0f) scale_in_place_(d, n, sdt, DDL_ALLREDUCE_OP_SUM, 1, r.prescale);
+                    if (n && r.postscale != 1.0f) scale_in_place_(d, n, sdt, DDL_ALLREDUCE_OP_SUM, 1, r.postscale);
+                    if (reqs[g.second[q]].sumsq && n) stat_in_place_(g.second[q], d, n, sdt);
                     ++q;
                 });
             } else if (p.req_begin == p.req_end && !comp) {
@@ -694,7 +694,7 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
                 // disagree about a prescale must still post the same collective.
                 if (r.prescale != 1.0f && cnt) {
                     if (src != dst) DDL_HIP(hipMemcpyAsync(dst, src, cnt * es, hipMemcpyDeviceToDevice, stream_));
-                    scale_in_place_(dst, cnt * es, DDL_ALLREDUCE_OP_SUM, 1, r.prescale);
+                    scale_in_place_(dst, cnt * es, dt, DDL_ALLREDUCE_OP_SUM, 1, r.prescale);
                     src = dst;
                 }
                 // a postscale: the allreduce of the reduction kind alone, then ONE in-place launch that
@@ -702,9 +702,9 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
                 const bool post = r.postscale != 1.0f;
                 data_->allreduce(src, dst, cnt, dt, post ? kind : r.op, stream_);
                 if (post && cnt)
-                    scale_in_place_(static_cast<char *>(r.out) + p.elem_begin * es, cnt * es, r.op, data_->size(), r.postscale);
+                    scale_in_place_(static_cast<char *>(r.out) + p.elem_begin * es, cnt * es, dt, r.op, data_->size(), r.postscale);
                 // no unpack to take it from: one read-only pass over the finished slice
-                if (r.sumsq && cnt) stat_in_place_(g.second[p.req_begin], static_cast<char *>(r.out) + p.elem_begin * es, cnt * es);
+                if (r.sumsq && cnt) stat_in_place_(g.second[p.req_begin], static_cast<char *>(r.out) + p.elem_begin * es, cnt * es, dt);
             } else {
                 // a compressed plan always comes here, also with one request: the conversion is
                 // the pack's and the unpack's, so the in-place direct path cannot apply.

@@ -125,10 +125,10 @@ private:
     };
     double *stat_take_(size_t n);
     // the in-place, read-only sum of squares (SegmentCopier::kSumsqInPlace) of reqs[req]'s slice on stream_
-    void stat_in_place_(size_t req, void *out, size_t bytes);
+    void stat_in_place_(size_t req, void *out, size_t bytes, int dtype);
     // one in-place launch of the scaled scatter on stream_ over a finished fp32 slice: AVG's quotient by
     // `divisor` where `op` is AVG, then `factor` (SegmentCopier::kDivInPlace with a factor)
-    void scale_in_place_(void *out, size_t bytes, int op, int divisor, float factor);
+    void scale_in_place_(void *out, size_t bytes, int dtype, int op, int divisor, float factor);
     struct Done {
         size_t plan;  // index into the round's plan events (kNoPlan: nothing to wait for)
         size_t req;

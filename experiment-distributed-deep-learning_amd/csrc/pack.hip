@@ -11,7 +11,8 @@
 // segment is cut into 1 KiB tiles that restart at the segment start, one 64-lane workgroup per
 // tile, the tile's segment from a one-byte-per-tile index built on the device (k_tile_index).
 // One kernel, k_seg, walks the tiles for every operation; what an operation does to a 16-byte
-// unit and to a single element is its Op struct (CopyOp, DivOp, CvtPackOp, CvtUnpackOp).
+// unit and to a single element is its Op struct (CopyOp, DivOp, CvtPackOp, CvtUnpackOp, ScaleGatherOp,
+// ScaleGather16Op).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -138,11 +139,13 @@ template <class T, class A0, class... A> __device__ inline T arg_of(A0 a0, A... 
 // included. A scaled launch carries one fp32 factor per segment (a const float * behind the launch's
 // other arguments: scl[seg], uploaded behind the block bases and the residual addresses); a segment
 // flagged kSegScale has every element multiplied by it, a segment without the flag is moved exactly as
-// the unscaled Op moves it (no multiply is issued: the bits are untouched). fp32 tensors only. Every
+// the unscaled Op moves it (no multiply is issued: the bits are untouched). fp32 tensors, and native bf16
+// tensors through the 16-bit Ops below (widened, multiplied, narrowed once per kernel). Every
 // product is one fp32 operation rounded to nearest even with subnormals kept, and never part of an fma:
 // hipcc contracts a * b + c by default, so the multiply is mul_rn, compiled with contraction off.
 //   pack:    c = g (x) a, then what the unscaled pack does with c (store / narrow / feedback's c (+) r)
 //   unpack:  y = s (widened), y = y (/) (float)P for kSegAvg, y = y (x) b for kSegScale, store y
+//   bf16 tensors:  c = narrow(widen(g) (x) a);  store narrow(widen(s) (/) (float)P (x) b): one rounding, at the end
 __device__ inline float mul_rn(float x, float a) {
 #pragma clang fp contract(off)
     return x * a;
@@ -228,8 +231,19 @@ template <> struct DivTraits<kDivBF16> {
 // What every scatter does to the values on their way into a tensor, written once (DivOp, CvtUnpackOp
 // and k_seg_sumsq after their loads and widenings): q(x, P) for a kSegAvg segment, then (SCALE) the
 // factor for a kSegScale one. This order is contract.
+// A native 16-bit tensor dtype seen as fp32 (the scaled and the counted paths of 16-bit tensors are written
+// over this trait): widen is exact, narrow the one rounding to nearest even of the wire of the same format
+// (overflow gives inf, a NaN stays a NaN). bfloat16 is the only instance; float16 would be one more.
+template <int DT> struct Wide16;
+template <> struct Wide16<kDivBF16> {
+    using T = DivTraits<kDivBF16>::T;  // the bits
+    static __device__ inline float widen(T x) { return __uint_as_float((uint32_t)x << 16); }
+    static __device__ inline T narrow(float y) { return __builtin_bit_cast(T, (__bf16)y); }
+};
+template <int DT> constexpr bool kIs16 = DT == kDivF16 || DT == kDivBF16;
+
 template <int DT, bool SCALE> struct Chain {
-    static_assert(!SCALE || DT == kDivF32, "scale factors are defined for float32 tensors");
+    static_assert(!SCALE || DT == kDivF32 || DT == kDivBF16, "scale factors are defined for float32 and bfloat16 tensors");
     using Tr = DivTraits<DT>;
     typename Tr::D dv;
     bool avg;
@@ -238,15 +252,28 @@ template <int DT, bool SCALE> struct Chain {
     __device__ Chain(const SegDesc &sd, int seg, typename Tr::D divisor, A... a)
         : dv(divisor), avg((sd.vec & kSegAvg) != 0), fac(sd, seg, a...) {}
     template <int N> __device__ void operator()(typename Tr::T (&x)[N]) const {
+        if constexpr (SCALE && kIs16<DT>) {
+            // 16-bit tensors: widen, quotient, factor, ONE narrowing — never one between the quotient and the
+            // factor. A segment without a factor takes the unscaled q (the same bits), a SUM one nothing.
+            if (fac.on) {
+#pragma unroll
+                for (int k = 0; k < N; ++k) {
+                    float y = Wide16<DT>::widen(x[k]);
+                    if (avg) y = y / dv;
+                    x[k] = Wide16<DT>::narrow(mul_rn(y, fac.a));
+                }
+                return;
+            }
+        }
         if (avg) {
 #pragma unroll
             for (int k = 0; k < N; ++k) x[k] = Tr::q(x[k], dv);
         }
-        if constexpr (SCALE) fac(x);
+        if constexpr (SCALE && !kIs16<DT>) fac(x);
     }
 };
 
-// SCALE (kDivF32 only): the scaled scatter, with the factor table behind the divisor.
+// SCALE (kDivF32, kDivBF16): the scaled scatter, with the factor table behind the divisor.
 template <int DT, bool SCALE = false> struct DivOp {
     using T = typename DivTraits<DT>::T;
     static constexpr uint32_t kUnit = sizeof(T);
@@ -590,6 +617,36 @@ struct ScaleGatherOp {
     __device__ void elem(uint64_t e) const { fl[e] = sc ? mul_rn(tp[e], a) : tp[e]; }
 };
 
+// ScaleGather16Op: the prescale of native 16-bit tensors, tensor -> flat: c = narrow(widen(g) (x) a) for a
+// kSegScale segment, the bits moved untouched for any other. Whole 16-bit elements (kUnit 2). The vector path
+// is one 16-byte load, 8 x widen / mul_rn / narrow and one 16-byte store; a tensor that is only 2-byte aligned
+// and a segment's last partial unit go element by element. 4 bytes moved per element, as the plain copy.
+template <int DT> struct ScaleGather16Op {
+    using W = Wide16<DT>;
+    using T = typename W::T;
+    static constexpr uint32_t kUnit = sizeof(T);
+    T *fl;
+    const T *tp;
+    float a;
+    bool sc, v;
+    __device__ ScaleGather16Op(char *flat, const SegDesc &sd, int seg, const float *__restrict__ scl)
+        : fl(reinterpret_cast<T *>(flat + sd.off)), tp(reinterpret_cast<const T *>(sd.ptr)),
+          sc((sd.vec & kSegScale) != 0), v((sd.vec & kSegVec) != 0) {
+        a = sc ? scl[seg] : 1.0f;
+    }
+    __device__ bool vector() const { return v; }
+    __device__ void vec(uint64_t b) const {
+        Wire8<T> x;
+        x.v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(tp) + b));
+        if (sc) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) x.e[k] = W::narrow(mul_rn(W::widen(x.e[k]), a));
+        }
+        __builtin_nontemporal_store(x.v, reinterpret_cast<u32x4 *>(reinterpret_cast<char *>(fl) + b));
+    }
+    __device__ void elem(uint64_t e) const { fl[e] = sc ? W::narrow(mul_rn(W::widen(tp[e]), a)) : tp[e]; }
+};
+
 // ---- the unpacks with the sum of squares (DDL_ALLREDUCE_SUMSQ) -----------------------------
 // k_seg_sumsq: the plain, the dividing (WIRE < 0: fp32 flat buffer, DivOp<kDivF32>'s quotient) and the
 // converting scatter (WIRE = kWireF16 / kWireBF16: CvtUnpackOp's widening and quotient) of fp32
@@ -696,6 +753,61 @@ __global__ void __launch_bounds__(64) k_seg_sumsq(const char *flat, const SegDes
     seg_sumsq<WIRE, NARROW, SCALE>(flat, d, blk_base, map, divisor, partials, a...);
 }
 
+// k_seg_sumsq16: the same for native 16-bit tensors (DT: kDivBF16) — 16-bit flat buffer, 16-bit tensors, the
+// 2-byte layout of the order above: T = 512 elements per tile, E = 8 per lane. The scatter stores what
+// DivOp<DT, SCALE> stores (Chain: the unscaled quotient, or widen / quotient / factor / one narrowing; a SUM
+// segment without a factor its bytes) and squares widen(stored element): the statistic is of what is in the
+// tensor, so it is finite exactly when every stored element is. Both sides of a lane's 8 elements are one
+// 16-byte unit: the flat side always, the tensor side where the tensor is 16-byte aligned and the lane holds 8
+// whole elements, else element by element. flat == nullptr: in place and read-only, as above.
+template <int DT, bool NARROW, bool SCALE, class... A>
+__global__ void __launch_bounds__(64) k_seg_sumsq16(const char *flat, const SegDesc *__restrict__ d,
+                                                    const uint32_t *__restrict__ blk_base, const void *__restrict__ map,
+                                                    float divisor, double *__restrict__ partials, A... a) {
+    using W = Wide16<DT>;
+    using T = typename W::T;
+    constexpr int E = 8;
+    const unsigned tile = blockIdx.x;
+    const int seg = tile_segment<NARROW>(tile, blk_base, map);
+    const SegDesc sd = d[seg];
+    const uint64_t n = sd.len / sizeof(T);
+    const uint64_t e0 = (uint64_t)(tile - sd.tile0) * (kSegTile / sizeof(T)) + threadIdx.x * E;
+    const int nv = e0 >= n ? 0 : n - e0 < (uint64_t)E ? (int)(n - e0) : E;  // the lane's elements inside the segment
+    T *tp = reinterpret_cast<T *>(sd.ptr) + e0;
+    const bool whole = (sd.vec & kSegVec) != 0 && nv == E;
+    Wire8<T> x;
+#pragma unroll
+    for (int k = 0; k < E; ++k) x.e[k] = 0;
+    if (flat) {
+        if (nv > 0) {
+            x.v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(flat + sd.off + e0 * sizeof(T)));
+            Chain<DT, SCALE>(sd, seg, divisor, a...)(x.e);
+            if (whole) {
+                __builtin_nontemporal_store(x.v, reinterpret_cast<u32x4 *>(tp));
+            } else {
+#pragma unroll
+                for (int k = 0; k < E; ++k)
+                    if (k < nv) tp[k] = x.e[k];
+            }
+        }
+    } else if (whole) {
+        x.v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(tp));
+    } else {
+#pragma unroll
+        for (int k = 0; k < E; ++k)
+            if (k < nv) x.e[k] = tp[k];
+    }
+    if (!(sd.vec & kSegStat)) return;  // (the whole workgroup: one segment per tile)
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < E; ++k) {
+        const double v = (double)W::widen(x.e[k]);
+        acc += k < nv ? v * v : 0.0;
+    }
+    acc = wave_sum(acc);
+    if (threadIdx.x == 0) partials[tile] = acc;
+}
+
 // The finishing kernels: a segment's tile partials (nt of them, contiguous from tile0) into out[seg], in a
 // fixed order that only nt decides. A GROUP is up to kFinGroup = 4096 consecutive values: lane l adds
 // values l, l + 64, l + 128, ... of the group to +0.0 in that order (at most 64 additions), then the
@@ -747,6 +859,13 @@ void launch_sumsq(bool narrow, dim3 g, hipStream_t stream, const char *fl, const
     hipLaunchKernelGGL(k, g, dim3(64), 0, stream, fl, dd, db, map, divisor, partials, a...);
 }
 
+template <int DT, bool SCALE, class... A>
+void launch_sumsq16(bool narrow, dim3 g, hipStream_t stream, const char *fl, const SegDesc *dd, const uint32_t *db,
+                    const void *map, float divisor, double *partials, A... a) {
+    const auto k = narrow ? k_seg_sumsq16<DT, true, SCALE, A...> : k_seg_sumsq16<DT, false, SCALE, A...>;
+    hipLaunchKernelGGL(k, g, dim3(64), 0, stream, fl, dd, db, map, divisor, partials, a...);
+}
+
 // A run-time fact of a launch as a compile-time constant: f(std::integral_constant), so that each
 // choice between two instances is written once.
 template <class F> void with_bool(bool b, F f) {
@@ -764,6 +883,20 @@ void require_f32_segments(const CopySeg *segs, int count, size_t unit) {
     for (int i = 0; i < count; ++i)
         DDL_REQUIRE(segs[i].bytes % unit == 0 && reinterpret_cast<uintptr_t>(segs[i].ptr) % 4 == 0,
                     DDL_STATUS_INVALID_ARGUMENT, "segment " << i << " is not whole, aligned float32 elements");
+}
+// native 16-bit tensors: every segment whole elements at a 2-byte aligned address
+void require_16bit_segments(const CopySeg *segs, int count, int dtype) {
+    for (int i = 0; i < count; ++i)
+        DDL_REQUIRE(segs[i].bytes % 2 == 0 && reinterpret_cast<uintptr_t>(segs[i].ptr) % 2 == 0, DDL_STATUS_INVALID_ARGUMENT,
+                    "segment " << i << " is not whole, aligned " << dtype_name(dtype) << " elements");
+}
+// the tensors of a scaled or counted launch: float32 (also under a wire), or bfloat16 without one
+void require_scalable_segments(const CopySeg *segs, int count, int dtype, int wire, const char *what) {
+    const bool h16 = dtype == DDL_BFLOAT16 && !wire;
+    DDL_REQUIRE(dtype == DDL_FLOAT || h16, DDL_STATUS_UNSUPPORTED_DTYPE,
+                what << " defined for float32 tensors, not " << dtype_name(dtype));
+    if (h16) require_16bit_segments(segs, count, dtype);
+    else require_f32_segments(segs, count, wire ? 2 : 4);
 }
 
 }  // namespace
@@ -830,6 +963,7 @@ void SegmentCopier::run(const CopyLaunch &how, const CopySeg *segs, int count) {
     const uint64_t seg_tile = kSegTile;  // segment-aligned tiles of kSegTile bytes per workgroup
     uint64_t tiles = 0;
     const bool plain = segs == plain_.data();  // copy()'s own segments: every option at its default
+    const bool h16 = !wire && dtype == DDL_BFLOAT16;  // native 16-bit tensors whose factors and statistic have kernels
     for (int i = 0; i < n; ++i) {
         const CopySeg &sg = segs[i];
         wanted |= sg.want;
@@ -872,9 +1006,7 @@ void SegmentCopier::run(const CopyLaunch &how, const CopySeg *segs, int count) {
     if (sc) {
         DDL_REQUIRE(bad_scale < 0, DDL_STATUS_INVALID_ARGUMENT,
                     "scale factor " << segs[bad_scale].scale << " of segment " << bad_scale << " is not finite and positive");
-        DDL_REQUIRE(dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
-                    "scale factors are defined for float32 tensors, not " << dtype_name(dtype));
-        require_f32_segments(segs, n, wire ? 2 : 4);
+        require_scalable_segments(segs, n, dtype, wire, "scale factors are");
     }
     if (dir == 1 || dir == kSumsqInPlace) {
         DDL_REQUIRE(!wanted || how.sumsq, DDL_STATUS_INVALID_ARGUMENT, "sum of squares without an output");
@@ -883,9 +1015,7 @@ void SegmentCopier::run(const CopyLaunch &how, const CopySeg *segs, int count) {
     }
     if (dir == kSumsqInPlace && !stat) return;  // nothing wanted: the zeros above are the answer
     if (stat) {
-        DDL_REQUIRE(dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
-                    "the sum of squares is defined for float32 tensors, not " << dtype_name(dtype));
-        require_f32_segments(segs, n, wire ? 2 : 4);
+        require_scalable_segments(segs, n, dtype, wire, "the sum of squares is");
     }
     if (dir == kDivInPlace) {
         if (!div && !sc) return;  // nothing to divide or scale: the segments already hold their results
@@ -1030,7 +1160,11 @@ void SegmentCopier::run(const CopyLaunch &how, const CopySeg *segs, int count) {
                     launch_sumsq<W, SCALE>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor, partials, x...);
                 });
             };
-            if (stat) {
+            if (stat && h16) {  // bfloat16 tensors (checked above): the 2-byte layout, scatter or in place
+                go([&](auto... x) {
+                    launch_sumsq16<kDivBF16, SCALE>(narrow, g, stream, fl, dd, db, sl.idx, (float)divisor, partials, x...);
+                });
+            } else if (stat) {
                 if (wire) with_wire(wire, sumsq);
                 else sumsq(std::integral_constant<int, -1>{});
             } else if (wire) {
@@ -1042,8 +1176,10 @@ void SegmentCopier::run(const CopyLaunch &how, const CopySeg *segs, int count) {
                     else if (fbk) seg((CvtPackOp<W, true, SCALE> *)nullptr, res);
                     else seg((CvtPackOp<W, false, SCALE> *)nullptr);
                 });
-            } else if constexpr (SCALE) {  // fp32 (checked above); the scatter also in place
-                if (dir == 0) seg((ScaleGatherOp *)nullptr);
+            } else if constexpr (SCALE) {  // fp32 or bf16 (checked above); the scatter also in place
+                if (h16 && dir == 0) seg((ScaleGather16Op<kDivBF16> *)nullptr);
+                else if (h16) seg((DivOp<kDivBF16, true> *)nullptr, (double)divisor);
+                else if (dir == 0) seg((ScaleGatherOp *)nullptr);
                 else seg((DivOp<kDivF32, true> *)nullptr, (double)divisor);
             } else if (dir == 0) {
                 seg((CopyOp<0> *)nullptr);

@@ -168,6 +168,13 @@ class CPPBackend:
         sig('ddl_testing_thread_fused_allreduce_scale', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp),
             ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(ci), ci, fp, fp, vp, ctypes.POINTER(sz), ub, dp,
             ctypes.POINTER(sz), ctypes.POINTER(sz), ci, ctypes.POINTER(ci))
+        # (testing library: the same for native bfloat16 tensors)
+        sig('ddl_pack_scale_dtype', ci, vp, ctypes.POINTER(vp), ctypes.POINTER(sz), ci, ci, fp, vp)
+        sig('ddl_unpack_scale_dtype', ci, ctypes.POINTER(vp), vp, ctypes.POINTER(sz), ctypes.POINTER(ci), ci, ci, ci, fp,
+            vp, ub, dp)
+        sig('ddl_testing_thread_fused_allreduce_native', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp),
+            ctypes.POINTER(sz), ctypes.POINTER(ci), ci, fp, fp, vp, ctypes.POINTER(sz), ub, dp, ctypes.POINTER(sz),
+            ctypes.POINTER(sz), ci, ctypes.POINTER(ci))
         sig('ddl_broadcast_submit_mem', ci, cid, ctypes.c_char_p, vp, vp, sz, ci, ci, ci, vp, DONE_FN, vp)
         sig('ddl_allgather_submit_mem', ci, cid, ctypes.c_char_p, vp, sz, sz, ci, ci, vp, ALLOC_FN, DONE_FN, vp)
         sig('ddl_control_channel_open', ctypes.c_longlong, ctypes.c_char_p, sz)

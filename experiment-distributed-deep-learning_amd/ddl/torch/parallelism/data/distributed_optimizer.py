@@ -56,7 +56,7 @@ No residual, nothing to reset, the plain 6-byte pack; the stable per-parameter n
 
 `track_grad_norm=True` (implied by `max_grad_norm` and `skip_nonfinite`): after
 `allreduce_gradients()`, `optimizer.grad_norm` is the global L2 norm of the averaged gradients (a
-float) and `optimizer.found_nonfinite` is `not math.isfinite(grad_norm)`. Every dense fp32 device
+float) and `optimizer.found_nonfinite` is `not math.isfinite(grad_norm)`. Every dense fp32 or bf16 device
 gradient contributes the engine's sum of squares (`allreduce_async(..., sumsq=True)`: taken by the
 kernel that writes the reduced gradient, no second read of it from HBM, and the same bits on every
 rank), on both paths, step() and the `overlap_backward` hooks; every other gradient (other dtypes,
@@ -70,16 +70,19 @@ is the same double on every rank) with one `torch._foreach_mul_` per device. `sk
 non-finite norm makes step() return without calling the wrapped step(). At size 1 nothing is
 communicated and the norm is torch's.
 
-`gradient_predivide_factor=f` (Horovod's): every dense fp32 contiguous device gradient is submitted with
+`gradient_predivide_factor=f` (Horovod's): every dense fp32 or bf16 contiguous device gradient is submitted with
 the engine's prescale 1 / f and postscale f (`allreduce_async(..., prescale=, postscale=)`), on both
 paths, so what is summed is g / f — with `compression=Compression.fp16` and f = the size, the mean, which
 cannot overflow where the gradients themselves do not. The two products are taken inside the pack and
 the unpack kernels: no pass over the gradients is added. Other gradients ignore it (the net factor is 1).
+A bf16 gradient is widened, multiplied in fp32 and rounded back to bf16 by the pack: a factor that is not a
+power of two costs the contribution one extra bf16 rounding (a power of two is exact short of under- and
+overflow); the postscale shares the unpack's one rounding with the mean's quotient.
 Every rank must pass the same value. Default 1 (off).
 
 `optimizer.loss_scale` (a plain attribute, default 1.0; read when a gradient is submitted, so with
 `overlap_backward` set it before backward()): the gradients are those of `loss * loss_scale`, and come
-back divided by it — the engine-handled gradients (dense fp32 contiguous device) by a postscale of
+back divided by it — the engine-handled gradients (dense fp32 or bf16 contiguous device) by a postscale of
 1 / loss_scale in the unpack kernel (together with the predivide's f), every other gradient by a torch
 multiply after its reduction. `grad_norm`, `max_grad_norm` and `found_nonfinite` then refer to the
 unscaled, averaged gradients, and no `unscale_` pass runs. `DynamicLossScaler` drives it. With an
@@ -129,8 +132,9 @@ class DataParallelismDistributedOptimizer:
 
     @staticmethod
     def _engine_sumsq(g) -> bool:
-        """Whether the engine takes this gradient's sum of squares (a dense fp32 device tensor)."""
-        return g.is_cuda and not g.is_sparse and g.dtype == torch.float32 and g.is_contiguous()
+        """Whether the engine takes this gradient's sum of squares and factors (a dense, contiguous fp32 or
+        bf16 device tensor)."""
+        return g.is_cuda and not g.is_sparse and g.dtype in (torch.float32, torch.bfloat16) and g.is_contiguous()
 
     def _unscale(self) -> float:
         return 1.0 / float(self.loss_scale)

@@ -454,8 +454,12 @@ def _compressible(tensor: torch.Tensor, communicator: Communicator, flag: int, m
     return communicator.size > 1 or CPPBackend.c_api().ddl_get_config(b'one_rank_shortcut') == 0
 
 
+# the dtypes whose sum of squares and scale factors the engine's pack / unpack kernels take (float16 is not one)
+_ENGINE_OPTION_DTYPES = (torch.float32, torch.bfloat16)
+
+
 def _check_sumsq(tensors, op: int, what: str) -> None:
-    """`sumsq=True` is the engine's DDL_ALLREDUCE_SUMSQ: dense fp32 device tensors, SUM or AVG.
+    """`sumsq=True` is the engine's DDL_ALLREDUCE_SUMSQ: dense fp32 or bf16 device tensors, SUM or AVG.
     Raised before any library call."""
     if int(op) in (cb.OP_MIN, cb.OP_MAX):
         raise ValueError(f'{what}: sumsq is defined for OP_SUM and OP_AVG, not OP_MIN / OP_MAX')
@@ -463,8 +467,8 @@ def _check_sumsq(tensors, op: int, what: str) -> None:
         if t.is_sparse or not t.is_cuda:
             raise ValueError(f'{what}: sumsq needs a dense device tensor, not a {t.device.type} '
                              f'{"sparse " if t.is_sparse else ""}one')
-        if t.dtype != torch.float32:
-            raise ValueError(f'{what}: sumsq is defined for float32 tensors, not {t.dtype}')
+        if t.dtype not in _ENGINE_OPTION_DTYPES:
+            raise ValueError(f'{what}: sumsq is defined for float32 and bfloat16 tensors, not {t.dtype}')
 
 
 def _scale_factor(value, what: str) -> float:
@@ -484,7 +488,7 @@ def _scale_factor(value, what: str) -> float:
 
 
 def _check_scale(tensors, op: int, what: str) -> None:
-    """A factor other than 1 is the engine's DDL_ALLREDUCE_SCALE: dense fp32 device tensors, SUM or AVG.
+    """A factor other than 1 is the engine's DDL_ALLREDUCE_SCALE: dense fp32 or bf16 device tensors, SUM or AVG.
     Raised before any library call."""
     if int(op) in (cb.OP_MIN, cb.OP_MAX):
         raise ValueError(f'{what}: prescale / postscale are defined for OP_SUM and OP_AVG, not OP_MIN / OP_MAX')
@@ -492,8 +496,8 @@ def _check_scale(tensors, op: int, what: str) -> None:
         if t.is_sparse or not t.is_cuda:
             raise ValueError(f'{what}: prescale / postscale need a dense device tensor, not a {t.device.type} '
                              f'{"sparse " if t.is_sparse else ""}one')
-        if t.dtype != torch.float32:
-            raise ValueError(f'{what}: prescale / postscale are defined for float32 tensors, not {t.dtype}')
+        if t.dtype not in _ENGINE_OPTION_DTYPES:
+            raise ValueError(f'{what}: prescale / postscale are defined for float32 and bfloat16 tensors, not {t.dtype}')
 
 
 def _same_memory(a: torch.Tensor, b: torch.Tensor, what: str) -> int:
@@ -519,15 +523,18 @@ def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator 
     of the tensor in device memory per distinct name until the communicator goes, so keep the names
     stable from step to step; ddl.torch.compression.reset_error_feedback after loading a checkpoint
     or a large change of the loss scale).
-    `sumsq=True` (a dense fp32 device tensor, OP_SUM or OP_AVG; anything else: ValueError): after
+    `sumsq=True` (a dense fp32 or bf16 device tensor, OP_SUM or OP_AVG; anything else: ValueError): after
     wait(), `handle.sumsq` is a Python float, the fp64 sum of the squares of the output's elements,
     taken by the engine where it writes them (include/ddl_amd.h "Sum of squares": no extra pass in a
-    fused plan, the same bits on every rank, finite if and only if every element is finite).
-    `prescale` / `postscale` (a dense fp32 device tensor, OP_SUM or OP_AVG; a factor must be finite and
+    fused plan, the same bits on every rank, finite if and only if every element is finite; of a bf16
+    output it is of the stored bf16 values).
+    `prescale` / `postscale` (a dense fp32 or bf16 device tensor, OP_SUM or OP_AVG; a factor must be finite and
     > 0; anything else: ValueError before anything is submitted): every element is multiplied by
     `prescale` on its way into the reduction and every result, behind OP_AVG's quotient, by `postscale`
     on its way into the output — by the kernels that move those bytes anyway (include/ddl_amd.h "Scale
-    factors"). They compose with `op`, `compression` and `sumsq` (which is then of the scaled output).
+    factors"). They compose with `op`, `compression` and `sumsq` (which is then of the scaled output). A bf16
+    tensor is widened, multiplied in fp32 and rounded to bf16 once per kernel: a prescale that is no power of
+    two costs the contribution one extra bf16 rounding; quotient and postscale share one rounding.
 
     `name` plays the role of the TF op name: the same name on every rank identifies the same
     gradient, and only one request per name may be pending (TensorCommunicateRequest.h:21).
@@ -589,10 +596,10 @@ def allreduce_async_batch(tensors, names, communicator: Communicator = None, out
     come back in the caller's order either way. The error-feedback kinds as in `allreduce_async`:
     one residual per name, so stable names. `sumsq` as in `allreduce_async`: True for every tensor, or
     one bool per tensor (a batch may mix requests with and without it); the flagged tensors must be
-    dense fp32 device tensors (ValueError otherwise) and their handles carry `sumsq` after wait().
+    dense fp32 or bf16 device tensors (ValueError otherwise) and their handles carry `sumsq` after wait().
     `prescale` / `postscale` as in `allreduce_async`: one value for every tensor, or one per tensor (a
     batch may mix scaled and unscaled requests); the tensors with a factor other than 1 must be dense
-    fp32 device tensors (ValueError otherwise, before anything is submitted)."""
+    fp32 or bf16 device tensors (ValueError otherwise, before anything is submitted)."""
     import ctypes
     _check_op_compression(op, compression)
     tensors = list(tensors)

@@ -90,7 +90,7 @@ enum ddl_allreduce_wire { DDL_ALLREDUCE_WIRE_FP16 = 0x100, DDL_ALLREDUCE_WIRE_BF
 /* Stochastic rounding onto the bf16 wire (MI355X extension; the data-plane section): one more bit of the
  * same `op`, valid only OR-ed with DDL_ALLREDUCE_WIRE_BF16 and never with DDL_ALLREDUCE_WIRE_FEEDBACK. */
 enum ddl_allreduce_wire_rounding { DDL_ALLREDUCE_WIRE_STOCHASTIC = 0x8000 };
-/* Sum of squares of a keyed device allreduce of DDL_FLOAT tensors (MI355X extension; the data-plane
+/* Sum of squares of a keyed device allreduce of DDL_FLOAT or DDL_BFLOAT16 tensors (MI355X extension; the data-plane
  * section): OR-ed into the `op` of ddl_allreduce_submit / _submit_batch (and _submit_mem /
  * _submit_batch_mem with DDL_MEMORY_DEVICE), SUM or AVG, with or without a wire flag. With the bit
  * `user` (every users[i] of a batch) points to a ddl_sumsq_arg, read during the call only: `done`
@@ -102,7 +102,7 @@ struct ddl_sumsq_arg {
     double *sumsq; /* where the sum of squares goes, or NULL */
 };
 
-/* Scale factors of a keyed device allreduce of DDL_FLOAT tensors (MI355X extension, Horovod's
+/* Scale factors of a keyed device allreduce of DDL_FLOAT or DDL_BFLOAT16 tensors (MI355X extension, Horovod's
  * prescale_factor / postscale_factor; the data-plane section): OR-ed into the `op` of the same entry
  * points as DDL_ALLREDUCE_SUMSQ, SUM or AVG, with or without a wire flag, the feedback bit and
  * DDL_ALLREDUCE_SUMSQ. With the bit `user` (every users[i] of a batch) points to a ddl_scale_arg, read
@@ -450,11 +450,19 @@ void py_error(const char *log_str);
  * uncompressed order also with a wire flag (nothing is compressed); with 0 the data plane runs and
  * the value is its result's. On a failed request the value is unspecified.
  * Refusals, before anything is registered (the communicator works afterwards): a non-NULL sumsq with
- * a dtype other than DDL_FLOAT returns DDL_STATUS_UNSUPPORTED_DTYPE, with MIN / MAX or with
+ * a dtype other than DDL_FLOAT and DDL_BFLOAT16 returns DDL_STATUS_UNSUPPORTED_DTYPE, with MIN / MAX or with
  * DDL_MEMORY_HOST DDL_STATUS_INVALID_ARGUMENT; the bit with a NULL `user` (`users`, users[i]), and the
  * bit on ddl_allreduce, ddl_allreduce_batch or ddl_allreduce_host, DDL_STATUS_INVALID_ARGUMENT; the
  * op's own refusals apply as without the bit. With every arg->sumsq NULL the request is the one
  * without the bit. No new entry point: the deployment surface is unchanged.
+ * bfloat16. A keyed DDL_BFLOAT16 device request with op SUM or AVG (no wire flag: it has none) takes the bit
+ * too: *sumsq = the fp64 sum of the squares of widen(e) over the bfloat16 elements e STORED to `out` — after
+ * AVG's quotient, the postscale and the one rounding to bfloat16 behind them — so it is finite exactly when
+ * every stored element is. The order is the 2-byte layout's, T = 512 and E = 8 (a 1 KiB tile holds 512
+ * elements, a lane's 16 bytes 8), pieces cut at 256-byte multiples = 128 elements, everything else as
+ * above; a plan of one request and the one-rank shortcut read the result in place in that same order
+ * (csrc/pack.hip k_seg_sumsq16). DDL_HALF, DDL_DOUBLE and the integer dtypes stay
+ * DDL_STATUS_UNSUPPORTED_DTYPE.
  *
  * Scale factors (DDL_ALLREDUCE_SCALE in `op`, `user` a ddl_scale_arg): two optional fp32 factors of a keyed
  * DDL_FLOAT device request with op SUM or AVG (a wire flag, the feedback bit and DDL_ALLREDUCE_SUMSQ
@@ -487,10 +495,22 @@ void py_error(const char *log_str);
  * rounding; with 0 the data plane runs and defines the value.
  * Refusals, before anything is registered (the communicator works afterwards): a factor that is not
  * finite or is <= 0 returns DDL_STATUS_INVALID_ARGUMENT; a factor other than 1 with a dtype other than
- * DDL_FLOAT DDL_STATUS_UNSUPPORTED_DTYPE, with MIN / MAX or DDL_MEMORY_HOST DDL_STATUS_INVALID_ARGUMENT;
+ * DDL_FLOAT and DDL_BFLOAT16 DDL_STATUS_UNSUPPORTED_DTYPE, with MIN / MAX or DDL_MEMORY_HOST DDL_STATUS_INVALID_ARGUMENT;
  * the bit with a NULL `user` (`users`, users[i]), and the bit on ddl_allreduce, ddl_allreduce_batch or
  * ddl_allreduce_host, DDL_STATUS_INVALID_ARGUMENT. If both factors are 1 the request is the one without
- * the bit. No new entry point. */
+ * the bit. No new entry point.
+ * bfloat16. A keyed DDL_BFLOAT16 device request with op SUM or AVG (no wire flag) takes the factors too, in
+ * fp32 arithmetic as above with widen exact and narrow the round-to-nearest-even fp32 -> bfloat16 of the
+ * bf16 wire (overflow gives inf, a NaN stays a NaN, payload unspecified):
+ *   contribution:  a != 1: c = narrow(widen(g) (x) a);  a = 1: the bytes are moved untouched;
+ *   reduction: the plan's plain bfloat16 allreduce, unchanged;
+ *   result, element s of the reduced stream:  y = widen(s);  AVG and P > 1: y = y (/) (float)P;  b != 1:
+ *     y = y (x) b;  narrow(y) is stored — ONE bfloat16 rounding, at the end, never one between the quotient
+ *     and the factor. With b = 1 these are the bits of the AVG op without factors; SUM with b = 1: bytes.
+ * A prescale that is no power of two therefore costs the contribution one extra bfloat16 rounding. A plan
+ * of one request takes the prescale in place ahead of its in-place allreduce and quotient and postscale in
+ * one in-place launch behind it, as for DDL_FLOAT. DDL_HALF, DDL_DOUBLE and the integer dtypes stay
+ * DDL_STATUS_UNSUPPORTED_DTYPE. */
 /* recv = SUM over ranks of send (elementwise), bit for bit the reference's MPI_Allreduce (MPICH
  * 3.3.2's order) with reference_order 1. The schedule is the tuned one for the bucket's size
  * class: by default at P > 2 the direct reduce-scatter (slices of every chunk to every peer over

@@ -179,6 +179,18 @@ int ddl_pack_scale(void *dst, const void *const *srcs, void *const *residuals, c
 int ddl_unpack_scale(void *const *dsts, const void *src, const size_t *elements, const int *ops, int count,
                      int wire_dtype, int divisor, const float *scale, void *hip_stream, const unsigned char *want,
                      double *sumsq_out);
+/* The scaled copies of native tensors (bfloat16; ddl_amd.h "Scale factors"; csrc/pack.hip ScaleGather16Op, the
+ * SCALE instance of DivOp<kDivBF16> and k_seg_sumsq16): as ddl_pack_scale / ddl_unpack_scale with wire_dtype 0, but
+ * the tensors AND the flat buffer hold elements[i] values of `dtype` (2-byte aligned). dtype DDL_FLOAT is
+ * ddl_pack_scale / ddl_unpack_scale themselves; any other dtype with a factor != 1 or a wanted segment returns
+ * DDL_STATUS_UNSUPPORTED_DTYPE. A pack segment with factor 1 is moved as bytes; the unpack stores
+ * narrow(widen(s) (/) P (x) b), one rounding, and sumsq_out[i] is of the stored bfloat16 values in the 2-byte
+ * layout's order. src == NULL (want NULL): in place, quotient and factor in one launch. */
+int ddl_pack_scale_dtype(void *dst, const void *const *srcs, const size_t *elements, int count, int dtype,
+                         const float *scale, void *hip_stream);
+int ddl_unpack_scale_dtype(void *const *dsts, const void *src, const size_t *elements, const int *ops, int count,
+                           int dtype, int divisor, const float *scale, void *hip_stream, const unsigned char *want,
+                           double *sumsq_out);
 /* ddl_pack_cvt with error feedback (DDL_ALLREDUCE_WIRE_FEEDBACK; k_seg<CvtPackOp<WIRE, true>>) on caller-owned
  * residuals: residuals[i] = elements[i] fp32 values (4-byte aligned), added to segment i before the
  * rounding and overwritten with what the rounding removed; NULL = segment i is converted as
@@ -292,6 +304,14 @@ int ddl_testing_thread_fused_allreduce_scale(int nranks, int count, const void *
                                              void *hip_stream, size_t *subplans, const unsigned char *want,
                                              double *sumsq_out, size_t *cut_segs, size_t *cut_elems, int max_cuts,
                                              int *ncuts);
+/* ddl_testing_thread_fused_allreduce_scale for native tensors: no wire and no residuals, the tensors and the plan
+ * hold elements[i] values of `dtype` (DDL_BFLOAT16, or DDL_FLOAT = the _scale entry with wire_dtype 0), as the keyed
+ * handler runs a native request group: pieces cut at 256-byte multiples of the tensors' own bytes. */
+int ddl_testing_thread_fused_allreduce_native(int nranks, int count, const void *const *srcs, void *const *dsts,
+                                              const size_t *elements, const int *ops, int dtype, const float *prescale,
+                                              const float *postscale, void *hip_stream, size_t *subplans,
+                                              const unsigned char *want, double *sumsq_out, size_t *cut_segs,
+                                              size_t *cut_elems, int max_cuts, int *ncuts);
 /* ddl_testing_thread_fused_allreduce_scale over the bf16 wire with stochastic rounding and no residuals:
  * sr_want[i] != 0 = segment i is rounded stochastically on every virtual rank, rank r with the stream key
  * streams[r * count + i] and first element index 0, handed to the plan as the keyed handler hands over its
