@@ -40,8 +40,12 @@ int ddl_version(void) { return 2; }
 #endif
 const char *ddl_build_info(void) { return "src=" DDL_SRC_HASH " arch=gfx950"; }
 const char *ddl_last_error(void) { return last_error(); }
-const char *ddl_dtype_name(int dtype) { return dtype_name(dtype); }
-size_t ddl_dtype_size(int dtype) { return dtype_size(dtype); }
+// (the engine's internal wire dtypes are no ddl_dtype: unsupported at every entry point)
+const char *ddl_dtype_name(int dtype) { return dtype_name(dtype == kDtypeE4m3 ? 0 : dtype); }
+size_t ddl_dtype_size(int dtype) { return dtype == kDtypeE4m3 ? 0 : dtype_size(dtype); }
+static void public_dtype(int dtype) {
+    DDL_REQUIRE(dtype != kDtypeE4m3, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported dtype " << dtype);
+}
 
 int ddl_get_unique_id(void *out, size_t len) {
     return guarded([&] {
@@ -268,24 +272,32 @@ void py_error(const char *s) { DDL_LOG(0, "[py]: " << (s ? s : "")); }
 // ---- data plane ---------------------------------------------------------------------------
 int ddl_allreduce(ddl_communicator_id id, const void *send, void *recv, size_t elements, int dtype,
                   int op, void *hip_stream) {
-    return guarded([&] { Registry::get().find(id)->allreduce(send, recv, elements, dtype, op, as_stream(hip_stream)); });
+    return guarded([&] {
+        public_dtype(dtype);
+        Registry::get().find(id)->allreduce(send, recv, elements, dtype, op, as_stream(hip_stream));
+    });
 }
 
 int ddl_allreduce_batch(ddl_communicator_id id, int count, const void *const *sends, void *const *recvs,
                         const size_t *elements, int dtype, int op, void *hip_stream) {
     return guarded([&] {
+        public_dtype(dtype);
         Registry::get().find(id)->allreduce_batch(sends, recvs, elements, count, dtype, op, as_stream(hip_stream));
     });
 }
 
 int ddl_broadcast(ddl_communicator_id id, void *buf, size_t elements, int dtype, int root, void *hip_stream) {
-    return guarded([&] { Registry::get().find(id)->broadcast(buf, elements, dtype, root, as_stream(hip_stream)); });
+    return guarded([&] {
+        public_dtype(dtype);
+        Registry::get().find(id)->broadcast(buf, elements, dtype, root, as_stream(hip_stream));
+    });
 }
 
 int ddl_allgatherv(ddl_communicator_id id, const void *send, size_t send_elements, void *recv,
                    const size_t *recv_counts, const size_t *displs, int dtype, void *hip_stream) {
     return guarded([&] {
         auto c = Registry::get().find(id);
+        public_dtype(dtype);
         DDL_REQUIRE(recv_counts && displs, DDL_STATUS_INVALID_ARGUMENT, "null counts/displs");
         DDL_REQUIRE(recv_counts[c->rank()] == send_elements, DDL_STATUS_INVALID_ARGUMENT,
                     "send_elements " << send_elements << " != recv_counts[rank] " << recv_counts[c->rank()]);
@@ -297,6 +309,7 @@ int ddl_allgather(ddl_communicator_id id, const void *send, size_t send_elements
                   int dtype, void *hip_stream) {
     return guarded([&] {
         auto c = Registry::get().find(id);
+        public_dtype(dtype);
         DDL_REQUIRE(send_elements == recv_elements, DDL_STATUS_INVALID_ARGUMENT,
                     "send_elements " << send_elements << " != recv_elements " << recv_elements);
         std::vector<size_t> counts(c->size(), recv_elements), displs(c->size());
@@ -306,7 +319,10 @@ int ddl_allgather(ddl_communicator_id id, const void *send, size_t send_elements
 }
 
 int ddl_allreduce_host(ddl_communicator_id id, const void *send, void *recv, size_t elements, int dtype, int op) {
-    return guarded([&] { Registry::get().find(id)->allreduce_host(send, recv, elements, dtype, op); });
+    return guarded([&] {
+        public_dtype(dtype);
+        Registry::get().find(id)->allreduce_host(send, recv, elements, dtype, op);
+    });
 }
 
 int ddl_comm_transport(ddl_communicator_id id, int *kind, int *ranks) {
@@ -384,6 +400,7 @@ int ddl_allreduce_submit_mem(ddl_communicator_id id, const char *key, const void
         r.host = memory == DDL_MEMORY_HOST;
         take_sumsq(&op, &user, &r.sumsq, &r.prescale, &r.postscale);
         r.wire = decode_keyed_op(op, dtype, r.host, &r.op, &r.feedback, &r.stochastic);  // refusals before anything is posted
+        check_wire_ranks(r.wire, c->size());
         check_sumsq(r.sumsq, dtype, r.op, r.host);
         check_scale(r.prescale, r.postscale, dtype, r.op, r.host);
         r.done = done;
@@ -482,6 +499,7 @@ int ddl_allreduce_submit_batch_mem(ddl_communicator_id id, int count, const char
             rs[i].user = users ? users[i] : nullptr;
             take_sumsq(&opi, &rs[i].user, &rs[i].sumsq, &rs[i].prescale, &rs[i].postscale);  // (sumsq entries may be NULL)
             rs[i].wire = decode_keyed_op(opi, dtypes[i], rs[i].host, &rs[i].op, &rs[i].feedback, &rs[i].stochastic);
+            check_wire_ranks(rs[i].wire, c->size());
             check_sumsq(rs[i].sumsq, dtypes[i], rs[i].op, rs[i].host);
             check_scale(rs[i].prescale, rs[i].postscale, dtypes[i], rs[i].op, rs[i].host);
             rs[i].done = done;

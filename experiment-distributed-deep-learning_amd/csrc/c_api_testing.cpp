@@ -239,6 +239,10 @@ void thread_fused(const FusedCall &c) {
                                    c.residuals ? c.residuals[k] : nullptr,
                                    c.sr_want && c.sr_want[i] ? WireStream{c.keys[k], 0, 1} : WireStream{},
                                    c.want && c.want[i]});
+            if (c.dtype == kDtypeE4m3) {  // c.n counts fp32 elements: whole granules on the wire
+                segs.back().bytes = e4m3_granules(c.n[i]) * kE4m3Granule;
+                segs.back().elems = c.n[i];
+            }
         }
     std::vector<std::pair<size_t, size_t>> cuts;
     const size_t j = thread_world(c.nranks).fused_allreduce(
@@ -711,6 +715,82 @@ int ddl_unpack_cvt(void *const *dsts, const void *src, const size_t *elements, c
         const std::vector<CopySeg> &segs = copy_segs(count, dsts, elements, wire_unit(wire_dtype), ops);
         abi_copier().run(CopyLaunch{1, const_cast<void *>(src), as_stream(hip_stream), DDL_FLOAT, wire_dtype, divisor},
                          segs.data(), count);
+    });
+}
+
+// The e4m3 wire's kernels (ddl_amd_testing.h): the copier's calls with the granule wire, the fold over granules.
+namespace {
+const CopySeg *e4m3_segs(int count, void *const *ptrs, const size_t *elements, const int *ops, const float *scale,
+                                const unsigned char *want) {
+    std::vector<CopySeg> &segs = copy_segs(count, ptrs, elements, 0, ops, scale, nullptr, want);
+    for (int i = 0; i < count; ++i) {
+        segs[(size_t)i].bytes = e4m3_granules(elements[i]) * kE4m3Granule;
+        segs[(size_t)i].elems = elements[i];
+    }
+    return segs.data();
+}
+}  // namespace
+
+int ddl_pack_e4m3(void *dst, const void *const *srcs, const size_t *elements, int count, const float *scale,
+                  void *hip_stream) {
+    return guarded([&] {
+        DDL_REQUIRE(count >= 0 && (count == 0 || (dst && srcs && elements)), DDL_STATUS_INVALID_ARGUMENT,
+                    "bad pack_e4m3 args");
+        std::lock_guard<std::mutex> g(abi_copier_mu());
+        const CopySeg *segs = e4m3_segs(count, unconst(srcs), elements, nullptr, scale, nullptr);
+        abi_copier().run(CopyLaunch{0, dst, as_stream(hip_stream), DDL_FLOAT, kDtypeE4m3}, segs, count);
+    });
+}
+
+int ddl_unpack_e4m3(void *const *dsts, const void *src, const size_t *elements, const int *ops, int count, int divisor,
+                    const float *scale, void *hip_stream, const unsigned char *want, double *sumsq_out) {
+    return guarded([&] {
+        DDL_REQUIRE(count >= 0 && (count == 0 || (src && dsts && elements)) && divisor >= 1 && (!want || sumsq_out),
+                    DDL_STATUS_INVALID_ARGUMENT, "bad unpack_e4m3 args");
+        if (count == 0) return;
+        check_float_ops(ops, count, "MIN / MAX take no wire");
+        std::lock_guard<std::mutex> g(abi_copier_mu());
+        const CopySeg *segs = e4m3_segs(count, dsts, elements, ops, scale, want);
+        auto run = [&](double *sq) {
+            abi_copier().run(CopyLaunch{1, const_cast<void *>(src), as_stream(hip_stream), DDL_FLOAT, kDtypeE4m3, divisor, sq},
+                             segs, count);
+        };
+        if (want) unpack_sumsq(count, hip_stream, sumsq_out, run);
+        else run(nullptr);
+    });
+}
+
+int ddl_fold_e4m3(void *out, const void *a, const void *const *ins, int nb, size_t granules, void *hip_stream) {
+    return ddl_reduce_fold_ordered(out, a, ins, nb, granules, kDtypeE4m3, kFoldLeft, hip_stream);
+}
+
+int ddl_testing_keyed_tune_result(ddl_communicator_id id, size_t bucket_bytes, int e4m3, int *chosen, int *count,
+                                  long long *configs, float *ms, int max_candidates) {
+    return guarded([&] {
+        auto c = Registry::get().find(id);
+        const std::shared_ptr<Communicator> data = c->keyed_data();  // the keyed plans' allreduces run (and tune) there
+        export_tune((data ? data.get() : c.get())->tune_result(bucket_bytes, e4m3 ? kDtypeE4m3 : 0), chosen, count, configs,
+                    ms, max_candidates);
+    });
+}
+
+int ddl_testing_thread_fused_allreduce_e4m3(int nranks, int count, const void *const *srcs, void *const *dsts,
+                                            const size_t *elements, const int *ops, const float *prescale,
+                                            const float *postscale, void *hip_stream, size_t *subplans,
+                                            const unsigned char *want, double *sumsq_out, size_t *cut_segs,
+                                            size_t *cut_elems, int max_cuts, int *ncuts) {
+    return guarded([&] {
+        DDL_REQUIRE(nranks >= 1 && nranks <= 64 && count >= 1 && srcs && dsts && elements && (!want || sumsq_out),
+                    DDL_STATUS_INVALID_ARGUMENT, "bad thread fused allreduce");
+        check_wire_ranks(kDtypeE4m3, nranks);
+        check_float_ops(ops, count, "MIN / MAX take no wire");
+        check_factors(prescale, postscale, count);
+        FusedCall c{nranks, count, srcs, dsts, elements, 0, kDtypeE4m3, DDL_FLOAT, hip_stream, subplans};
+        c.ops = ops;
+        c.prescale = prescale, c.postscale = postscale;
+        c.want = want, c.sumsq_out = sumsq_out;
+        c.cut_segs = cut_segs, c.cut_elems = cut_elems, c.max_cuts = max_cuts, c.ncuts = ncuts;
+        thread_fused(c);
     });
 }
 

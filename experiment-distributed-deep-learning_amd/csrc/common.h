@@ -18,8 +18,17 @@
 
 namespace ddl {
 
+// The wire element of DDL_ALLREDUCE_WIRE_E4M3 as a dtype of the engine's own (never a ddl_dtype: the C-ABI
+// refuses it): one 256-byte granule — 252 e4m3fn codes and an fp32 scale (include/ddl_amd.h "The e4m3 wire").
+// Plans, cuts, chunks and slices of such an allreduce count granules; its reduce is k_foldq, on the fold-once
+// schedules only, its inputs always in rank order.
+constexpr int kDtypeE4m3 = 0x1e43;
+constexpr size_t kE4m3Granule = 256, kE4m3Elems = 252;
+inline size_t e4m3_granules(size_t elements) { return (elements + kE4m3Elems - 1) / kE4m3Elems; }
+
 inline size_t dtype_size(int dt) {
     switch (dt) {
+        case kDtypeE4m3: return kE4m3Granule;
         case DDL_FLOAT: case DDL_INT32: return 4;
         case DDL_DOUBLE: case DDL_INT64: case DDL_UINT64: return 8;
         case DDL_HALF: case DDL_BFLOAT16: return 2;
@@ -36,6 +45,7 @@ inline const char *dtype_name(int dt) {
         case DDL_UINT64: return "uint64";
         case DDL_HALF: return "float16";
         case DDL_BFLOAT16: return "bfloat16";
+        case kDtypeE4m3: return "e4m3 granule";
         default: return "unsupported";
     }
 }
@@ -93,12 +103,13 @@ inline void check_allreduce_op(int op, int dtype) {
 
 // The `op` of a keyed allreduce request: SUM / AVG / MIN / MAX in the low bits, with SUM / AVG
 // optionally one ddl_allreduce_wire format flag, optionally DDL_ALLREDUCE_WIRE_FEEDBACK with it, or
-// DDL_ALLREDUCE_WIRE_STOCHASTIC with WIRE_BF16. Returns the wire dtype (DDL_HALF / DDL_BFLOAT16; 0 =
+// DDL_ALLREDUCE_WIRE_STOCHASTIC with WIRE_BF16; or DDL_ALLREDUCE_WIRE_E4M3 alone (kDtypeE4m3). Returns the wire dtype (DDL_HALF / DDL_BFLOAT16; 0 =
 // uncompressed), leaves the op in *base, the feedback bit in *feedback and the stochastic bit in
 // *stochastic. Refusals as ddl_amd.h lists them, before anything is registered.
 inline int decode_keyed_op(int op, int dtype, bool host, int *base, bool *feedback, bool *stochastic) {
     constexpr int kWire = DDL_ALLREDUCE_WIRE_FP16 | DDL_ALLREDUCE_WIRE_BF16;
-    *base = op & ~(kWire | DDL_ALLREDUCE_WIRE_FEEDBACK | DDL_ALLREDUCE_WIRE_STOCHASTIC);
+    const bool q8 = (op & DDL_ALLREDUCE_WIRE_E4M3) != 0;
+    *base = op & ~(kWire | DDL_ALLREDUCE_WIRE_FEEDBACK | DDL_ALLREDUCE_WIRE_STOCHASTIC | DDL_ALLREDUCE_WIRE_E4M3);
     *feedback = (op & DDL_ALLREDUCE_WIRE_FEEDBACK) != 0;
     *stochastic = (op & DDL_ALLREDUCE_WIRE_STOCHASTIC) != 0;
     const int w = op & kWire;
@@ -116,11 +127,23 @@ inline int decode_keyed_op(int op, int dtype, bool host, int *base, bool *feedba
                 "WIRE_STOCHASTIC takes WIRE_BF16 and no other wire flag (allreduce op " << op << ")");
     DDL_REQUIRE(!*stochastic || !*feedback, DDL_STATUS_INVALID_ARGUMENT,
                 "WIRE_STOCHASTIC and WIRE_FEEDBACK are alternatives (allreduce op " << op << ")");
-    if (!w) return 0;
+    DDL_REQUIRE(!q8 || (!w && !*feedback && !*stochastic), DDL_STATUS_INVALID_ARGUMENT,
+                "WIRE_E4M3 takes no other wire flag, no WIRE_FEEDBACK and no WIRE_STOCHASTIC (allreduce op " << op << ")");
+    DDL_REQUIRE(!q8 || !op_is_minmax(*base), DDL_STATUS_INVALID_ARGUMENT,
+                "MIN / MAX take no wire flag (allreduce op " << op << ")");
+    if (!w && !q8) return 0;
     DDL_REQUIRE(!host, DDL_STATUS_INVALID_ARGUMENT, "wire compression is for device requests only");
     DDL_REQUIRE(dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
                 "wire compression is defined for float32 only, not " << dtype_name(dtype));
+    if (q8) return kDtypeE4m3;
     return w == DDL_ALLREDUCE_WIRE_FP16 ? DDL_HALF : DDL_BFLOAT16;
+}
+
+// The e4m3 wire folds every chunk once: at most kMaxInputs + 1 ranks (more would go through partials, which
+// requantize). The one refusal of every entry point that takes the wire, before anything is registered.
+inline void check_wire_ranks(int wire, int size) {
+    DDL_REQUIRE(wire != kDtypeE4m3 || size <= 16, DDL_STATUS_INVALID_ARGUMENT,
+                "DDL_ALLREDUCE_WIRE_E4M3 takes a communicator of at most 16 ranks, not " << size);
 }
 
 // Stochastic rounding of the bf16 wire (DDL_ALLREDUCE_WIRE_STOCHASTIC; the rule, R and the host mix are
@@ -187,6 +210,7 @@ struct SegTable {
 // One N-input problem over the inputs x_0 = a, x_1 = b[0], ..., x_nb = b[nb-1]: the direct and
 // one-shot schedules' reduce of a chunk with its P-1 received copies.
 constexpr int kMaxInputs = 15;
+static_assert(kMaxInputs + 1 == 16, "check_wire_ranks: the e4m3 wire's rank cap is one fold's inputs");
 // Addition order of an N-input fold (fp32 / fp64; integers wrap, so any order is the same):
 enum FoldOrder : int {
     kFoldLeft = 0,      // ((x_0 + x_1) + x_2) + ...: the ring-0 order of the direct schedule
@@ -302,6 +326,9 @@ struct CopySeg {
     // order: 512 elements per tile, 8 per lane), then the finishing kernel and an async copy of the launch's
     // values into CopyLaunch::sumsq on its stream. The order of the additions: include/ddl_amd.h.
     bool want = false;
+    // the e4m3 wire (CopyLaunch::wire == kDtypeE4m3) only: the segment's true fp32 element count. `bytes` is
+    // whole granules there (the one place where the tensor side is not bytes x a constant: the tail)
+    size_t elems = 0;
 };
 struct CopyLaunch {  // what is per launch, not per segment
     int dir;         // 0 gather, 1 scatter, SegmentCopier::kDivInPlace, SegmentCopier::kSumsqInPlace

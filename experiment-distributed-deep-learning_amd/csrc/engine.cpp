@@ -311,13 +311,16 @@ namespace {
 }  // namespace
 
 int size_class(size_t bytes) { return bytes ? 63 - __builtin_clzll((unsigned long long)bytes) : -1; }
+// The key of a tuned class: a fold-once dtype (the e4m3 wire's granules) times another candidate list — no rings
+// at P > 2 — so its classes are kept apart from the summing dtypes' of the same bytes, 256 up.
+int tune_class(size_t bytes, int dtype) { return size_class(bytes) + (for_dtype(RingConfig{}, dtype).fold_once ? 256 : 0); }
 
 namespace {
 
 // Candidate schedules for a P-rank communicator (the configured one first). Every rank builds
 // the same list: it depends on P, the bucket size and the shared config only.
-// With ref_order every candidate is the schedule that runs (effective_config: rings at P > 2
-// become direct), duplicates dropped, so only reference-exact schedules are timed.
+// With ref_order (or fold_once: the e4m3 wire's granules) every candidate is the schedule that runs
+// (effective_config: rings at P > 2 become direct), duplicates dropped, so only those schedules are timed.
 std::vector<RingConfig> tune_candidates(int P, size_t bytes, const RingConfig &base) {
     std::vector<RingConfig> c{effective_config(base, P)};
     auto add = [&](int algo, int rings, size_t slice, int max_slices) {
@@ -327,6 +330,7 @@ std::vector<RingConfig> tune_candidates(int P, size_t bytes, const RingConfig &b
         r.slice_bytes = slice;
         r.max_slices = max_slices;
         r.ref_order = base.ref_order;
+        r.fold_once = base.fold_once;  // (its rings at P > 2 become direct too: duplicates, dropped below)
         r = effective_config(r, P);
         for (const RingConfig &x : c)
             if (x.algo == r.algo && x.rings == r.rings && x.slice_bytes == r.slice_bytes &&
@@ -448,7 +452,7 @@ TuneResult Communicator::tune_(size_t n, int dtype, hipStream_t stream, const Ri
 }
 
 RingConfig Communicator::ring_config(size_t n, int dtype, hipStream_t stream) {
-    const RingConfig base = config().ring();
+    const RingConfig base = for_dtype(config().ring(), dtype);  // (fold_once shapes the candidate list, tune_candidates)
     if (size_ <= 1 || n == 0) return base;
     agree_config(stream);
     if (!config().tune.load()) return base;
@@ -456,7 +460,7 @@ RingConfig Communicator::ring_config(size_t n, int dtype, hipStream_t stream) {
         tuned_.clear();
         tuned_hash_ = agreed_hash_;
     }
-    const int cls = size_class(n * dtype_size(dtype));
+    const int cls = tune_class(n * dtype_size(dtype), dtype);
     auto it = tuned_.find(cls);
     if (it == tuned_.end()) {
         // tuning times candidates and synchronises: inside a graph capture the configured
@@ -467,9 +471,9 @@ RingConfig Communicator::ring_config(size_t n, int dtype, hipStream_t stream) {
     return it->second.candidates[it->second.chosen];
 }
 
-TuneResult Communicator::tune_result(size_t bytes) {
+TuneResult Communicator::tune_result(size_t bytes, int dtype) {
     std::lock_guard<std::mutex> g(mu_);
-    auto it = tuned_.find(size_class(bytes));
+    auto it = tuned_.find(tune_class(bytes, dtype));
     if (it == tuned_.end() || tuned_hash_ != config().shared_hash()) return TuneResult{};
     return it->second;
 }

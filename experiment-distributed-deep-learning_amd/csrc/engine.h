@@ -178,6 +178,7 @@ struct TuneResult {
 
 // floor(log2(bytes)): the autotuner's bucket-size class.
 int size_class(size_t bytes);
+int tune_class(size_t bytes, int dtype);  // the key of a tuned class (the e4m3 wire's granules: classes of their own)
 
 // Times every candidate schedule for a P-rank bucket of `bytes` (`run` launches one allreduce
 // on `stream`), combines the per-candidate times across ranks with `agree_max` and picks the
@@ -243,7 +244,7 @@ public:
     // collectively, if this is the class's first bucket), or the configured one.
     RingConfig ring_config(size_t n, int dtype, hipStream_t stream);
     // Tuning result for the size class of `bytes` (chosen = -1 if not tuned yet).
-    TuneResult tune_result(size_t bytes);
+    TuneResult tune_result(size_t bytes, int dtype = 0);  // dtype: kDtypeE4m3 for the e4m3 wire's classes (bytes of granules)
 
     // Keyed requests: the handler (created on first use; not collective), this communicator's
     // token ring and the private data-plane communicator its handler reduces on.

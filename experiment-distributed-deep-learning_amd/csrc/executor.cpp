@@ -242,7 +242,8 @@ KernelStats RingExecutor::collect_stats() {
 }
 
 void RingExecutor::allreduce(const void *in, void *out, size_t n, int dtype, hipStream_t user,
-                             const RingConfig &cfg, int op) {
+                             const RingConfig &cfg_in, int op) {
+    const RingConfig cfg = for_dtype(cfg_in, dtype);
     const size_t es = dtype_size(dtype);
     DDL_REQUIRE(es != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported dtype " << dtype);
     check_allreduce_op(op, dtype);
@@ -264,7 +265,8 @@ void RingExecutor::allreduce(const void *in, void *out, size_t n, int dtype, hip
 }
 
 void RingExecutor::allreduce_batch(const void *const *in, void *const *out, const size_t *n, int count, int dtype,
-                                   hipStream_t user, const RingConfig &cfg, int op) {
+                                   hipStream_t user, const RingConfig &cfg_in, int op) {
+    const RingConfig cfg = for_dtype(cfg_in, dtype);
     const size_t es = dtype_size(dtype);
     DDL_REQUIRE(es != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported dtype " << dtype);
     check_allreduce_op(op, dtype);

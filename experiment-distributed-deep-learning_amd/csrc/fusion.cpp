@@ -44,7 +44,10 @@ void FusionPipe::run(const std::vector<PlanSeg> &segs, int dt, int src_dt, size_
     const size_t es = dtype_size(dt);
     DDL_REQUIRE(es != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported dtype " << dt);
     const bool cvt = src_dt != 0 && src_dt != dt;
-    const size_t ses = cvt ? dtype_size(src_dt) : es;  // the tensors' element size
+    const bool q8 = dt == kDtypeE4m3;
+    DDL_REQUIRE(!q8 || src_dt == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE, "the e4m3 wire carries float32 tensors");
+    // the tensors' element size (the e4m3 wire: of the 252 elements behind one wire element)
+    const size_t ses = q8 ? kE4m3Elems * sizeof(float) : cvt ? dtype_size(src_dt) : es;
     DDL_REQUIRE(ses != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported source dtype " << src_dt);
     // gather (dir 0) / scatter (dir 1) of one (sub-)plan on `s`: the converting kernels with a wire dtype.
     // The scatter of a (sub-)plan with a wanted non-empty piece (`all`: or an empty one) takes the sums of

@@ -14,6 +14,9 @@
 // A compressed plan (fp32 tensors over an fp16 / bf16 wire, ddl_allreduce_wire) is the same
 // pipeline over the wire stream: the converting pack / unpack kernels, cuts at 256-byte multiples
 // of the wire bytes (a tensor's offset is twice the wire offset), the allreduce in the wire dtype.
+// The e4m3 wire (dtype kDtypeE4m3 over DDL_FLOAT tensors) is a compressed plan whose wire element is one
+// 256-byte granule of 252 tensor elements: the cuts fall between granules (a tensor's offset is 1008 / 256
+// times the wire offset), a piece knows its true element count (PlanSeg::elems: the tail), and `ar` is told granules.
 //
 // One FusionPipe per engine thread: the keyed handler owns one (handler.cpp) and the thread world
 // one per virtual rank (executor.cpp, ddl_testing_thread_fused_allreduce), so the same code runs
@@ -37,15 +40,17 @@ struct PlanSeg {
     void *residual = nullptr;  // error feedback (a compressed plan): an fp32 array indexed like the tensor
     WireStream stream{};  // stochastic rounding (a compressed bf16 plan); `first`: the first element's index in its request
     bool want = false;  // the sum of squares of the result (PlanSumsq)
-    // `len` wire bytes at wire offset `off` (es / ses: the wire's / the tensors' element size): src, dst, residual, stream there
+    size_t elems = 0;  // the e4m3 wire only (bytes: whole granules): the fp32 elements of the tensors behind them
+    // `len` wire bytes at wire offset `off` (es / ses: the wire's / the tensors' element size; the e4m3 wire: a
+    // granule's 256 bytes / the 1008 bytes of its elements): src, dst, residual, stream and elems there
     PlanSeg piece(size_t off, size_t len, size_t es, size_t ses) const;
-    CopySeg pack() const { return CopySeg{const_cast<void *>(src), bytes, DDL_ALLREDUCE_OP_SUM, prescale, residual, stream, false}; }
-    CopySeg unpack() const { return CopySeg{dst, bytes, op, postscale, nullptr, WireStream{}, want}; }
+    CopySeg pack() const { return CopySeg{const_cast<void *>(src), bytes, DDL_ALLREDUCE_OP_SUM, prescale, residual, stream, false, elems}; }
+    CopySeg unpack() const { return CopySeg{dst, bytes, op, postscale, nullptr, WireStream{}, want, elems}; }
 };
 
 // A plan above `cap` bytes (a non-zero multiple of 256) as sub-plans of at most that size: a piece fills its
 // sub-plan up to cap, so every cut is a multiple of 256 bytes from the segment start. seg[k], elem[k]: piece k's
-// segment and first element in it; flat: the sub-plan's fusion-buffer bytes. No HIP call (fusion_cuts.cpp).
+// segment and first element in it (of the tensors, also with the e4m3 wire); flat: the sub-plan's fusion-buffer bytes. No HIP call (fusion_cuts.cpp).
 struct SubPlan {
     std::vector<PlanSeg> segs;
     std::vector<size_t> seg, elem;

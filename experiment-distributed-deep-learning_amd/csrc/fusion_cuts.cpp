@@ -12,6 +12,10 @@ PlanSeg PlanSeg::piece(size_t off, size_t len, size_t es, size_t ses) const {
     p.bytes = len;
     if (residual) p.residual = static_cast<char *>(residual) + e * ses;
     p.stream.first += e;
+    if (es == kE4m3Granule) {  // granules e .. e + len / es of the request's elements; the last one may be short
+        const size_t e0 = e * kE4m3Elems, e1 = e0 + len / es * kE4m3Elems;
+        p.elems = e0 >= elems ? 0 : (e1 < elems ? e1 : elems) - e0;
+    }
     return p;
 }
 
@@ -26,7 +30,7 @@ std::vector<SubPlan> cut_plan(const std::vector<PlanSeg> &segs, size_t cap, size
             const size_t len = left <= room ? left : room;
             cur.segs.push_back(segs[i].piece(off, len, es, ses));
             cur.seg.push_back(i);
-            cur.elem.push_back(off / es);
+            cur.elem.push_back(es == kE4m3Granule ? off / es * kE4m3Elems : off / es);
             cur.flat += (len + 255) & ~size_t(255);
             off += len;
         } while (off < segs[i].bytes);

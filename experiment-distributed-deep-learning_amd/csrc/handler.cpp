@@ -120,12 +120,17 @@ RequestHandler::~RequestHandler() {
 
 namespace {
 void validate(const Request &r, int size) {
-    DDL_REQUIRE(dtype_size(r.dtype) != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported dtype " << r.dtype);
+    DDL_REQUIRE(dtype_size(r.dtype) != 0 && r.dtype != kDtypeE4m3, DDL_STATUS_UNSUPPORTED_DTYPE,
+                "unsupported dtype " << r.dtype);
     switch (r.type) {
         case kReqAllreduce:
             check_allreduce_op(r.op, r.dtype);
-            DDL_REQUIRE(r.wire == 0 || (r.dtype == DDL_FLOAT && !r.host && (r.wire == DDL_HALF || r.wire == DDL_BFLOAT16)),
+            DDL_REQUIRE(r.wire == 0 || (r.dtype == DDL_FLOAT && !r.host &&
+                                        (r.wire == DDL_HALF || r.wire == DDL_BFLOAT16 || r.wire == kDtypeE4m3)),
                         DDL_STATUS_INVALID_ARGUMENT, "wire dtype " << r.wire << " on a " << dtype_name(r.dtype) << " request");
+            check_wire_ranks(r.wire, size);
+            DDL_REQUIRE(r.wire != kDtypeE4m3 || (!r.feedback && !op_is_minmax(r.op)), DDL_STATUS_INVALID_ARGUMENT,
+                        "the e4m3 wire takes SUM or AVG and no error feedback");
             DDL_REQUIRE(!r.feedback || r.wire != 0, DDL_STATUS_INVALID_ARGUMENT, "error feedback without a wire dtype");
             DDL_REQUIRE(!r.stochastic || (r.wire == DDL_BFLOAT16 && !r.feedback), DDL_STATUS_INVALID_ARGUMENT,
                         "stochastic rounding takes the bfloat16 wire and no error feedback");
@@ -476,11 +481,20 @@ void RequestHandler::wait_inputs_(const Request &r, std::vector<hipEvent_t> &wai
 
 namespace {
 // fn(src, dst, bytes) for the element slice of every request (reqs[group[q]]) inside plan p.
+// What a request's plans and cuts count: its elements, or with the e4m3 wire its granules of 252.
+size_t plan_units(const Request &r) { return r.wire == kDtypeE4m3 ? e4m3_granules(r.n) : r.n; }
+
 template <class Fn>
 void plan_slices(const Plan &p, const std::vector<Request> &reqs, const std::vector<size_t> &group, size_t es, Fn fn) {
     for (size_t q = p.req_begin; q <= p.req_end; ++q) {
         const Request &r = reqs[group[q]];
-        const size_t b = q == p.req_begin ? p.elem_begin : 0, e = q == p.req_end ? p.elem_end : r.n;
+        const size_t b = q == p.req_begin ? p.elem_begin : 0, e = q == p.req_end ? p.elem_end : plan_units(r);
+        if (r.wire == kDtypeE4m3) {  // granules b..e of an fp32 tensor: the tail is the request's, not the granule's
+            const size_t e0 = b * kE4m3Elems, e1 = std::min(e * kE4m3Elems, r.n);
+            fn(static_cast<const char *>(r.in) + e0 * sizeof(float), static_cast<char *>(r.out) + e0 * sizeof(float),
+               (e1 - e0) * sizeof(float));
+            continue;
+        }
         fn(static_cast<const char *>(r.in) + b * es, static_cast<char *>(r.out) + b * es, (e - b) * es);
     }
 }
@@ -578,7 +592,7 @@ void RequestHandler::finish_plan_(const Plan &p, const std::vector<Request> &req
                                   std::vector<Done> &dones, size_t &nplans) {
     const size_t plan = record_plan_(nplans);
     for (size_t q = p.req_begin; q <= p.req_end; ++q)
-        if (q < p.req_end || p.elem_end == reqs[group[q]].n) dones.push_back(Done{plan, group[q], DDL_STATUS_OK});
+        if (q < p.req_end || p.elem_end == plan_units(reqs[group[q]])) dones.push_back(Done{plan, group[q], DDL_STATUS_OK});
 }
 
 // allreduceRequests (MPIRingTokenCommunication.cc:105-157): dtype groups in ascending enum order,
@@ -592,7 +606,8 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
     // uncompressed requests are formed and ordered as without the flag. The reduction kind (0 SUM /
     // AVG, 1 MIN, 2 MAX) is communicated too — it is what the plan's allreduce computes — so MIN and
     // MAX requests form groups of their own after the SUM / AVG group of the same dtype and memory;
-    // a round without them forms exactly the groups it formed before.
+    // a round without them forms exactly the groups it formed before. The e4m3 wire's internal dtype id is
+    // above every ddl_dtype, so its group comes after all of these.
     auto kind_rank = [](int op) { return op == DDL_ALLREDUCE_OP_MIN ? 1 : op == DDL_ALLREDUCE_OP_MAX ? 2 : 0; };
     std::map<std::tuple<int, int, int, int>, std::vector<size_t>> groups;
     for (size_t i = 0; i < reqs.size(); ++i) {
@@ -611,10 +626,12 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
         const int sdt = comp ? DDL_FLOAT : dt;  // what the tensors hold
         // plans, the fusion threshold and the message size count wire bytes (es); the tensors'
         // slices their own (ses)
-        const size_t es = dtype_size(dt), ses = dtype_size(sdt);
+        // (the e4m3 wire: es one granule, ses the 252 fp32 elements it carries, the plans in granules)
+        const bool q8 = dt == kDtypeE4m3;
+        const size_t es = dtype_size(dt), ses = q8 ? kE4m3Elems * sizeof(float) : dtype_size(sdt);
         std::vector<size_t> elems, esz;
         for (size_t i : g.second) {
-            elems.push_back(reqs[i].n);
+            elems.push_back(plan_units(reqs[i]));
             esz.push_back(es);
         }
         const std::unique_lock<std::mutex> rg = lock_host_group_(reqs, g.second, es, host);
@@ -628,8 +645,9 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
         whole.reserve(fused ? g.second.size() : 0);
         for (size_t q = 0; fused && q < g.second.size(); ++q) {
             const Request &r = reqs[g.second[q]];
-            whole.push_back(PlanSeg{r.in, r.out, r.n * es, r.op, r.prescale, r.postscale});
+            whole.push_back(PlanSeg{r.in, r.out, plan_units(r) * es, r.op, r.prescale, r.postscale});
             whole.back().want = r.sumsq != nullptr;
+            if (q8) whole.back().elems = r.n;
             if (wire_opts && r.feedback) whole.back().residual = residual_(r);
             if (wire_opts && r.stochastic) whole.back().stream = WireStream{stochastic_stream_(r), 0, 1};
         }
@@ -674,7 +692,7 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
                 // the scale factors: (g (x) a) (x) b in one in-place launch behind the copy, each factor
                 // skipped when it is 1 (two launches when both are present: two separately rounded products)
                 size_t q = p.req_begin;
-                plan_slices(p, reqs, g.second, ses, [&](const char *s, char *d, size_t n) {
+                plan_slices(p, reqs, g.second, q8 ? sizeof(float) : ses, [&](const char *s, char *d, size_t n) {
                     const Request &r = reqs[g.second[q]];
                     if (s != d && n) DDL_HIP(hipMemcpyAsync(d, s, n, hipMemcpyDeviceToDevice, stream_));
                     if (n && r.prescale != 1.0f) scale_in_place_(d, n, sdt, DDL_ALLREDUCE_OP_SUM, 1, r.prescale);
@@ -713,11 +731,11 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
                 // requests' sequence numbers: that is not undone.
                 // (a plan of the whole group, the usual one, is run from the group's vector)
                 const bool all = p.req_begin == 0 && p.elem_begin == 0 && p.req_end + 1 == whole.size() &&
-                                 p.elem_end == reqs[g.second[p.req_end]].n;
+                                 p.elem_end == plan_units(reqs[g.second[p.req_end]]);
                 std::vector<PlanSeg> slices;
                 slices.reserve(all ? 0 : p.req_end - p.req_begin + 1);
                 for (size_t q = p.req_begin; q <= p.req_end && !all; ++q) {
-                    const size_t b = q == p.req_begin ? p.elem_begin : 0, e = q == p.req_end ? p.elem_end : reqs[g.second[q]].n;
+                    const size_t b = q == p.req_begin ? p.elem_begin : 0, e = q == p.req_end ? p.elem_end : plan_units(reqs[g.second[q]]);
                     slices.push_back(whole[q].piece(b * es, (e - b) * es, es, ses));
                 }
                 const std::vector<PlanSeg> &segs = all ? whole : slices;

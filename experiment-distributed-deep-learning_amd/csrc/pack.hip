@@ -12,7 +12,7 @@
 // tile, the tile's segment from a one-byte-per-tile index built on the device (k_tile_index).
 // One kernel, k_seg, walks the tiles for every operation; what an operation does to a 16-byte
 // unit and to a single element is its Op struct (CopyOp, DivOp, CvtPackOp, CvtUnpackOp, ScaleGatherOp,
-// ScaleGather16Op).
+// ScaleGather16Op, Q8PackOp, Q8UnpackOp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,6 +26,7 @@
 
 #include "common.h"
 #include "deptrace.h"
+#include "e4m3.h"
 
 namespace ddl {
 
@@ -591,6 +592,113 @@ template <int WIRE, bool SCALE = false> struct CvtUnpackOp {
     }
 };
 
+// ---- the e4m3 wire (DDL_ALLREDUCE_WIRE_E4M3: fp32 tensors, 256-byte granules in the flat buffer) ----
+// Q8PackOp / Q8UnpackOp: the tiles are defined on the WIRE side, as the converting copies': SegDesc::len / off
+// count granule bytes (whole granules: len is a multiple of 256, so the walk takes every lane through vec()
+// and a 16-lane row — one granule — is always whole), a 1 KiB tile is 4 granules and 1008 elements. The
+// tensor side is not len x a constant at the tail, so the launch carries one SegElems per segment: the true
+// element count. The lane whose unit is wire byte b works on granule b / 256 at row position r = b / 16 % 16.
+// The mapping follows the TENSOR side, which moves four fifths of the bytes: a granule's 252 elements are 63
+// 16-byte fp32 vectors, and lane r takes vectors r, 16 + r, 32 + r, 48 + r (vector 63 does not exist: lane
+// 15 takes three), so each of the four load / store instructions of a row covers 256 contiguous tensor bytes
+// (a first version gave lane r the 16 consecutive elements of its own wire unit, 64-byte strides between the
+// lanes of one instruction: the unpack took 3.98 and the pack 1.26 of their bf16 counterparts' time,
+// profiles/wire_e4m3/e4m3_probe_lane_contiguous.json). The codes of vector v are wire dword v of the granule:
+// four dword accesses per lane, 64 contiguous bytes per row each; dword 63 — lane 15's fourth — is the scale.
+// A tensor that is only 4-byte aligned and the vectors over the request's tail go element by element, elements
+// past the end counting as +0.0. 4 + 256/252 bytes moved per element. The rule itself — amax over the row, the
+// scale, the rounding, the NaN code — is e4m3.h's quantize_row; the prescale (SCALE) ahead of it through mul_rn.
+// Unpack: code x scale (every lane loads its granule's scale dword), then Chain: AVG's quotient, the postscale.
+struct SegElems {
+    uint64_t n;
+};
+
+template <bool SCALE = false> struct Q8PackOp {
+    static constexpr uint32_t kUnit = 1;
+    char *fl;
+    const float *tp;
+    uint64_t n;
+    bool v;
+    Factor<SCALE> fac;
+    template <class... A>
+    __device__ Q8PackOp(char *flat, const SegDesc &sd, int seg, A... a)
+        : fl(flat + sd.off), tp(reinterpret_cast<const float *>(sd.ptr)), n(arg_of<const SegElems *>(a...)[seg].n),
+          v((sd.vec & kSegVec) != 0), fac(sd, seg, a...) {}
+    __device__ bool vector() const { return true; }  // whole granules: the edges are the tensor side's, below
+    __device__ void vec(uint64_t b) const {
+        const int r = (int)(b >> 4) & 15;
+        const uint64_t g0 = (b >> 8) * kE4m3Elems;  // the granule's first element
+        float x[16];
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const int vi = 16 * h + r;  // the granule's vector
+            const uint64_t e = g0 + (uint64_t)vi * 4;
+            F32x4 q;
+            q.v = u32x4{0, 0, 0, 0};
+            if (vi < 63) {
+                if (v && e + 4 <= n) {
+                    q.v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(tp + e));
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (e + k < n) q.e[k] = __builtin_nontemporal_load(tp + e + k);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) x[4 * h + k] = q.e[k];
+        }
+        fac(x);
+        const u32x4 w = e4m3::quantize_row(x, r);
+        uint32_t *dst = reinterpret_cast<uint32_t *>(fl + (b & ~uint64_t(255))) + r;
+#pragma unroll
+        for (int h = 0; h < 4; ++h) __builtin_nontemporal_store(w[h], dst + 16 * h);
+    }
+    __device__ void elem(uint64_t) const {}
+};
+
+template <bool SCALE = false> struct Q8UnpackOp {
+    static constexpr uint32_t kUnit = 1;
+    const char *fl;
+    float *tp;
+    uint64_t n;
+    Chain<kDivF32, SCALE> val;
+    bool v;
+    template <class... A>
+    __device__ Q8UnpackOp(const char *flat, const SegDesc &sd, int seg, float dv, A... a)
+        : fl(flat + sd.off), tp(reinterpret_cast<float *>(sd.ptr)), n(arg_of<const SegElems *>(a...)[seg].n),
+          val(sd, seg, dv, a...), v((sd.vec & kSegVec) != 0) {}
+    __device__ bool vector() const { return true; }
+    __device__ void vec(uint64_t b) const {
+        const int r = (int)(b >> 4) & 15;
+        const uint64_t g0 = (b >> 8) * kE4m3Elems;
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(fl + (b & ~uint64_t(255)));
+        u32x4 raw;
+#pragma unroll
+        for (int h = 0; h < 4; ++h) raw[h] = __builtin_nontemporal_load(src + 16 * h + r);
+        const float s = __uint_as_float(__builtin_nontemporal_load(src + 63));
+        float y[16];
+        e4m3::dequantize(raw, s, y);
+        val(y);
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const int vi = 16 * h + r;
+            const uint64_t e = g0 + (uint64_t)vi * 4;
+            if (vi >= 63) continue;
+            if (v && e + 4 <= n) {
+                F32x4 q;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) q.e[k] = y[4 * h + k];
+                __builtin_nontemporal_store(q.v, reinterpret_cast<u32x4 *>(tp + e));
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (e + k < n) __builtin_nontemporal_store(y[4 * h + k], tp + e + k);
+            }
+        }
+    }
+    __device__ void elem(uint64_t) const {}
+};
+
 // ScaleGatherOp: the uncompressed prescale, tensor -> flat. Whole fp32 elements (kUnit 4): CopyOp moves
 // bytes, so it has no twin to fold into.
 struct ScaleGatherOp {
@@ -964,6 +1072,7 @@ void SegmentCopier::run(const CopyLaunch &how, const CopySeg *segs, int count) {
     uint64_t tiles = 0;
     const bool plain = segs == plain_.data();  // copy()'s own segments: every option at its default
     const bool h16 = !wire && dtype == DDL_BFLOAT16;  // native 16-bit tensors whose factors and statistic have kernels
+    const bool q8 = wire == kDtypeE4m3;  // the e4m3 wire: granules in the flat buffer, the element counts in a table
     for (int i = 0; i < n; ++i) {
         const CopySeg &sg = segs[i];
         wanted |= sg.want;
@@ -981,16 +1090,22 @@ void SegmentCopier::run(const CopyLaunch &how, const CopySeg *segs, int count) {
     fbk = fbk && wire && dir == 0;  // a converting pack's
     srk = srk && wire && dir == 0;
     sc = sc && (dir == 0 || dir == 1 || dir == kDivInPlace);
-    stat = stat && (dir == 1 || dir == kSumsqInPlace);
+    // the e4m3 unpack takes no statistic itself: one read-only pass over the outputs behind it (below)
+    const bool q8stat = q8 && stat && dir == 1 && how.sumsq;
+    stat = stat && (dir == 1 || dir == kSumsqInPlace) && !q8;
     // the quotient where it is not the identity (kSumsqInPlace: the segments hold their results, nothing is
     // divided; a converting pack has no ops)
     div = div && divisor > 1 && (wire ? dir == 1 : dir != kSumsqInPlace);
     if (wire) {
         DDL_REQUIRE(dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
                     "wire compression is defined for float32 sources, not " << dtype_name(dtype));
-        DDL_REQUIRE(wire == DDL_HALF || wire == DDL_BFLOAT16, DDL_STATUS_UNSUPPORTED_DTYPE,
+        DDL_REQUIRE(wire == DDL_HALF || wire == DDL_BFLOAT16 || q8, DDL_STATUS_UNSUPPORTED_DTYPE,
                     "wire dtype " << wire << " is neither float16 nor bfloat16");
-        DDL_REQUIRE(dir == 0 || dir == 1 || dir == kSumsqInPlace, DDL_STATUS_INVALID_ARGUMENT, "copier direction " << dir);
+        DDL_REQUIRE(dir == 0 || dir == 1 || (dir == kSumsqInPlace && !q8), DDL_STATUS_INVALID_ARGUMENT,
+                    "copier direction " << dir);
+        for (int i = 0; i < n && q8; ++i)
+            DDL_REQUIRE(segs[i].bytes == e4m3_granules(segs[i].elems) * kE4m3Granule && !segs[i].residual && !segs[i].stream.on,
+                        DDL_STATUS_INVALID_ARGUMENT, "segment " << i << " is not the granules of its elements");
         DDL_REQUIRE(divisor >= 1, DDL_STATUS_INVALID_ARGUMENT, "divisor " << divisor);
         require_f32_segments(segs, n, 2);
         for (int i = 0; i < n && fbk; ++i)
@@ -1059,8 +1174,9 @@ void SegmentCopier::run(const CopyLaunch &how, const CopySeg *segs, int count) {
     // descriptors, then the block bases, then (feedback pack) one residual address per segment or
     // (stochastic pack) one WireStream per segment, then (scaled launch) one factor per segment
     const size_t rtab = (table + nblk * sizeof(uint32_t) + 7) & ~size_t(7);
-    const size_t wtab = fbk ? rtab + (size_t)count * sizeof(uint64_t) : rtab;
-    const size_t stab = srk ? wtab + (size_t)count * sizeof(WireStream) : fbk ? wtab : table + nblk * sizeof(uint32_t);
+    // (the e4m3 wire: one SegElems per segment where a feedback pack has its residual addresses)
+    const size_t wtab = fbk || q8 ? rtab + (size_t)count * sizeof(uint64_t) : rtab;
+    const size_t stab = srk ? wtab + (size_t)count * sizeof(WireStream) : fbk || q8 ? wtab : table + nblk * sizeof(uint32_t);
     const size_t need = sc ? stab + (size_t)count * sizeof(float) : stab;
     if (need > sl.cap) {  // outgrown tables kept until ddl_finalize: no hipFree on a data path (engine.h)
         retire_host(sl.host);
@@ -1092,6 +1208,7 @@ void SegmentCopier::run(const CopyLaunch &how, const CopySeg *segs, int count) {
         uint64_t *rt = reinterpret_cast<uint64_t *>(static_cast<char *>(sl.host) + rtab);
         for (int i = 0; i < count; ++i) rt[i] = segs[i].bytes ? reinterpret_cast<uint64_t>(segs[i].residual) : 0;
     }
+    for (int i = 0; i < count && q8; ++i) reinterpret_cast<SegElems *>(static_cast<char *>(sl.host) + rtab)[i].n = segs[i].elems;
     for (int i = 0; i < count && srk; ++i) reinterpret_cast<WireStream *>(static_cast<char *>(sl.host) + wtab)[i] = segs[i].stream;
     for (int i = 0; i < count && sc; ++i) reinterpret_cast<float *>(static_cast<char *>(sl.host) + stab)[i] = segs[i].scale;
     // block b's base: the segment of tile b * 128 (the last one with tile0 <= it, as
@@ -1167,6 +1284,10 @@ void SegmentCopier::run(const CopyLaunch &how, const CopySeg *segs, int count) {
             } else if (stat) {
                 if (wire) with_wire(wire, sumsq);
                 else sumsq(std::integral_constant<int, -1>{});
+            } else if (q8) {
+                const SegElems *cnt = reinterpret_cast<const SegElems *>(res);
+                if (dir != 0) seg((Q8UnpackOp<SCALE> *)nullptr, (float)divisor, cnt);
+                else seg((Q8PackOp<SCALE> *)nullptr, cnt);
             } else if (wire) {
                 with_wire(wire, [&](auto w) {
                     constexpr int W = decltype(w)::value;
@@ -1210,10 +1331,12 @@ void SegmentCopier::run(const CopyLaunch &how, const CopySeg *segs, int count) {
         std::vector<dep::Access> acc;
         const bool gather = dir == 0 || dir == kSumsqInPlace;  // segments read (and the flat buffer written)
         if (!in_place) acc.push_back(gather ? dep::wr(flat, off) : dep::rd(flat, off));
-        const size_t widen = wire ? dtype_size(dtype) / dtype_size(wire) : 1;  // the tensor side in its own bytes
+        const size_t widen = wire && !q8 ? dtype_size(dtype) / dtype_size(wire) : 1;  // the tensor side in its own bytes
         for (int i = 0; i < count; ++i)
-            if (segs[i].bytes)
-                acc.push_back(gather ? dep::rd(segs[i].ptr, segs[i].bytes * widen) : dep::wr(segs[i].ptr, segs[i].bytes * widen));
+            if (segs[i].bytes) {
+                const size_t tb = q8 ? segs[i].elems * sizeof(float) : segs[i].bytes * widen;
+                acc.push_back(gather ? dep::rd(segs[i].ptr, tb) : dep::wr(segs[i].ptr, tb));
+            }
         for (int i = 0; i < count && fbk; ++i)
             if (segs[i].bytes && segs[i].residual) {  // read and written: both, so the race check sees either side
                 acc.push_back(dep::rd(segs[i].residual, segs[i].bytes * widen));
@@ -1224,6 +1347,11 @@ void SegmentCopier::run(const CopyLaunch &how, const CopySeg *segs, int count) {
                      : std::string(dir == 0 ? "pack" : "unpack") + (wire ? " cvt" : "") + (fbk ? " fb" : "") + (srk ? " sr" : "") +
                            (div && !sc && !stat ? " avg" : "") + (sc ? " scale" : "") + (stat ? " sumsq" : "");
         dep::op(stream, label, std::move(acc));
+    }
+    if (q8stat) {  // the canonical uncompressed sums over what the unpack stored: one extra read of the outputs
+        std::vector<CopySeg> f32(segs, segs + count);
+        for (CopySeg &sg : f32) sg.bytes = sg.elems * sizeof(float), sg.scale = 1.0f, sg.op = DDL_ALLREDUCE_OP_SUM;
+        run(CopyLaunch{kSumsqInPlace, nullptr, stream, DDL_FLOAT, 0, 1, how.sumsq}, f32.data(), count);
     }
 }
 

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "common.h"
+#include "e4m3.h"
 
 namespace ddl {
 namespace {
@@ -485,6 +486,73 @@ __global__ void __launch_bounds__(kFoldThreads) k_sumN_tile(FoldBatch fb) {
     }
 }
 
+// ---- the fold of the e4m3 wire (kDtypeE4m3: DDL_ALLREDUCE_WIRE_E4M3) --------------------------------
+// k_foldq<NB>: the N-input fold over 256-byte granules (t.n counts granules), in k_sumN_tile's tile form: one
+// 2 KiB tile = 8 granules per 128-lane workgroup, one buffer_load_dwordx4 per input through one descriptor per
+// input tile (lanes past the tile's last unit read 0 and drop their store; a granule is 16 units, so a 16-lane
+// row is whole inside or whole outside), all NB + 1 loads in flight before the first add, the cache bits of
+// fold_variant. Per lane: its 16 codes of every input decoded and multiplied by the input granule's scale (from
+// lane 15 of the row) — exact — and added in fp32 left to right in the order of the inputs, one rounding per
+// add, into 16 accumulators; then the pack's rule (e4m3.h quantize_row: amax over the row, scale, RNE; a NaN
+// sum is 0x7f, an overflowed one 0x7f | sign) writes the output granule. Whoever builds the table hands the inputs over in RANK order. SUM only.
+// HBM bytes per gradient element: (nb + 2) * 256 / 252.
+template <int NB, int FV>
+__global__ void __launch_bounds__(kFoldThreads) k_foldq(FoldBatch fb) {
+    const SegTableN &t = fb.t[blockIdx.y];
+    constexpr uint64_t kTileVec = kFoldThreads;
+    constexpr int kLoadAux = (FV & 1) ? kAuxNt : 0;
+    constexpr int kStoreAux = ((FV & 2) ? kAuxNt : 0) | ((FV & 4) ? (kAuxSc0 | kAuxSc1) : 0);
+    const uint64_t nv = t.n * (kE4m3Granule / 16);
+    const uint64_t base = (uint64_t)blockIdx.x * kTileVec;
+    if (base >= nv) return;
+    const int bytes = (int)((nv - base < kTileVec ? nv - base : kTileVec) * 16);
+    const int off = (int)threadIdx.x * 16;
+    u32x4 raw[NB + 1];
+    raw[0] = __builtin_amdgcn_raw_buffer_load_b128(
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<u32x4 *>(static_cast<const u32x4 *>(t.a) + base), 0, bytes, kRsrcWord3),
+        off, 0, kLoadAux);
+#pragma unroll
+    for (int k = 0; k < NB; ++k)
+        raw[k + 1] = __builtin_amdgcn_raw_buffer_load_b128(
+            __builtin_amdgcn_make_buffer_rsrc(const_cast<u32x4 *>(static_cast<const u32x4 *>(t.b[k]) + base), 0, bytes,
+                                              kRsrcWord3),
+            off, 0, kLoadAux);
+    const int r = (int)threadIdx.x & 15;
+    float acc[16];
+    e4m3::dequantize(raw[0], e4m3::row_scale(raw[0][3]), acc);
+#pragma unroll
+    for (int k = 1; k <= NB; ++k) {
+        float x[16];
+        e4m3::dequantize(raw[k], e4m3::row_scale(raw[k][3]), x);
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[e] = acc[e] + x[e];
+    }
+    __builtin_amdgcn_raw_buffer_store_b128(
+        e4m3::quantize_row<true>(acc, r),
+        __builtin_amdgcn_make_buffer_rsrc(static_cast<u32x4 *>(t.out) + base, 0, bytes, kRsrcWord3), off, 0, kStoreAux);
+}
+
+template <int NB>
+void launch_foldq_nb(const FoldBatch &b, hipStream_t stream) {
+    if constexpr (NB > kMaxInputs) {
+        fail(DDL_STATUS_INVALID_ARGUMENT, "too many reduce inputs");
+    } else {
+        if (b.t[0].nb != NB) return launch_foldq_nb<NB + 1>(b, stream);
+        uint64_t max_n = 0, total = 0;
+        for (int i = 0; i < b.count; ++i) {
+            max_n = b.t[i].n > max_n ? b.t[i].n : max_n;
+            total += b.t[i].n;
+        }
+        const uint64_t tiles = (max_n * (kE4m3Granule / 16) + kFoldThreads - 1) / kFoldThreads;
+        DDL_REQUIRE(tiles < (1ull << 31), DDL_STATUS_INVALID_ARGUMENT, "segment too large: " << max_n << " granules");
+        const dim3 grid((unsigned)tiles, (unsigned)b.count);
+        const int forced = g_fold_variant.load(std::memory_order_relaxed);
+        const int fv = forced >= 0 ? forced : fold_variant((size_t)total * kE4m3Granule);
+        if (fv == 4) hipLaunchKernelGGL((k_foldq<NB, 4>), grid, dim3(kFoldThreads), 0, stream, b);
+        else hipLaunchKernelGGL((k_foldq<NB, 5>), grid, dim3(kFoldThreads), 0, stream, b);
+    }
+}
+
 // ---- run form of the fold (large chunks) ----------------------------------------------------
 // The tile form above has every workgroup read one 2 KiB tile of all NB + 1 inputs at once, so
 // the chip streams NB + 2 address streams in lock step — and HBM delivers less the more streams
@@ -909,6 +977,15 @@ void launch_sumN_batch(const SegTableN *t, int count, int dtype, hipStream_t str
         b.t[b.count++] = t[i];
     }
     if (b.count == 0) return;
+    if (dtype == kDtypeE4m3) {  // granules: k_foldq, the inputs as handed over (rank order), left to right
+        DDL_REQUIRE(op == DDL_ALLREDUCE_OP_SUM, DDL_STATUS_INVALID_ARGUMENT, "the e4m3 wire sums");
+        for (int i = 0; i < b.count; ++i)
+            DDL_REQUIRE(fold_aligned(b.t[i]) && b.t[i].order == kFoldLeft, DDL_STATUS_INVALID_ARGUMENT,
+                        "an e4m3 fold takes 16-byte aligned granules and the left order");
+        launch_foldq_nb<1>(b, stream);
+        DDL_HIP(hipGetLastError());
+        return;
+    }
     if (op != DDL_ALLREDUCE_OP_SUM)  // associative: every order is the left fold's instance
         for (int i = 0; i < b.count; ++i) b.t[i].order = kFoldLeft;
     with_combine(dtype, op, [&](auto id) { launch_sumN_dt<decltype(id)::value>(b, stream); });
@@ -962,6 +1039,15 @@ int ring_variant() { return kNtLoadA; }
 void launch_sum2(const SegTable &t, int dtype, hipStream_t stream, int variant, int op) {
     DDL_REQUIRE(t.count >= 1 && t.count <= kMaxSegments, DDL_STATUS_INVALID_ARGUMENT,
                 "segment count " << t.count << " outside [1, " << kMaxSegments << "]");
+    if (dtype == kDtypeE4m3) {  // the ring's single step at P = 2: k_foldq with one received input
+        SegTableN f[kMaxSegments];
+        for (int s = 0; s < t.count; ++s) {
+            f[s].a = t.a[s], f[s].b[0] = t.b[s], f[s].out = t.out[s], f[s].n = t.n[s], f[s].nb = 1;
+        }
+        static_assert(kMaxSegments <= kMaxFoldBatch, "one fold batch per reduce table");
+        launch_sumN_batch(f, t.count, dtype, stream, op);
+        return;
+    }
     const size_t es = dtype_size(dtype);
     DDL_REQUIRE(es != 0, DDL_STATUS_UNSUPPORTED_DTYPE, "unsupported dtype " << dtype);
     uint64_t max_n = 0, total_n = 0;

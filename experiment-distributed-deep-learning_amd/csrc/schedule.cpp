@@ -422,6 +422,9 @@ void build_program(RingProgram &prog, int rank, int P, const void *in, void *out
                    size_t n, int dtype, const RingConfig &cfg_in) {
     const RingConfig cfg = effective_config(cfg_in, P);
     const size_t es = dtype_size(dtype);
+    // the callers' refusal (check_wire_ranks) comes first; this is the builder's own invariant
+    DDL_REQUIRE(cfg.fold_once == for_dtype(RingConfig{}, dtype).fold_once && (!cfg.fold_once || P <= kMaxInputs + 1),
+                DDL_STATUS_ERROR_UNKNOWN, "fold-once program: dtype " << dtype << ", " << P << " ranks");
     prog.P = P;
     prog.rank = rank;
     prog.n = n;
@@ -434,8 +437,10 @@ void build_program(RingProgram &prog, int rank, int P, const void *in, void *out
     // fold order of the direct / one-shot N-input reduce (kFoldLeft: ring 0's order)
     // (fp16 / bf16, which the reference rejects, always fold left in fp32)
     const bool half = dtype == DDL_HALF || dtype == DDL_BFLOAT16;
-    const int order =
-        cfg.ref_order && !half ? mpich_fold_order(cfg.order_bytes ? cfg.order_bytes : n * es, es, P) : kFoldLeft;
+    // (a fold-once dtype: left to right over the ranks in rank order, always)
+    const int order = cfg.ref_order && !half && !cfg.fold_once
+                          ? mpich_fold_order(cfg.order_bytes ? cfg.order_bytes : n * es, es, P)
+                          : kFoldLeft;
     if (cfg.algo == kAlgoOneShot) {
         build_oneshot(prog, rank, P, static_cast<const char *>(in), static_cast<char *>(out),
                       static_cast<char *>(staging), n, es, order);
@@ -448,7 +453,7 @@ void build_program(RingProgram &prog, int rank, int P, const void *in, void *out
     }
     if (is_direct(cfg.algo)) {
         build_direct(prog, rank, P, static_cast<const char *>(in), static_cast<char *>(out),
-                     static_cast<char *>(staging), n, es, order, cfg.ref_order != 0,
+                     static_cast<char *>(staging), n, es, order, cfg.ref_order != 0 || cfg.fold_once != 0,
                      cfg.algo == kAlgoDirectGather && direct_gather_eligible(n, es, P));
         return;
     }
@@ -492,6 +497,8 @@ void build_program(RingProgram &prog, int rank, int P, const void *in, void *out
                     const int c = t.reduce.count++;
                     t.reduce.a[c] = inb + rs.begin * es;
                     t.reduce.b[c] = st;
+                    // (fold once: P = 2, one step; the two inputs in rank order on both ranks)
+                    if (cfg.fold_once && pred[j] < rank) std::swap(t.reduce.a[c], t.reduce.b[c]);
                     t.reduce.out[c] = outb + rs.begin * es;
                     t.reduce.n[c] = rs.size();
                 }

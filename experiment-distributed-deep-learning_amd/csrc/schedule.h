@@ -109,12 +109,22 @@ struct RingConfig {
     // 0: direct folds left in ring 0's order, the ring runs as configured.
     int ref_order = 0;
     size_t order_bytes = 0;  // message size that picks MPICH's algorithm (0 = this bucket's)
+    // The reduce is not a dtype's sum and may run only once per chunk (kDtypeE4m3, the e4m3 wire: the fold
+    // requantizes its result). Set from the dtype by for_dtype — RingExecutor::allreduce[_batch] for what runs,
+    // Communicator::ring_config for the tuner's candidate list — never by a caller: the
+    // fold-once schedules only (a ring at P > 2 runs as the direct schedule), the inputs in rank order, left
+    // to right, whatever ref_order says; at most kMaxInputs + 1 ranks (no partials).
+    int fold_once = 0;
 };
+inline RingConfig for_dtype(RingConfig c, int dtype) {
+    if (dtype == kDtypeE4m3) c.fold_once = 1;
+    return c;
+}
 
 // The schedule that actually runs for P ranks: with ref_order, a ring at P > 2 becomes the
 // direct schedule with the same slicing. Every builder and shape query goes through it.
 inline RingConfig effective_config(RingConfig c, int P) {
-    if (c.ref_order && c.algo == kAlgoRing && P > 2) {
+    if ((c.ref_order || c.fold_once) && c.algo == kAlgoRing && P > 2) {
         c.algo = kAlgoDirect;
         c.rings = 1;
     }

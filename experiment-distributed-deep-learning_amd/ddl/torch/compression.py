@@ -39,6 +39,15 @@ index, so the ranks round independently and the noise of the sum averages down w
 residual, has nothing to reset, moves the plain bf16 pack's 6 bytes per element, and unlike feedback it
 removes the bias but not the per-step noise. The engine keeps one 8-byte counter per name, so — as with
 feedback — only for names that are stable from step to step. bf16 only: fp16's limit is range.
+
+8 bits: `Compression.fp8` sends every 252 gradient values as 252 OCP e4m3fn codes plus one power-of-two fp32
+scale (a 256-byte granule: include/ddl_amd.h, DDL_ALLREDUCE_WIRE_E4M3): a quarter of fp32's bytes per hop, half
+of the 16-bit wires'. An 8-bit float cannot be summed hop by hop, so the engine quantizes exactly twice whatever
+the size is — each rank's contribution in the pack, the fp32 sum of all ranks in the kernel that folds them —
+and runs these requests on its fold-once schedules. The per-granule scale removes the range problem (no
+predivide factor or loss scale is needed for the wire's sake; both still compose), what remains is precision:
+3 mantissa bits, an error below amax / 14 of each granule per quantization. It keeps no per-name state, so
+fresh names are fine (allreduce_gradient takes it); communicators of at most 16 ranks; SUM and AVG only.
 """
 from ddl.torch import cpp_backend as cb
 
@@ -68,13 +77,16 @@ class Compression:
     14-byte-per-element pack instead of 6; `reset_error_feedback()` after loading a checkpoint or
     a large change of the loss scale). `bf16_stochastic` rounds onto the bf16 wire stochastically
     (module docstring: unbiased, no residual, nothing to reset, the plain 6-byte pack; one 8-byte
-    counter per request name). allreduce_gradient takes neither the `_feedback` kinds nor it."""
+    counter per request name). allreduce_gradient takes neither the `_feedback` kinds nor it. `fp8`: block-scaled
+    e4m3 granules, quantized once per contribution and once per sum (module docstring: no per-name state, at most
+    16 ranks)."""
     none = _Wire('none', 0)
     fp16 = _Wire('fp16', cb.WIRE_FP16)
     bf16 = _Wire('bf16', cb.WIRE_BF16)
     fp16_feedback = _Wire('fp16_feedback', cb.WIRE_FP16 | cb.WIRE_FEEDBACK)
     bf16_feedback = _Wire('bf16_feedback', cb.WIRE_BF16 | cb.WIRE_FEEDBACK)
     bf16_stochastic = _Wire('bf16_stochastic', cb.WIRE_BF16 | cb.WIRE_STOCHASTIC)
+    fp8 = _Wire('fp8', cb.WIRE_E4M3)
 
 
 def wire_flag(compression) -> int:
@@ -82,8 +94,8 @@ def wire_flag(compression) -> int:
     if compression is None:
         return 0
     if not isinstance(compression, _Wire):
-        raise TypeError('compression must be Compression.none, .fp16, .bf16, .fp16_feedback, .bf16_feedback or '
-                        f'.bf16_stochastic, not {compression!r}')
+        raise TypeError('compression must be Compression.none, .fp16, .bf16, .fp16_feedback, .bf16_feedback, '
+                        f'.bf16_stochastic or .fp8, not {compression!r}')
     return compression.flag
 
 

@@ -44,6 +44,7 @@ OP_MIN, OP_MAX = 3, 4  # element-wise IEEE 754-2019 minimum / maximum (integers:
 WIRE_FP16, WIRE_BF16 = 0x100, 0x200  # enum ddl_allreduce_wire: OR-ed into a keyed fp32 device request's op
 WIRE_FEEDBACK = 0x1000  # error feedback: only together with exactly one of the two wire flags
 WIRE_STOCHASTIC = 0x8000  # stochastic rounding: only together with WIRE_BF16, never with WIRE_FEEDBACK
+WIRE_E4M3 = 0x20000  # enum ddl_allreduce_wire8: block-scaled e4m3fn granules; no other wire bit with it
 SUMSQ = 0x2000  # enum ddl_allreduce_stat: `user` points to a SumsqArg (struct ddl_sumsq_arg)
 SCALE = 0x4000  # enum ddl_allreduce_scale: `user` points to a ScaleArg (struct ddl_scale_arg)
 MEMORY_DEVICE, MEMORY_HOST = 0, 1  # enum ddl_memory
@@ -235,6 +236,15 @@ class CPPBackend:
             ctypes.POINTER(sz), ctypes.POINTER(sz), ci, ctypes.POINTER(ci))
         sig('ddl_testing_stochastic_stream', ci, ctypes.c_ulonglong, ci, ctypes.c_char_p, ctypes.c_ulonglong, u64p)
         sig('ddl_unpack_cvt', ci, ctypes.POINTER(vp), vp, ctypes.POINTER(sz), ctypes.POINTER(ci), ci, ci, ci, vp)
+        # (testing library: the e4m3 wire's pack, unpack and fold, and the thread world over it)
+        sig('ddl_pack_e4m3', ci, vp, ctypes.POINTER(vp), ctypes.POINTER(sz), ci, fp, vp)
+        sig('ddl_unpack_e4m3', ci, ctypes.POINTER(vp), vp, ctypes.POINTER(sz), ctypes.POINTER(ci), ci, ci, fp, vp, ub, dp)
+        sig('ddl_fold_e4m3', ci, vp, vp, ctypes.POINTER(vp), ci, sz, vp)
+        sig('ddl_testing_keyed_tune_result', ci, cid, sz, ci, ctypes.POINTER(ci), ctypes.POINTER(ci),
+            ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_float), ci)
+        sig('ddl_testing_thread_fused_allreduce_e4m3', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp),
+            ctypes.POINTER(sz), ctypes.POINTER(ci), fp, fp, vp, ctypes.POINTER(sz), ub, dp, ctypes.POINTER(sz),
+            ctypes.POINTER(sz), ci, ctypes.POINTER(ci))
         sig('ddl_testing_thread_fused_allreduce_wire', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp),
             ctypes.POINTER(sz), ctypes.POINTER(ci), ci, vp, ctypes.POINTER(sz))
         sig('ddl_local_ring_allreduce', ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp), sz, ci, ci, vp)

@@ -54,6 +54,12 @@ No residual, nothing to reset, the plain 6-byte pack; the stable per-parameter n
 (step() and the `overlap_backward` hooks) are what the engine's per-name sequence numbers need.
 `ddl.torch.compression.set_stochastic_seed(seed)` chooses the random bits (the rank is mixed in).
 
+`compression=Compression.fp8`: every dense fp32 device gradient travels as block-scaled e4m3 granules (252
+codes and a power-of-two scale per 256 bytes), quantized once per rank and once for the sum, on both paths.
+It keeps no state, composes with `fused_mean`, the norm tracking, `gradient_predivide_factor`, `loss_scale`
+and `DynamicLossScaler` (the per-block scale makes neither factor necessary for the wire's sake), and takes
+communicators of at most 16 ranks.
+
 `track_grad_norm=True` (implied by `max_grad_norm` and `skip_nonfinite`): after
 `allreduce_gradients()`, `optimizer.grad_norm` is the global L2 norm of the averaged gradients (a
 float) and `optimizer.found_nonfinite` is `not math.isfinite(grad_norm)`. Every dense fp32 or bf16 device

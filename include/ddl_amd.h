@@ -90,6 +90,11 @@ enum ddl_allreduce_wire { DDL_ALLREDUCE_WIRE_FP16 = 0x100, DDL_ALLREDUCE_WIRE_BF
 /* Stochastic rounding onto the bf16 wire (MI355X extension; the data-plane section): one more bit of the
  * same `op`, valid only OR-ed with DDL_ALLREDUCE_WIRE_BF16 and never with DDL_ALLREDUCE_WIRE_FEEDBACK. */
 enum ddl_allreduce_wire_rounding { DDL_ALLREDUCE_WIRE_STOCHASTIC = 0x8000 };
+/* The block-scaled 8-bit wire (MI355X extension; "The e4m3 wire" in the data-plane section): OCP e4m3fn codes
+ * with one power-of-two fp32 scale per 252 elements. OR-ed into the `op` (SUM or AVG) of the keyed entry points
+ * for DDL_FLOAT device requests, optionally with DDL_ALLREDUCE_SUMSQ and DDL_ALLREDUCE_SCALE; never with a
+ * ddl_allreduce_wire flag, DDL_ALLREDUCE_WIRE_FEEDBACK or DDL_ALLREDUCE_WIRE_STOCHASTIC. */
+enum ddl_allreduce_wire8 { DDL_ALLREDUCE_WIRE_E4M3 = 0x20000 };
 /* Sum of squares of a keyed device allreduce of DDL_FLOAT or DDL_BFLOAT16 tensors (MI355X extension; the data-plane
  * section): OR-ed into the `op` of ddl_allreduce_submit / _submit_batch (and _submit_mem /
  * _submit_batch_mem with DDL_MEMORY_DEVICE), SUM or AVG, with or without a wire flag. With the bit
@@ -384,6 +389,41 @@ void py_error(const char *log_str);
  * alternatives; a request with both has no defined meaning here.
  * P = 1: with "one_rank_shortcut" 1 nothing is rounded and n does not advance; with 0 the data plane runs
  * and the rule applies.
+ *
+ * The e4m3 wire: DDL_ALLREDUCE_WIRE_E4M3, on a keyed DDL_FLOAT device request with op SUM or AVG, optionally
+ * with DDL_ALLREDUCE_SUMSQ and DDL_ALLREDUCE_SCALE. An 8-bit float cannot be summed hop by hop, so this wire
+ * is quantized exactly twice whatever P is: every rank's contribution once in the pack, the fp32 sum once in
+ * the kernel that folds all P contributions of a chunk (the fold-once schedules: direct, direct-gather,
+ * one-shot, gather-fold; a ring at P > 2 becomes the direct schedule, whatever "reference_order" says).
+ * tests/_e4m3_helpers.py restates everything below in NumPy / torch, bit for bit.
+ * Granule: the wire element is 256 bytes carrying 252 consecutive fp32 elements of one request: bytes 0..251
+ * one OCP e4m3fn code per element, bytes 252..255 the bits of an fp32 scale s. A request of n elements is
+ * ceil(n / 252) granules; elements past n in the last granule count as +0.0 (code 0x00). Plans, the fusion
+ * threshold, plan cuts and pipeline cuts count granules (256 wire bytes = 1008 tensor bytes).
+ * Pack, per granule: c = g, or g (x) prescale; amax = the largest |c| over the granule's FINITE elements (0
+ * if none); s = the smallest power of two with amax / s <= 448, at least 2^-126 (amax 0: 2^-126; 448 -> 1,
+ * 449 -> 2, 1.0 -> 2^-8, 1.75 -> 2^-8, 1.76 -> 2^-7); a finite element becomes RNE_e4m3(c / s) — the division
+ * is exact, subnormal codes and -0 are kept, nothing saturates — and a NaN or an infinity 0x7f | sign (e4m3fn
+ * has no infinity: an infinity comes back as NaN).
+ * Fold: x_r = code_r * s_r in fp32 (exact, fp32 subnormals included), y = ((x_0 (+) x_1) (+) x_2) ... left to
+ * right in RANK order 0..P-1 whatever the schedule, its slices or the tuner chose, every add one rounding to
+ * nearest even; y is quantized by the pack's rule into the output granule, with ONE DIFFERENCE:
+ *     A NaN SUM IS WRITTEN AS 0x7f, WHATEVER ITS SIGN BIT (the pack writes 0x7f | sign).
+ * IEEE 754 does not pin the sign of a NaN that an addition produced, so it cannot be part of a bit-exact wire. A
+ * NaN code or a NaN scale makes the element NaN; a sum that overflowed to an infinity is 0x7f | its sign. Every
+ * rank ends with the same bytes. Requantizing decoded values is lossless, so a step that only copies granules
+ * changes no value.
+ * Unpack: y = code * s, then AVG's quotient by (float)P, then the postscale, stored as fp32; only the
+ * request's n elements are written.
+ * The sum of squares is the canonical UNCOMPRESSED order above over each piece of `out` (pieces added in
+ * offset order), taken by one read-only pass over the outputs behind the unpack: one extra read of them.
+ * Like the other wires the flag is a property of the key that every rank shares; its requests form a fusion
+ * group of their own behind the existing compressed groups, and a round without it forms exactly the groups
+ * it formed before. Refusals, before anything is registered: another wire flag, WIRE_FEEDBACK or
+ * WIRE_STOCHASTIC with it, MIN / MAX, DDL_MEMORY_HOST, ddl_allreduce / ddl_allreduce_batch /
+ * ddl_allreduce_host, or a communicator of more than 16 ranks (a fold of more than 16 inputs goes through
+ * partials, which would requantize) return DDL_STATUS_INVALID_ARGUMENT; another dtype
+ * DDL_STATUS_UNSUPPORTED_DTYPE. P = 1: with "one_rank_shortcut" 1 nothing is quantized.
  *
  * MIN / MAX: DDL_ALLREDUCE_OP_MIN = 3 and DDL_ALLREDUCE_OP_MAX = 4, on every dtype and every
  * allreduce entry point. Per element over the P inputs: DDL_INT32 / DDL_INT64 in signed order,

@@ -312,6 +312,34 @@ int ddl_testing_thread_fused_allreduce_native(int nranks, int count, const void 
                                               const float *postscale, void *hip_stream, size_t *subplans,
                                               const unsigned char *want, double *sumsq_out, size_t *cut_segs,
                                               size_t *cut_elems, int max_cuts, int *ncuts);
+/* The kernels of the e4m3 wire (DDL_ALLREDUCE_WIRE_E4M3; ddl_amd.h "The e4m3 wire"; csrc/pack.hip k_seg<Q8PackOp> /
+ * k_seg<Q8UnpackOp>, csrc/reduce_kernels.hip k_foldq). The tensors hold elements[i] fp32 values (4-byte aligned);
+ * segment i of the flat buffer is its ceil(elements[i] / 252) granules of 256 bytes at the running sum of the
+ * granule bytes before it. scale: NULL, or one factor per segment as ddl_pack_scale / ddl_unpack_scale (the
+ * prescale ahead of the quantization; the postscale behind AVG's quotient). _unpack_e4m3: ops as
+ * ddl_unpack_cvt; want / sumsq_out as ddl_unpack_cvt_sumsq (want NULL: no statistic, no wait), the values in
+ * the canonical UNCOMPRESSED order over the stored outputs (one extra read-only pass).
+ * _fold_e4m3: out = the requantized fp32 sum a + ins[0] + ... + ins[nb - 1], left to right, over `granules`
+ * granules (16-byte aligned buffers; nb = 1..15; out may be one of the inputs). */
+int ddl_pack_e4m3(void *dst, const void *const *srcs, const size_t *elements, int count, const float *scale,
+                  void *hip_stream);
+int ddl_unpack_e4m3(void *const *dsts, const void *src, const size_t *elements, const int *ops, int count, int divisor,
+                    const float *scale, void *hip_stream, const unsigned char *want, double *sumsq_out);
+int ddl_fold_e4m3(void *out, const void *a, const void *const *ins, int nb, size_t granules, void *hip_stream);
+/* ddl_tune_result of the communicator's private keyed data plane (where the keyed plans' allreduces run and are
+ * tuned; the communicator itself at size 1). e4m3 != 0: the tuned classes of the e4m3 wire's allreduces, kept apart
+ * from the summing dtypes' classes of the same bytes (another candidate list: no rings at P > 2); bucket_bytes = the
+ * plan's allreduce in wire bytes. */
+int ddl_testing_keyed_tune_result(ddl_communicator_id id, size_t bucket_bytes, int e4m3, int *chosen, int *count,
+                                  long long *configs, float *ms, int max_candidates);
+/* ddl_testing_thread_fused_allreduce_scale over the e4m3 wire (no residuals): elements[i] fp32 values per
+ * segment, the plan in granules as the keyed handler runs a DDL_ALLREDUCE_WIRE_E4M3 group; cut_elems in tensor
+ * elements (multiples of 252). More than 16 virtual ranks: DDL_STATUS_INVALID_ARGUMENT. */
+int ddl_testing_thread_fused_allreduce_e4m3(int nranks, int count, const void *const *srcs, void *const *dsts,
+                                            const size_t *elements, const int *ops, const float *prescale,
+                                            const float *postscale, void *hip_stream, size_t *subplans,
+                                            const unsigned char *want, double *sumsq_out, size_t *cut_segs,
+                                            size_t *cut_elems, int max_cuts, int *ncuts);
 /* ddl_testing_thread_fused_allreduce_scale over the bf16 wire with stochastic rounding and no residuals:
  * sr_want[i] != 0 = segment i is rounded stochastically on every virtual rank, rank r with the stream key
  * streams[r * count + i] and first element index 0, handed to the plan as the keyed handler hands over its
