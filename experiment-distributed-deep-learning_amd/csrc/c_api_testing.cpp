@@ -742,6 +742,21 @@ int ddl_pack_e4m3(void *dst, const void *const *srcs, const size_t *elements, in
     });
 }
 
+int ddl_pack_e4m3_fb(void *dst, const void *const *srcs, void *const *residuals, const size_t *elements, int count,
+                     const float *scale, void *hip_stream) {
+    return guarded([&] {
+        DDL_REQUIRE(count >= 0 && (count == 0 || (dst && srcs && residuals && elements)), DDL_STATUS_INVALID_ARGUMENT,
+                    "bad pack_e4m3_fb args");
+        std::lock_guard<std::mutex> g(abi_copier_mu());
+        std::vector<CopySeg> &segs = copy_segs(count, unconst(srcs), elements, 0, nullptr, scale, residuals);
+        for (int i = 0; i < count; ++i) {
+            segs[(size_t)i].bytes = e4m3_granules(elements[i]) * kE4m3Granule;
+            segs[(size_t)i].elems = elements[i];
+        }
+        abi_copier().run(CopyLaunch{0, dst, as_stream(hip_stream), DDL_FLOAT, kDtypeE4m3}, segs.data(), count);
+    });
+}
+
 int ddl_unpack_e4m3(void *const *dsts, const void *src, const size_t *elements, const int *ops, int count, int divisor,
                     const float *scale, void *hip_stream, const unsigned char *want, double *sumsq_out) {
     return guarded([&] {
@@ -787,6 +802,27 @@ int ddl_testing_thread_fused_allreduce_e4m3(int nranks, int count, const void *c
         check_factors(prescale, postscale, count);
         FusedCall c{nranks, count, srcs, dsts, elements, 0, kDtypeE4m3, DDL_FLOAT, hip_stream, subplans};
         c.ops = ops;
+        c.prescale = prescale, c.postscale = postscale;
+        c.want = want, c.sumsq_out = sumsq_out;
+        c.cut_segs = cut_segs, c.cut_elems = cut_elems, c.max_cuts = max_cuts, c.ncuts = ncuts;
+        thread_fused(c);
+    });
+}
+
+int ddl_testing_thread_fused_allreduce_e4m3_fb(int nranks, int count, const void *const *srcs, void *const *dsts,
+                                               void *const *residuals, const size_t *elements, const int *ops,
+                                               const float *prescale, const float *postscale, void *hip_stream,
+                                               size_t *subplans, const unsigned char *want, double *sumsq_out,
+                                               size_t *cut_segs, size_t *cut_elems, int max_cuts, int *ncuts) {
+    return guarded([&] {
+        DDL_REQUIRE(nranks >= 1 && nranks <= 64 && count >= 1 && srcs && dsts && residuals && elements && (!want || sumsq_out),
+                    DDL_STATUS_INVALID_ARGUMENT, "bad thread fused allreduce");
+        check_wire_ranks(kDtypeE4m3, nranks);
+        check_float_ops(ops, count, "MIN / MAX take no wire");
+        check_factors(prescale, postscale, count);
+        FusedCall c{nranks, count, srcs, dsts, elements, 0, kDtypeE4m3, DDL_FLOAT, hip_stream, subplans};
+        c.ops = ops;
+        c.residuals = residuals;
         c.prescale = prescale, c.postscale = postscale;
         c.want = want, c.sumsq_out = sumsq_out;
         c.cut_segs = cut_segs, c.cut_elems = cut_elems, c.max_cuts = max_cuts, c.ncuts = ncuts;

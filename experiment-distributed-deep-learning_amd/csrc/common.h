@@ -103,13 +103,16 @@ inline void check_allreduce_op(int op, int dtype) {
 
 // The `op` of a keyed allreduce request: SUM / AVG / MIN / MAX in the low bits, with SUM / AVG
 // optionally one ddl_allreduce_wire format flag, optionally DDL_ALLREDUCE_WIRE_FEEDBACK with it, or
-// DDL_ALLREDUCE_WIRE_STOCHASTIC with WIRE_BF16; or DDL_ALLREDUCE_WIRE_E4M3 alone (kDtypeE4m3). Returns the wire dtype (DDL_HALF / DDL_BFLOAT16; 0 =
+// DDL_ALLREDUCE_WIRE_STOCHASTIC with WIRE_BF16; or DDL_ALLREDUCE_WIRE_E4M3 alone (kDtypeE4m3), optionally with
+// DDL_ALLREDUCE_WIRE_E4M3_FEEDBACK (then *feedback is set: the wire dtype says which rule). Returns the wire dtype (DDL_HALF / DDL_BFLOAT16; 0 =
 // uncompressed), leaves the op in *base, the feedback bit in *feedback and the stochastic bit in
 // *stochastic. Refusals as ddl_amd.h lists them, before anything is registered.
 inline int decode_keyed_op(int op, int dtype, bool host, int *base, bool *feedback, bool *stochastic) {
     constexpr int kWire = DDL_ALLREDUCE_WIRE_FP16 | DDL_ALLREDUCE_WIRE_BF16;
     const bool q8 = (op & DDL_ALLREDUCE_WIRE_E4M3) != 0;
-    *base = op & ~(kWire | DDL_ALLREDUCE_WIRE_FEEDBACK | DDL_ALLREDUCE_WIRE_STOCHASTIC | DDL_ALLREDUCE_WIRE_E4M3);
+    const bool q8fb = (op & DDL_ALLREDUCE_WIRE_E4M3_FEEDBACK) != 0;
+    *base = op & ~(kWire | DDL_ALLREDUCE_WIRE_FEEDBACK | DDL_ALLREDUCE_WIRE_STOCHASTIC | DDL_ALLREDUCE_WIRE_E4M3 |
+                   DDL_ALLREDUCE_WIRE_E4M3_FEEDBACK);
     *feedback = (op & DDL_ALLREDUCE_WIRE_FEEDBACK) != 0;
     *stochastic = (op & DDL_ALLREDUCE_WIRE_STOCHASTIC) != 0;
     const int w = op & kWire;
@@ -129,8 +132,11 @@ inline int decode_keyed_op(int op, int dtype, bool host, int *base, bool *feedba
                 "WIRE_STOCHASTIC and WIRE_FEEDBACK are alternatives (allreduce op " << op << ")");
     DDL_REQUIRE(!q8 || (!w && !*feedback && !*stochastic), DDL_STATUS_INVALID_ARGUMENT,
                 "WIRE_E4M3 takes no other wire flag, no WIRE_FEEDBACK and no WIRE_STOCHASTIC (allreduce op " << op << ")");
-    DDL_REQUIRE(!q8 || !op_is_minmax(*base), DDL_STATUS_INVALID_ARGUMENT,
+    DDL_REQUIRE(!(q8 || q8fb) || !op_is_minmax(*base), DDL_STATUS_INVALID_ARGUMENT,
                 "MIN / MAX take no wire flag (allreduce op " << op << ")");
+    DDL_REQUIRE(!q8fb || q8, DDL_STATUS_INVALID_ARGUMENT,
+                "WIRE_E4M3_FEEDBACK takes WIRE_E4M3 and no other wire flag (allreduce op " << op << ")");
+    if (q8fb) *feedback = true;
     if (!w && !q8) return 0;
     DDL_REQUIRE(!host, DDL_STATUS_INVALID_ARGUMENT, "wire compression is for device requests only");
     DDL_REQUIRE(dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
@@ -301,7 +307,7 @@ inline std::vector<size_t> host_chunk_cuts(size_t total, size_t chunk) {
 // non-empty segment of it asks for the option: every other launch is the kernel it was, its tables
 // unchanged, and a segment without the option inside such a launch is moved as it was. A launch ignores
 // what it cannot use: a converting pack `op` and `want`; a scatter `residual` and `stream`; kSumsqInPlace
-// `op` and `scale`; a non-converting launch `residual` and `stream`.
+// `op` and `scale`; a non-converting launch `residual` and `stream`; an e4m3 pack `stream`.
 struct CopySeg {
     void *ptr = nullptr;  // the tensor side: read by a pack, written by a scatter / in place
     size_t bytes = 0;     // flat-side bytes (wire bytes for a converting copy: elements x 2)
@@ -316,6 +322,8 @@ struct CopySeg {
     float scale = 1.0f;
     // DDL_ALLREDUCE_WIRE_FEEDBACK (a converting pack): the segment packs narrow(tensor + residual) and leaves
     // what the rounding removed in `residual` (fp32, the segment's element count; CvtPackOp<WIRE, true>)
+    // DDL_ALLREDUCE_WIRE_E4M3_FEEDBACK (an e4m3 pack): the granules of tensor + residual, and what their
+    // quantization removed in `residual` (fp32, `elems` elements; Q8PackOp<SCALE, true>)
     void *residual = nullptr;
     // DDL_ALLREDUCE_WIRE_STOCHASTIC (a converting bf16 pack): a segment with stream.on (and no residual) is
     // narrowed by the rule of ddl_amd.h (k_seg<CvtPackSrOp>)

@@ -85,6 +85,45 @@ template <bool SUM = false> __device__ inline u32x4 quantize_row(const float (&x
     return u32x4{w[0], w[1], w[2], w[3]};
 }
 
+// The same rule in two halves for the feedback pack (pack.hip Q8PackOp<SCALE, true>), which needs the scale on every
+// lane to decode its own codes, without a second reduction or a shuffle: row_scale_exponent — the biased exponent of
+// the granule's scale, the same on all sixteen lanes (the row reduction leaves the amax on every one) — and
+// encode_row, the lane's four dwords under that scale. Written apart from quantize_row, not under it: the kernels
+// that call quantize_row keep their instruction streams only while it stays the one function it was
+// (profiles/wire_e4m3_feedback/parent_kernels_unchanged.txt).
+__device__ inline uint32_t row_scale_exponent(const float (&x)[16], int r) {
+    const int cnt = lane_count(r);
+    uint32_t m = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const uint32_t a = __float_as_uint(x[k]) & 0x7fffffffu;
+        if (k < cnt && a < 0x7f800000u) m = a > m ? a : m;  // finite elements only
+    }
+    return scale_exponent(row_max(m));
+}
+
+__device__ inline u32x4 encode_row(const float (&x)[16], int r, const uint32_t se) {
+    const float inv = __uint_as_float((254u - se) << 23);  // 1 / s
+    uint32_t w[4];
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+        float y[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) y[k] = mul1(x[4 * h + k], inv);
+        int p = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0, false);
+        p = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], p, true);
+        uint32_t c = (uint32_t)p;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {  // a NaN or an infinity: 0x7f | sign
+            const uint32_t u = __float_as_uint(x[4 * h + k]);
+            if ((u & 0x7fffffffu) >= 0x7f800000u) c = (c & ~(0xffu << (8 * k))) | ((0x7fu | ((u >> 24) & 0x80u)) << (8 * k));
+        }
+        w[h] = c;
+    }
+    if (r == 15) w[3] = se << 23;
+    return u32x4{w[0], w[1], w[2], w[3]};
+}
+
 // code * s of the lane's 16 codes, one fp32 product each (exact; subnormals kept; a NaN code or scale gives NaN)
 __device__ inline void dequantize(const u32x4 raw, float s, float (&y)[16]) {
 #pragma unroll

@@ -37,7 +37,7 @@ struct PlanSeg {
     // AVG: the unpack stores quotients. (A MIN / MAX plan holds that one kind: `ar` reduces with it, the unpack copies.)
     int op = DDL_ALLREDUCE_OP_SUM;
     float prescale = 1.0f, postscale = 1.0f;  // every piece is packed with the one, unpacked with the other
-    void *residual = nullptr;  // error feedback (a compressed plan): an fp32 array indexed like the tensor
+    void *residual = nullptr;  // error feedback (a compressed plan, the e4m3 wire's too): an fp32 array indexed like the tensor
     WireStream stream{};  // stochastic rounding (a compressed bf16 plan); `first`: the first element's index in its request
     bool want = false;  // the sum of squares of the result (PlanSumsq)
     size_t elems = 0;  // the e4m3 wire only (bytes: whole granules): the fp32 elements of the tensors behind them

@@ -129,8 +129,8 @@ void validate(const Request &r, int size) {
                                         (r.wire == DDL_HALF || r.wire == DDL_BFLOAT16 || r.wire == kDtypeE4m3)),
                         DDL_STATUS_INVALID_ARGUMENT, "wire dtype " << r.wire << " on a " << dtype_name(r.dtype) << " request");
             check_wire_ranks(r.wire, size);
-            DDL_REQUIRE(r.wire != kDtypeE4m3 || (!r.feedback && !op_is_minmax(r.op)), DDL_STATUS_INVALID_ARGUMENT,
-                        "the e4m3 wire takes SUM or AVG and no error feedback");
+            DDL_REQUIRE(r.wire != kDtypeE4m3 || !op_is_minmax(r.op), DDL_STATUS_INVALID_ARGUMENT,
+                        "the e4m3 wire takes SUM or AVG");
             DDL_REQUIRE(!r.feedback || r.wire != 0, DDL_STATUS_INVALID_ARGUMENT, "error feedback without a wire dtype");
             DDL_REQUIRE(!r.stochastic || (r.wire == DDL_BFLOAT16 && !r.feedback), DDL_STATUS_INVALID_ARGUMENT,
                         "stochastic rounding takes the bfloat16 wire and no error feedback");
@@ -510,11 +510,14 @@ std::vector<int> plan_ops(const Plan &p, const std::vector<Request> &reqs, const
 
 // Engine thread only. hipMalloc does not wait for the device (profiles/r06/s17); the zeroing is
 // posted on stream_, so it runs after every earlier pack of this key and before the next one. A
-// residual of another element count is retired, not freed: its last pack may still be running.
+// residual of another element count is retired, not freed: its last pack may still be running. A key that
+// comes back under the other family of wire (e4m3 after a 16-bit wire, or the reverse) restarts from zero.
 void *RequestHandler::residual_(const Request &r) {
     const long long epoch = config().wire_feedback_epoch.load();
+    const int family = r.wire == kDtypeE4m3 ? kFamilyE4m3 : kFamily16;
     Residual &res = residuals_[r.key];
-    if (res.ptr && res.n == r.n && res.epoch == epoch) return res.ptr;
+    if (res.ptr && res.n == r.n && res.epoch == epoch && res.family == family) return res.ptr;
+    res.family = family;
     if (res.n != r.n) {
         if (res.ptr) retire_device(res.ptr);
         res.ptr = nullptr;

@@ -56,7 +56,7 @@ struct Request {
     int dtype = 0;
     int op = 0;                       // allreduce: SUM / AVG / MIN / MAX (the wire flag decoded into `wire`)
     int wire = 0;                     // allreduce: wire dtype of a compressed fp32 request (0: its own dtype)
-    bool feedback = false;            // allreduce: DDL_ALLREDUCE_WIRE_FEEDBACK (only with `wire`; rank-local)
+    bool feedback = false;            // allreduce: DDL_ALLREDUCE_WIRE_FEEDBACK, or with the e4m3 `wire` _E4M3_FEEDBACK (rank-local)
     bool stochastic = false;          // allreduce: DDL_ALLREDUCE_WIRE_STOCHASTIC (only with the bf16 `wire`; rank-local)
     double *sumsq = nullptr;          // allreduce: where the sum of squares of `out` goes before done() (host; rank-local)
     // allreduce: DDL_ALLREDUCE_SCALE's factors (1 = absent; fp32 device SUM / AVG requests). Rank-local like
@@ -183,7 +183,7 @@ private:
     // multi-request plans: pack -> allreduce -> unpack, pipelined in sub-plans above
     // fusion_pipeline_bytes (fusion.h); its buffer 0 also packs broadcast / allgather plans
     FusionPipe fp_;
-    // Error feedback (DDL_ALLREDUCE_WIRE_FEEDBACK): what the wire's rounding removed from this rank's
+    // Error feedback (DDL_ALLREDUCE_WIRE_FEEDBACK, DDL_ALLREDUCE_WIRE_E4M3_FEEDBACK): what the wire's rounding removed from this rank's
     // contribution to a key, added back at the key's next request. One fp32 array per key that ever
     // asked for feedback, owned here and freed with the handler (a replaced one is retired, never
     // freed on a data path). Touched by the engine thread only (allreduce_reqs_ posts the packs).
@@ -191,10 +191,12 @@ private:
         void *ptr = nullptr;
         size_t n = 0;         // elements
         long long epoch = 0;  // config wire_feedback_epoch when it was last (re)started
+        int family = 0;       // kFamily16 (fp16 and bf16 share it) or kFamilyE4m3: the rule that last wrote it
     };
+    static constexpr int kFamily16 = 1, kFamilyE4m3 = 2;
     std::unordered_map<std::string, Residual> residuals_;
     // the residual of request r for a pack posted on stream_: made, or restarted from zero (another
-    // element count, another epoch), by work posted on stream_ ahead of that pack
+    // element count, another epoch, the other family of wire), by work posted on stream_ ahead of that pack
     void *residual_(const Request &r);
     // Stochastic rounding (DDL_ALLREDUCE_WIRE_STOCHASTIC): a key's sequence number n — how many requests of
     // the key with the bit this handler has packed before — one of the four things a request's stream key S

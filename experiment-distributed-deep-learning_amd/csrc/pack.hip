@@ -613,19 +613,40 @@ struct SegElems {
     uint64_t n;
 };
 
-template <bool SCALE = false> struct Q8PackOp {
+// FB (DDL_ALLREDUCE_WIRE_E4M3_FEEDBACK; the rule is ddl_amd.h's "Error feedback of the e4m3 wire"): the pack plus one
+// table of residual addresses, res[seg], behind the element counts (0: the segment is packed exactly as
+// Q8PackOp<SCALE, false> packs it). A lane reads and writes the residual with the tensor's mapping — vectors r,
+// 16 + r, 32 + r, 48 + r of the granule, 256 contiguous bytes per row and instruction — so the lane that loaded
+// v[k] holds its code when encode_row returns, and row_scale_exponent left the scale on every lane: it decodes its own four
+// dwords (dequantize) and stores v (-) code * s, +0.0 behind a NaN or an infinity. The residual moves as 16-byte
+// vectors wherever it is 16-byte aligned and the vector lies inside the request (every piece of a cut request
+// starts a multiple of 1008 bytes into a hipMalloc'd array), whatever the tensor's alignment, else element by
+// element; nothing at or past n is read or written. Loads of the residual are plain, its stores non-temporal, as
+// CvtPackOp<WIRE, true>'s. 4 + 4 + 4 + 256/252 bytes moved per element. c (+) r never contracts with the prescale
+// (mul_rn), v (-) d never with the decode (mul1). FB = false takes no table and stays its own kernel.
+template <bool SCALE = false, bool FB = false> struct Q8PackOp {
     static constexpr uint32_t kUnit = 1;
     char *fl;
     const float *tp;
+    float *rs = nullptr;
     uint64_t n;
-    bool v;
+    bool v, rv = false;
     Factor<SCALE> fac;
     template <class... A>
     __device__ Q8PackOp(char *flat, const SegDesc &sd, int seg, A... a)
         : fl(flat + sd.off), tp(reinterpret_cast<const float *>(sd.ptr)), n(arg_of<const SegElems *>(a...)[seg].n),
-          v((sd.vec & kSegVec) != 0), fac(sd, seg, a...) {}
+          v((sd.vec & kSegVec) != 0), fac(sd, seg, a...) {
+        if constexpr (FB) {
+            const uint64_t r = arg_of<const uint64_t *>(a...)[seg];
+            rs = reinterpret_cast<float *>(r);
+            rv = (r & 15u) == 0;
+        }
+    }
     __device__ bool vector() const { return true; }  // whole granules: the edges are the tensor side's, below
     __device__ void vec(uint64_t b) const {
+        if constexpr (FB) {
+            if (rs) return vec_fb(b);
+        }
         const int r = (int)(b >> 4) & 15;
         const uint64_t g0 = (b >> 8) * kE4m3Elems;  // the granule's first element
         float x[16];
@@ -652,6 +673,65 @@ template <bool SCALE = false> struct Q8PackOp {
         uint32_t *dst = reinterpret_cast<uint32_t *>(fl + (b & ~uint64_t(255))) + r;
 #pragma unroll
         for (int h = 0; h < 4; ++h) __builtin_nontemporal_store(w[h], dst + 16 * h);
+    }
+    // the lane's share of a granule of `p` (the tensor, non-temporal; the residual, plain loads): vectors where
+    // `whole` and inside the request, else elements; +0.0 past n
+    template <bool NT> __device__ void gather(const float *p, bool whole, uint64_t g0, int r, float (&x)[16]) const {
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const int vi = 16 * h + r;
+            const uint64_t e = g0 + (uint64_t)vi * 4;
+            F32x4 q;
+            q.v = u32x4{0, 0, 0, 0};
+            if (vi < 63) {
+                if (whole && e + 4 <= n) {
+                    const u32x4 *src = reinterpret_cast<const u32x4 *>(p + e);
+                    q.v = NT ? __builtin_nontemporal_load(src) : *src;
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (e + k < n) q.e[k] = NT ? __builtin_nontemporal_load(p + e + k) : p[e + k];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) x[4 * h + k] = q.e[k];
+        }
+    }
+    __device__ void vec_fb(uint64_t b) const {  // a segment with a residual
+        const int r = (int)(b >> 4) & 15;
+        const uint64_t g0 = (b >> 8) * kE4m3Elems;
+        float x[16], q[16];
+        gather<true>(tp, v, g0, r, x);
+        gather<false>(rs, rv, g0, r, q);
+        fac(x);
+#pragma unroll
+        for (int k = 0; k < 16; ++k) x[k] = x[k] + q[k];  // v = c (+) r
+        const uint32_t se = e4m3::row_scale_exponent(x, r);
+        const u32x4 w = e4m3::encode_row(x, r, se);
+        uint32_t *dst = reinterpret_cast<uint32_t *>(fl + (b & ~uint64_t(255))) + r;
+#pragma unroll
+        for (int h = 0; h < 4; ++h) __builtin_nontemporal_store(w[h], dst + 16 * h);
+        float d[16];  // what the fold / the unpack will read (lane 15's d[12..15] decode the scale dword: unused)
+        e4m3::dequantize(w, __uint_as_float(se << 23), d);
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const int vi = 16 * h + r;
+            const uint64_t e = g0 + (uint64_t)vi * 4;
+            if (vi >= 63) continue;
+            F32x4 o;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float y = x[4 * h + k];
+                o.e[k] = (__float_as_uint(y) & 0x7fffffffu) < 0x7f800000u ? y - d[4 * h + k] : 0.0f;
+            }
+            if (rv && e + 4 <= n) {
+                __builtin_nontemporal_store(o.v, reinterpret_cast<u32x4 *>(rs + e));
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (e + k < n) __builtin_nontemporal_store(o.e[k], rs + e + k);
+            }
+        }
     }
     __device__ void elem(uint64_t) const {}
 };
@@ -1104,7 +1184,7 @@ void SegmentCopier::run(const CopyLaunch &how, const CopySeg *segs, int count) {
         DDL_REQUIRE(dir == 0 || dir == 1 || (dir == kSumsqInPlace && !q8), DDL_STATUS_INVALID_ARGUMENT,
                     "copier direction " << dir);
         for (int i = 0; i < n && q8; ++i)
-            DDL_REQUIRE(segs[i].bytes == e4m3_granules(segs[i].elems) * kE4m3Granule && !segs[i].residual && !segs[i].stream.on,
+            DDL_REQUIRE(segs[i].bytes == e4m3_granules(segs[i].elems) * kE4m3Granule && !segs[i].stream.on,
                         DDL_STATUS_INVALID_ARGUMENT, "segment " << i << " is not the granules of its elements");
         DDL_REQUIRE(divisor >= 1, DDL_STATUS_INVALID_ARGUMENT, "divisor " << divisor);
         require_f32_segments(segs, n, 2);
@@ -1174,8 +1254,10 @@ void SegmentCopier::run(const CopyLaunch &how, const CopySeg *segs, int count) {
     // descriptors, then the block bases, then (feedback pack) one residual address per segment or
     // (stochastic pack) one WireStream per segment, then (scaled launch) one factor per segment
     const size_t rtab = (table + nblk * sizeof(uint32_t) + 7) & ~size_t(7);
-    // (the e4m3 wire: one SegElems per segment where a feedback pack has its residual addresses)
-    const size_t wtab = fbk || q8 ? rtab + (size_t)count * sizeof(uint64_t) : rtab;
+    // (the e4m3 wire: one SegElems per segment where a 16-bit feedback pack has its residual addresses, the
+    // residual addresses of an e4m3 feedback pack behind them)
+    const size_t ftab = q8 ? rtab + (size_t)count * sizeof(SegElems) : rtab;
+    const size_t wtab = fbk ? ftab + (size_t)count * sizeof(uint64_t) : ftab;
     const size_t stab = srk ? wtab + (size_t)count * sizeof(WireStream) : fbk || q8 ? wtab : table + nblk * sizeof(uint32_t);
     const size_t need = sc ? stab + (size_t)count * sizeof(float) : stab;
     if (need > sl.cap) {  // outgrown tables kept until ddl_finalize: no hipFree on a data path (engine.h)
@@ -1205,7 +1287,7 @@ void SegmentCopier::run(const CopyLaunch &how, const CopySeg *segs, int count) {
     }
     if (off == 0) return;
     if (fbk) {
-        uint64_t *rt = reinterpret_cast<uint64_t *>(static_cast<char *>(sl.host) + rtab);
+        uint64_t *rt = reinterpret_cast<uint64_t *>(static_cast<char *>(sl.host) + ftab);
         for (int i = 0; i < count; ++i) rt[i] = segs[i].bytes ? reinterpret_cast<uint64_t>(segs[i].residual) : 0;
     }
     for (int i = 0; i < count && q8; ++i) reinterpret_cast<SegElems *>(static_cast<char *>(sl.host) + rtab)[i].n = segs[i].elems;
@@ -1256,7 +1338,7 @@ void SegmentCopier::run(const CopyLaunch &how, const CopySeg *segs, int count) {
             }
             partials = static_cast<double *>(sl.stat);
         }
-        const uint64_t *res = reinterpret_cast<const uint64_t *>(static_cast<char *>(sl.dev) + rtab);  // (fbk)
+        const uint64_t *res = reinterpret_cast<const uint64_t *>(static_cast<char *>(sl.dev) + ftab);  // (fbk)
         const WireStream *sts = reinterpret_cast<const WireStream *>(static_cast<char *>(sl.dev) + wtab);  // (srk)
         const float *scl = reinterpret_cast<const float *>(static_cast<char *>(sl.dev) + stab);        // (sc)
         // The instance, from the launch's facts. SCALE: the scaled twin of the same Op, the factor table
@@ -1285,8 +1367,9 @@ void SegmentCopier::run(const CopyLaunch &how, const CopySeg *segs, int count) {
                 if (wire) with_wire(wire, sumsq);
                 else sumsq(std::integral_constant<int, -1>{});
             } else if (q8) {
-                const SegElems *cnt = reinterpret_cast<const SegElems *>(res);
+                const SegElems *cnt = reinterpret_cast<const SegElems *>(static_cast<char *>(sl.dev) + rtab);
                 if (dir != 0) seg((Q8UnpackOp<SCALE> *)nullptr, (float)divisor, cnt);
+                else if (fbk) seg((Q8PackOp<SCALE, true> *)nullptr, cnt, res);
                 else seg((Q8PackOp<SCALE> *)nullptr, cnt);
             } else if (wire) {
                 with_wire(wire, [&](auto w) {
@@ -1339,8 +1422,9 @@ void SegmentCopier::run(const CopyLaunch &how, const CopySeg *segs, int count) {
             }
         for (int i = 0; i < count && fbk; ++i)
             if (segs[i].bytes && segs[i].residual) {  // read and written: both, so the race check sees either side
-                acc.push_back(dep::rd(segs[i].residual, segs[i].bytes * widen));
-                acc.push_back(dep::wr(segs[i].residual, segs[i].bytes * widen));
+                const size_t rb = q8 ? segs[i].elems * sizeof(float) : segs[i].bytes * widen;
+                acc.push_back(dep::rd(segs[i].residual, rb));
+                acc.push_back(dep::wr(segs[i].residual, rb));
             }
         const std::string label =
             in_place ? (dir == kSumsqInPlace ? "sumsq" : sc ? "scale" : "divide")

@@ -48,6 +48,21 @@ and runs these requests on its fold-once schedules. The per-granule scale remove
 predivide factor or loss scale is needed for the wire's sake; both still compose), what remains is precision:
 3 mantissa bits, an error below amax / 14 of each granule per quantization. It keeps no per-name state, so
 fresh names are fine (allreduce_gradient takes it); communicators of at most 16 ranks; SUM and AVG only.
+
+8 bits with error feedback: `Compression.fp8_feedback` (include/ddl_amd.h, DDL_ALLREDUCE_WIRE_E4M3_FEEDBACK). On 3
+mantissa bits the bias feedback cures is more than 16 times the 16-bit wires': within a granule whose amax does not
+move an element rounds to the same wrong code every step, and an element below 2**-10 of its granule's amax is zero
+for ever. What is compensated: the contributions — every rank keeps what the pack's quantization removed from its
+own gradient under a name and adds it to that name's next tensor ahead of the next quantization, in the same pack
+kernel. What is not: the requantization of the ranks' sum in the fold (it has no single owner); the P pack errors
+outweigh that one error from 2 ranks on, and contributions that dither no longer hold the sum on one rounding
+boundary — a statement from the arithmetic, not a training measurement. The cost: one fp32 copy of each gradient in
+device memory, kept per request NAME until the communicator goes (stable names only: allreduce_gradient refuses
+it), and a pack that moves 4 + 4 + 4 + 256/252 = 13.0 bytes per element against 5.0 (measured on one MI355X: 1.59 ms
+against the plain pack's 0.66 on the C5 gradient set, 2.42 times, and 1.05 times the bf16 feedback pack's). When to
+reset: as for the 16-bit kinds — `reset_error_feedback()` after loading a checkpoint or a large change of the loss
+scale (unless prescale = 1 / loss scale keeps the residual in the true gradient's units). A name that moves between
+`fp8_feedback` and a 16-bit `_feedback` kind restarts from zero by itself.
 """
 from ddl.torch import cpp_backend as cb
 
@@ -60,7 +75,7 @@ class _Wire:
 
     @property
     def feedback(self) -> bool:
-        return bool(self.flag & cb.WIRE_FEEDBACK)
+        return bool(self.flag & (cb.WIRE_FEEDBACK | cb.WIRE_E4M3_FEEDBACK))
 
     @property
     def stochastic(self) -> bool:
@@ -79,7 +94,10 @@ class Compression:
     (module docstring: unbiased, no residual, nothing to reset, the plain 6-byte pack; one 8-byte
     counter per request name). allreduce_gradient takes neither the `_feedback` kinds nor it. `fp8`: block-scaled
     e4m3 granules, quantized once per contribution and once per sum (module docstring: no per-name state, at most
-    16 ranks)."""
+    16 ranks). `fp8_feedback`: the same wire with an error-feedback residual per request name for the pack's
+    quantization (module docstring: one fp32 copy of every gradient, a 13-byte-per-element pack instead of 5, the
+    sum's requantization not compensated, `reset_error_feedback()` as for the 16-bit kinds; not for
+    allreduce_gradient)."""
     none = _Wire('none', 0)
     fp16 = _Wire('fp16', cb.WIRE_FP16)
     bf16 = _Wire('bf16', cb.WIRE_BF16)
@@ -87,6 +105,7 @@ class Compression:
     bf16_feedback = _Wire('bf16_feedback', cb.WIRE_BF16 | cb.WIRE_FEEDBACK)
     bf16_stochastic = _Wire('bf16_stochastic', cb.WIRE_BF16 | cb.WIRE_STOCHASTIC)
     fp8 = _Wire('fp8', cb.WIRE_E4M3)
+    fp8_feedback = _Wire('fp8_feedback', cb.WIRE_E4M3 | cb.WIRE_E4M3_FEEDBACK)
 
 
 def wire_flag(compression) -> int:
@@ -95,12 +114,12 @@ def wire_flag(compression) -> int:
         return 0
     if not isinstance(compression, _Wire):
         raise TypeError('compression must be Compression.none, .fp16, .bf16, .fp16_feedback, .bf16_feedback, '
-                        f'.bf16_stochastic or .fp8, not {compression!r}')
+                        f'.bf16_stochastic, .fp8 or .fp8_feedback, not {compression!r}')
     return compression.flag
 
 
 def reset_error_feedback() -> None:
-    """Restart every error-feedback residual of this process from zero at its next use (raises the
+    """Restart every error-feedback residual of this process — the 16-bit kinds' and `fp8_feedback`'s — from zero at its next use (raises the
     engine's per-process `wire_feedback_epoch` by one). Call it after loading a checkpoint, or after
     a change of the loss scale by a large factor: the residuals describe gradients that no longer
     exist. Rank-local: nothing is communicated, the ranks need not call it together."""

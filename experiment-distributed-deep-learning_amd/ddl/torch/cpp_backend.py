@@ -45,6 +45,7 @@ WIRE_FP16, WIRE_BF16 = 0x100, 0x200  # enum ddl_allreduce_wire: OR-ed into a key
 WIRE_FEEDBACK = 0x1000  # error feedback: only together with exactly one of the two wire flags
 WIRE_STOCHASTIC = 0x8000  # stochastic rounding: only together with WIRE_BF16, never with WIRE_FEEDBACK
 WIRE_E4M3 = 0x20000  # enum ddl_allreduce_wire8: block-scaled e4m3fn granules; no other wire bit with it
+WIRE_E4M3_FEEDBACK = 0x40000  # enum ddl_allreduce_wire8_feedback: error feedback of the e4m3 pack; only with WIRE_E4M3
 SUMSQ = 0x2000  # enum ddl_allreduce_stat: `user` points to a SumsqArg (struct ddl_sumsq_arg)
 SCALE = 0x4000  # enum ddl_allreduce_scale: `user` points to a ScaleArg (struct ddl_scale_arg)
 MEMORY_DEVICE, MEMORY_HOST = 0, 1  # enum ddl_memory
@@ -245,6 +246,11 @@ class CPPBackend:
         sig('ddl_testing_thread_fused_allreduce_e4m3', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp),
             ctypes.POINTER(sz), ctypes.POINTER(ci), fp, fp, vp, ctypes.POINTER(sz), ub, dp, ctypes.POINTER(sz),
             ctypes.POINTER(sz), ci, ctypes.POINTER(ci))
+        # (testing library: error feedback of the e4m3 wire with caller-owned residuals)
+        sig('ddl_pack_e4m3_fb', ci, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(sz), ci, fp, vp)
+        sig('ddl_testing_thread_fused_allreduce_e4m3_fb', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp),
+            ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(ci), fp, fp, vp, ctypes.POINTER(sz), ub, dp,
+            ctypes.POINTER(sz), ctypes.POINTER(sz), ci, ctypes.POINTER(ci))
         sig('ddl_testing_thread_fused_allreduce_wire', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp),
             ctypes.POINTER(sz), ctypes.POINTER(ci), ci, vp, ctypes.POINTER(sz))
         sig('ddl_local_ring_allreduce', ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp), sz, ci, ci, vp)

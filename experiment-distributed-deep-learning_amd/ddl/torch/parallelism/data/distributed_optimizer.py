@@ -60,6 +60,13 @@ It keeps no state, composes with `fused_mean`, the norm tracking, `gradient_pred
 and `DynamicLossScaler` (the per-block scale makes neither factor necessary for the wire's sake), and takes
 communicators of at most 16 ranks.
 
+`compression=Compression.fp8_feedback`: the same wire with error feedback of the pack's quantization — every
+rank keeps what its own quantization removed from each gradient under the gradient's stable name and adds it
+back at the next step (ddl.torch.compression: one fp32 copy of every gradient in device memory, a pack of 13
+bytes per element instead of 5; the requantization of the sum is not compensated). On both paths; it composes
+with everything `Compression.fp8` composes with, the residuals being in prescaled units, and
+`ddl.torch.compression.reset_error_feedback()` restarts it as it restarts the 16-bit kinds.
+
 `track_grad_norm=True` (implied by `max_grad_norm` and `skip_nonfinite`): after
 `allreduce_gradients()`, `optimizer.grad_norm` is the global L2 norm of the averaged gradients (a
 float) and `optimizer.found_nonfinite` is `not math.isfinite(grad_norm)`. Every dense fp32 or bf16 device

@@ -111,7 +111,7 @@ def allreduce_gradient(tensor: torch.Tensor, communicator: Communicator = None,
     `compression` (Compression.fp16 / .bf16; a dense fp32 device gradient at size > 1): the gradient
     goes through the keyed path and travels as 16-bit values (ddl.torch.compression); every other
     gradient is reduced as without it. The error-feedback kinds (Compression.fp16_feedback /
-    .bf16_feedback) raise ValueError: the compressed path here makes a fresh request name per call,
+    .bf16_feedback / .fp8_feedback) raise ValueError: the compressed path here makes a fresh request name per call,
     and the engine keeps one residual per name, so every call would leak one — use
     allreduce_async[_batch] or the optimizer wrapper, whose names are stable. Compression.bf16_stochastic
     raises ValueError for the same reason: the engine keeps one sequence counter per name, and a fresh
@@ -122,7 +122,7 @@ def allreduce_gradient(tensor: torch.Tensor, communicator: Communicator = None,
     divides the values; duplicate indices stay uncoalesced, as IndexedSlices keeps them.
     """
     communicator = _comm(communicator)
-    if wire_flag(compression) & cb.WIRE_FEEDBACK:
+    if wire_flag(compression) & (cb.WIRE_FEEDBACK | cb.WIRE_E4M3_FEEDBACK):
         raise ValueError(f'allreduce_gradient does not take {compression!r}: its compressed requests get a fresh '
                          'name per call, which would leak one error-feedback residual per call; use allreduce_async '
                          'with a stable name')
@@ -522,7 +522,8 @@ def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator 
     `name` and adds it to the next tensor submitted under that name (error feedback: one fp32 copy
     of the tensor in device memory per distinct name until the communicator goes, so keep the names
     stable from step to step; ddl.torch.compression.reset_error_feedback after loading a checkpoint
-    or a large change of the loss scale).
+    or a large change of the loss scale). Compression.fp8_feedback is the same for Compression.fp8's
+    e4m3 granules: the residual of the pack's quantization under `name`, the sum's requantization uncompensated.
     `sumsq=True` (a dense fp32 or bf16 device tensor, OP_SUM or OP_AVG; anything else: ValueError): after
     wait(), `handle.sumsq` is a Python float, the fp64 sum of the squares of the output's elements,
     taken by the engine where it writes them (include/ddl_amd.h "Sum of squares": no extra pass in a

@@ -95,6 +95,10 @@ enum ddl_allreduce_wire_rounding { DDL_ALLREDUCE_WIRE_STOCHASTIC = 0x8000 };
  * for DDL_FLOAT device requests, optionally with DDL_ALLREDUCE_SUMSQ and DDL_ALLREDUCE_SCALE; never with a
  * ddl_allreduce_wire flag, DDL_ALLREDUCE_WIRE_FEEDBACK or DDL_ALLREDUCE_WIRE_STOCHASTIC. */
 enum ddl_allreduce_wire8 { DDL_ALLREDUCE_WIRE_E4M3 = 0x20000 };
+/* Error feedback of the e4m3 wire ("Error feedback of the e4m3 wire" in the data-plane section): one more bit of
+ * the same `op`, valid only OR-ed with DDL_ALLREDUCE_WIRE_E4M3. A bit of its own, not DDL_ALLREDUCE_WIRE_FEEDBACK
+ * (which stays refused with WIRE_E4M3): another rule — per granule, no overflow case, another byte cost. */
+enum ddl_allreduce_wire8_feedback { DDL_ALLREDUCE_WIRE_E4M3_FEEDBACK = 0x40000 };
 /* Sum of squares of a keyed device allreduce of DDL_FLOAT or DDL_BFLOAT16 tensors (MI355X extension; the data-plane
  * section): OR-ed into the `op` of ddl_allreduce_submit / _submit_batch (and _submit_mem /
  * _submit_batch_mem with DDL_MEMORY_DEVICE), SUM or AVG, with or without a wire flag. With the bit
@@ -424,6 +428,55 @@ void py_error(const char *log_str);
  * ddl_allreduce_host, or a communicator of more than 16 ranks (a fold of more than 16 inputs goes through
  * partials, which would requantize) return DDL_STATUS_INVALID_ARGUMENT; another dtype
  * DDL_STATUS_UNSUPPORTED_DTYPE. P = 1: with "one_rank_shortcut" 1 nothing is quantized.
+ *
+ * Error feedback of the e4m3 wire: DDL_ALLREDUCE_WIRE_E4M3_FEEDBACK, OR-ed with DDL_ALLREDUCE_WIRE_E4M3 (and
+ * optionally DDL_ALLREDUCE_SUMSQ / DDL_ALLREDUCE_SCALE) on the keyed entry points. The wire keeps 3 mantissa bits:
+ * within a granule whose amax does not move an element rounds to the same wrong code every step, and an element
+ * below 2^-10 of its granule's amax is zero for ever. With the bit the rank keeps what the PACK's quantization
+ * removed from its contribution and adds it back at the key's next request. Only the first of the wire's two
+ * quantizations is compensated: THE FOLD'S REQUANTIZATION OF THE SUM IS NOT (whichever rank folds a chunk depends
+ * on the schedule, the tuner and the cuts, and the fold-everything schedules have no single owner). The P pack
+ * errors add up against one fold error, so at P >= 2 the pack side dominates, and once the contributions dither
+ * the fold's input no longer sits on the same rounding boundary every step; that is a statement from the
+ * arithmetic, nobody has measured it in training.
+ * r is the rank's residual for the key: fp32, the request's element count, indexed like the tensor, zero the
+ * first time. All arithmetic is fp32, round to nearest even, subnormals kept, every product and sum rounded on
+ * its own, never contracted. Per granule of a request that carries the bit:
+ *     c  = g, or g (x) prescale                      as without the bit
+ *     v  = c (+) r
+ *     (codes, s) = the pack's rule above applied to the granule's v (amax over the FINITE v, the same scale
+ *                  rule, RNE_e4m3(v / s), 0x7f | sign for a NaN or an infinity)
+ *     d  = code * s                                  exact: what the unpack / the fold will read
+ *     r' = isfinite(v) ? v (-) d : +0.0
+ * (codes, s) go to the wire, r' replaces r. Elements of the last granule past n have no residual and stay +0.0
+ * on the wire. tests/_e4m3_feedback_helpers.py restates the rule in NumPy, bit for bit.
+ * No overflow case: nothing saturates on this wire, so the rule has none; a NaN or an infinity in v clears that
+ * element's residual and can never poison later steps. v (-) d is exact for finite v: 0 is on the code grid, so
+ * |v - d| <= |v|, and the grid's quantum — s * 2^-9 at its finest — is never below ulp(v), because |v| <= 448 s.
+ * The rule therefore costs one fp32 rounding (c + r) beyond the wire's own (tests/test_e4m3_feedback_model_cpu.py
+ * checks the subtraction against fp64). From the wire bytes on the request is the plain e4m3 request: granules,
+ * fusion group, plan and pipeline cuts, fold-once schedules, the fold, the unpack, AVG's quotient, the postscale
+ * and the sum of squares are unchanged. The residual is in prescaled units, as for the 16-bit wires.
+ * The residual has the lifetime and the restarts of the 16-bit one: kept by the communicator until it is
+ * destroyed (a failed plan is not undone), restarted from zero on another element count and on another
+ * "wire_feedback_epoch"; and also when the key comes back under the other family of wire — e4m3 after a 16-bit
+ * wire with DDL_ALLREDUCE_WIRE_FEEDBACK, or the reverse (fp16 <-> bf16 keeps the residual, as before). EVERY
+ * DISTINCT KEY THAT EVER CARRIED THE BIT HOLDS 4 BYTES PER ELEMENT UNTIL THEN: never use it with fresh key names
+ * per step. A request of the key without the bit leaves the residual untouched and unused. The pack of a segment
+ * with a residual moves 4 + 4 + 4 + 256/252 (about 13.0) bytes per element against 5.0 (csrc/pack.hip
+ * k_seg<Q8PackOp<SCALE, true>>; the vector and the element path give the same bits, so nothing depends on the
+ * tensor's alignment, on "fusion_threshold_bytes" or on "fusion_pipeline_bytes": a piece's residual starts at the
+ * piece's first element).
+ * The bit is rank-local like the 16-bit feedback bit: it is in no fusion group key, plan cut or negotiation, one
+ * pack launch may mix e4m3 segments with and without it (a segment without it is packed exactly as the plain
+ * pack packs it), a launch with no feedback segment is the kernel it was, with the same tables and arguments,
+ * and ranks that disagree about it get different numbers, never a hang.
+ * Refusals, before anything is registered (the communicator works afterwards): the bit without WIRE_E4M3, with
+ * WIRE_FP16 or WIRE_BF16, with WIRE_FEEDBACK or WIRE_STOCHASTIC, with MIN / MAX, with DDL_MEMORY_HOST, on
+ * ddl_allreduce, ddl_allreduce_batch or ddl_allreduce_host, or on a communicator of more than 16 ranks returns
+ * DDL_STATUS_INVALID_ARGUMENT; a dtype other than DDL_FLOAT DDL_STATUS_UNSUPPORTED_DTYPE.
+ * P = 1: with "one_rank_shortcut" 1 nothing is touched and no residual is made; with 0 the data plane runs and
+ * the rule applies.
  *
  * MIN / MAX: DDL_ALLREDUCE_OP_MIN = 3 and DDL_ALLREDUCE_OP_MAX = 4, on every dtype and every
  * allreduce entry point. Per element over the P inputs: DDL_INT32 / DDL_INT64 in signed order,

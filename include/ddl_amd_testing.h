@@ -340,6 +340,21 @@ int ddl_testing_thread_fused_allreduce_e4m3(int nranks, int count, const void *c
                                             const float *postscale, void *hip_stream, size_t *subplans,
                                             const unsigned char *want, double *sumsq_out, size_t *cut_segs,
                                             size_t *cut_elems, int max_cuts, int *ncuts);
+/* Error feedback of the e4m3 wire (DDL_ALLREDUCE_WIRE_E4M3_FEEDBACK; ddl_amd.h "Error feedback of the e4m3 wire";
+ * csrc/pack.hip k_seg<Q8PackOp<SCALE, true>>) with caller-owned residuals. _pack_e4m3_fb: ddl_pack_e4m3 where
+ * residuals[i] holds elements[i] fp32 values (4-byte aligned; read, then overwritten with what the pack's
+ * quantization removed) and NULL means segment i is packed as ddl_pack_e4m3 packs it; with every residual NULL the
+ * launch is ddl_pack_e4m3's. Only the pack's quantization is compensated, never the fold's.
+ * _thread_fused_allreduce_e4m3_fb: ddl_testing_thread_fused_allreduce_e4m3 plus residuals[r * count + i] (NULL: none
+ * for that rank's segment) as in ddl_testing_thread_fused_allreduce_wire_fb, handed to the plan as the keyed handler
+ * hands over its own: a sub-plan's piece gets the residual at its first element. */
+int ddl_pack_e4m3_fb(void *dst, const void *const *srcs, void *const *residuals, const size_t *elements, int count,
+                     const float *scale, void *hip_stream);
+int ddl_testing_thread_fused_allreduce_e4m3_fb(int nranks, int count, const void *const *srcs, void *const *dsts,
+                                               void *const *residuals, const size_t *elements, const int *ops,
+                                               const float *prescale, const float *postscale, void *hip_stream,
+                                               size_t *subplans, const unsigned char *want, double *sumsq_out,
+                                               size_t *cut_segs, size_t *cut_elems, int max_cuts, int *ncuts);
 /* ddl_testing_thread_fused_allreduce_scale over the bf16 wire with stochastic rounding and no residuals:
  * sr_want[i] != 0 = segment i is rounded stochastically on every virtual rank, rank r with the stream key
  * streams[r * count + i] and first element index 0, handed to the plan as the keyed handler hands over its
