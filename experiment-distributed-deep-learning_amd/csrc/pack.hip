@@ -618,7 +618,8 @@ struct SegElems {
 // Q8PackOp<SCALE, false> packs it). A lane reads and writes the residual with the tensor's mapping — vectors r,
 // 16 + r, 32 + r, 48 + r of the granule, 256 contiguous bytes per row and instruction — so the lane that loaded
 // v[k] holds its code when encode_row returns, and row_scale_exponent left the scale on every lane: it decodes its own four
-// dwords (dequantize) and stores v (-) code * s, +0.0 behind a NaN or an infinity. The residual moves as 16-byte
+// dwords (dequantize) and stores v (-) code * s, +0.0 where that is not finite (a NaN or an infinity in v, or a code
+// that decodes to one: 256 * 2^120 and up). The residual moves as 16-byte
 // vectors wherever it is 16-byte aligned and the vector lies inside the request (every piece of a cut request
 // starts a multiple of 1008 bytes into a hipMalloc'd array), whatever the tensor's alignment, else element by
 // element; nothing at or past n is read or written. Loads of the residual are plain, its stores non-temporal, as
@@ -721,8 +722,9 @@ template <bool SCALE = false, bool FB = false> struct Q8PackOp {
             F32x4 o;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const float y = x[4 * h + k];
-                o.e[k] = (__float_as_uint(y) & 0x7fffffffu) < 0x7f800000u ? y - d[4 * h + k] : 0.0f;
+                // not finite: v is a NaN or an infinity, or d is (256 * 2^120 and up: a finite v past 248 * 2^120)
+                const float y = x[4 * h + k] - d[4 * h + k];
+                o.e[k] = (__float_as_uint(y) & 0x7fffffffu) < 0x7f800000u ? y : 0.0f;
             }
             if (rv && e + 4 <= n) {
                 __builtin_nontemporal_store(o.v, reinterpret_cast<u32x4 *>(rs + e));

@@ -447,11 +447,14 @@ void py_error(const char *log_str);
  *     (codes, s) = the pack's rule above applied to the granule's v (amax over the FINITE v, the same scale
  *                  rule, RNE_e4m3(v / s), 0x7f | sign for a NaN or an infinity)
  *     d  = code * s                                  exact: what the unpack / the fold will read
- *     r' = isfinite(v) ? v (-) d : +0.0
+ *     r' = isfinite(v (-) d) ? v (-) d : +0.0
  * (codes, s) go to the wire, r' replaces r. Elements of the last granule past n have no residual and stay +0.0
  * on the wire. tests/_e4m3_feedback_helpers.py restates the rule in NumPy, bit for bit.
- * No overflow case: nothing saturates on this wire, so the rule has none; a NaN or an infinity in v clears that
- * element's residual and can never poison later steps. v (-) d is exact for finite v: 0 is on the code grid, so
+ * Nothing saturates on this wire; a NaN or an infinity in v (d is a NaN then) clears that element's residual and can
+ * never poison later steps. The one overflow is the decode's: 2^120 is the largest scale (FLT_MAX / 2^120 < 256), so
+ * a finite |v| above 248 * 2^120 rounds to the code of 256, and d = 256 * 2^120 is an infinity in fp32 — for the fold
+ * and the unpack too, with or without the bit. There is nothing to keep for what went out as an infinity: v (-) d is
+ * not finite and r' is +0.0. Wherever d is finite, v (-) d is exact: 0 is on the code grid, so
  * |v - d| <= |v|, and the grid's quantum — s * 2^-9 at its finest — is never below ulp(v), because |v| <= 448 s.
  * The rule therefore costs one fp32 rounding (c + r) beyond the wire's own (tests/test_e4m3_feedback_model_cpu.py
  * checks the subtraction against fp64). From the wire bytes on the request is the plain e4m3 request: granules,

@@ -7,7 +7,9 @@ operation rounded on its own:
     v  = c + r
     (codes, s) = the plain pack's rule over the granule's v
     d  = code * s
-    r' = isfinite(v) ? v - d : +0.0
+    r' = isfinite(v - d) ? v - d : +0.0
+(not finite: v is a NaN or an infinity — d is a NaN then — or v is finite and past 248 * 2**120, whose code 256 and up
+under the largest scale 2**120 decodes to an infinity in fp32).
 Only the pack's quantization is compensated: the fold requantizes the sum as it does without the bit.
 """
 import numpy as np
@@ -29,7 +31,8 @@ def pack_fb(g, r, prescale=1.0):
         v = (c + r).astype(F)
         wire = q8.quantize(v)
         d = q8.dequantize(wire)[:v.size]
-        rn = np.where(np.isfinite(v), (v - d).astype(F), F(0)).astype(F)
+        e = (v - d).astype(F)
+        rn = np.where(np.isfinite(e), e, F(0)).astype(F)
     return wire, rn
 
 
