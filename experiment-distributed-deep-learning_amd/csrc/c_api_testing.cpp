@@ -1161,6 +1161,20 @@ int ddl_testing_compute_stream_cus(int every, int *enabled, int *total) {
     });
 }
 
+int ddl_testing_cu_mask_supported(int *supported) {
+    return guarded([&] {
+        DDL_REQUIRE(supported, DDL_STATUS_INVALID_ARGUMENT, "null output");
+        (void)current_device();
+        const int ncu = device_cu_count();
+        std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, 0u);
+        for (int c = 0; c < ncu; c += 2) mask[(size_t)c / 32] |= 1u << (c % 32);
+        hipStream_t s = nullptr;
+        *supported = hipExtStreamCreateWithCUMask(&s, (uint32_t)mask.size(), mask.data()) == hipSuccess;
+        if (*supported) (void)hipStreamDestroy(s);
+        else (void)hipGetLastError();
+    });
+}
+
 int ddl_testing_stream_priorities(ddl_communicator_id id, int *prio) {
     return guarded([&] {
         DDL_REQUIRE(prio, DDL_STATUS_INVALID_ARGUMENT, "null output");
@@ -1171,6 +1185,17 @@ int ddl_testing_stream_priorities(ddl_communicator_id id, int *prio) {
         prio[2] = prio[3] = DDL_TESTING_NO_STREAM;
         if (RequestHandler *h = c->handler_if_created()) DDL_HIP(hipStreamGetPriority(h->stream(), &prio[2]));
         if (auto kd = c->keyed_data()) DDL_HIP(hipStreamGetPriority(kd->executor().resources().comm, &prio[3]));
+    });
+}
+
+int ddl_testing_host_register_supported(int *supported) {
+    return guarded([&] {
+        DDL_REQUIRE(supported, DDL_STATUS_INVALID_ARGUMENT, "null output");
+        (void)current_device();
+        alignas(4096) static char page[4096];
+        *supported = hipHostRegister(page, sizeof page, hipHostRegisterMapped) == hipSuccess;
+        if (*supported) (void)hipHostUnregister(page);
+        else (void)hipGetLastError();
     });
 }
 

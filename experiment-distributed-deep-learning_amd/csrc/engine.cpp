@@ -515,12 +515,19 @@ bool host_pinned(const void *p) {
     return a.type == hipMemoryTypeHost;
 }
 
-// Registers a pageable host range for async DMA for the lifetime of the guard.
+// Registers a pageable host range for async DMA for the lifetime of the guard. Where the platform
+// cannot pin memory a process already has (a GPU passed through to a virtual machine:
+// hipHostRegister returns hipErrorInvalidValue), the range stays pageable and the pipeline's
+// hipMemcpyAsync calls go through the runtime's own pinned staging: the same bytes, the copies
+// of a chunk no longer overlapped with the caller's thread.
 class HostRegistration {
 public:
     HostRegistration(const void *p, size_t bytes) {
         if (!p || !bytes || host_pinned(p)) return;
-        DDL_HIP(hipHostRegister(const_cast<void *>(p), bytes, hipHostRegisterDefault));
+        if (hipHostRegister(const_cast<void *>(p), bytes, hipHostRegisterDefault) != hipSuccess) {
+            (void)hipGetLastError();  // else the next kernel launch of this thread reports it
+            return;
+        }
         p_ = const_cast<void *>(p);
     }
     ~HostRegistration() {

@@ -399,6 +399,10 @@ int ddl_testing_dep_check(long long *counts, char *report, size_t len);
 /* The CUs enabled on an executor compute stream created with every `every`-th CU masked off
  * (config "compute_cu_mask"; 0 = unmasked), read back with hipExtStreamGetCUMask. */
 int ddl_testing_compute_stream_cus(int every, int *enabled, int *total);
+/* *supported = 1 when hipExtStreamCreateWithCUMask creates a masked stream, 0 where the platform
+ * refuses it (the engine then runs its compute streams unmasked, create_compute_stream). The tests
+ * that read a mask back skip themselves there. */
+int ddl_testing_cu_mask_supported(int *supported);
 /* The stream priorities of a communicator's engine streams (config "queue_isolation", executor.h
  * QueueClass): prio[0] / prio[1] its executor's comm / compute stream, prio[2] its keyed
  * handler's stream, prio[3] its private keyed data-plane communicator's comm stream
@@ -411,6 +415,10 @@ int ddl_testing_stream_priorities(ddl_communicator_id id, int *prio);
  * cut[0] = 0 < ... < cut[count - 1] = total_bytes into cuts and sets *count. Pure host arithmetic
  * (no device). */
 int ddl_testing_host_chunk_cuts(size_t total_bytes, size_t chunk_bytes, size_t *cuts, size_t cap, size_t *count);
+/* *supported = 1 when hipHostRegister can pin a page the process already has, 0 where the platform
+ * refuses it (the registration cache, config "host_register_cache_bytes", then stages every
+ * pageable tensor as if it were off). The tests of the cache skip themselves there. */
+int ddl_testing_host_register_supported(int *supported);
 
 /* ---- RCCL loopback: the production RCCL transport on one GPU (TEST / DIAGNOSTIC) ---------
  * A one-rank RCCL communicator (ncclGetUniqueId + ncclCommInitRank, the calls ddl_init makes at

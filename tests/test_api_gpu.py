@@ -406,6 +406,15 @@ def test_keyed_fusion_pipeline_large_segment(world, lib, data_plane_at_one_rank)
         assert torch.equal(h.wait(timeout=60), w)
 
 
+def _skip_without_host_register(lib):
+    """The registration cache pins pageable memory the process already has (hipHostRegister); a
+    platform that refuses that stages every pageable tensor, and the cache has nothing to show."""
+    ok = ctypes.c_int()
+    assert lib.ddl_testing_host_register_supported(ctypes.byref(ok)) == 0, lib.ddl_last_error()
+    if not ok.value:
+        pytest.skip('hipHostRegister is not supported here')
+
+
 @pytest.mark.parametrize('memory', ['pageable', 'pinned', 'pinned_outputs', 'mixed', 'pinned_misaligned',
                                     'registered'])
 @pytest.mark.parametrize('chunk', [4096, 64 << 10, 32 << 20])
@@ -420,6 +429,8 @@ def test_keyed_host_requests_data_plane(world, lib, chunk, memory):
     registration cache take the pinned paths (the unpack kernel writes the registered outputs
     through their device mapping); switching the cache off unregisters them again."""
     from ddl.torch.tensor_communicate import allreduce_async_batch, broadcast_async
+    if memory == 'registered':
+        _skip_without_host_register(lib)
     keys = (b'one_rank_shortcut', b'host_chunk_bytes', b'host_register_cache_bytes')
     old = {k: lib.ddl_get_config(k) for k in keys}
     try:
@@ -531,6 +542,7 @@ def test_registration_cache_address_reuse(world, lib):
     import gc
     import mmap as _mmap
     from ddl.torch.tensor_communicate import allreduce_async
+    _skip_without_host_register(lib)
     libc = ctypes.CDLL(None, use_errno=True)
     libc.mmap.restype = ctypes.c_void_p
     libc.mmap.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long]
