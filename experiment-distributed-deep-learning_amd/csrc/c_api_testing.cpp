@@ -809,6 +809,59 @@ int ddl_testing_thread_fused_allreduce_e4m3(int nranks, int count, const void *c
     });
 }
 
+// The e4m3 wire over native 16-bit tensors: the three entries above with the tensors' dtype (the copier and the pipe
+// refuse what the wire does not carry).
+int ddl_pack_e4m3_16(void *dst, const void *const *srcs, const size_t *elements, int count, int dtype, const float *scale,
+                     void *hip_stream) {
+    return guarded([&] {
+        DDL_REQUIRE(count >= 0 && (count == 0 || (dst && srcs && elements)), DDL_STATUS_INVALID_ARGUMENT,
+                    "bad pack_e4m3_16 args");
+        std::lock_guard<std::mutex> g(abi_copier_mu());
+        const CopySeg *segs = e4m3_segs(count, unconst(srcs), elements, nullptr, scale, nullptr);
+        abi_copier().run(CopyLaunch{0, dst, as_stream(hip_stream), dtype, kDtypeE4m3}, segs, count);
+    });
+}
+
+int ddl_unpack_e4m3_16(void *const *dsts, const void *src, const size_t *elements, const int *ops, int count, int dtype,
+                       int divisor, const float *scale, void *hip_stream, const unsigned char *want, double *sumsq_out) {
+    return guarded([&] {
+        DDL_REQUIRE(count >= 0 && (count == 0 || (src && dsts && elements)) && divisor >= 1 && (!want || sumsq_out),
+                    DDL_STATUS_INVALID_ARGUMENT, "bad unpack_e4m3_16 args");
+        if (count == 0) return;
+        check_float_ops(ops, count, "MIN / MAX take no wire");
+        std::lock_guard<std::mutex> g(abi_copier_mu());
+        const CopySeg *segs = e4m3_segs(count, dsts, elements, ops, scale, want);
+        auto run = [&](double *sq) {
+            abi_copier().run(CopyLaunch{1, const_cast<void *>(src), as_stream(hip_stream), dtype, kDtypeE4m3, divisor, sq},
+                             segs, count);
+        };
+        if (want) unpack_sumsq(count, hip_stream, sumsq_out, run);
+        else run(nullptr);
+    });
+}
+
+int ddl_testing_thread_fused_allreduce_e4m3_16(int nranks, int count, const void *const *srcs, void *const *dsts,
+                                               const size_t *elements, const int *ops, int dtype, const float *prescale,
+                                               const float *postscale, void *hip_stream, size_t *subplans,
+                                               const unsigned char *want, double *sumsq_out, size_t *cut_segs,
+                                               size_t *cut_elems, int max_cuts, int *ncuts) {
+    return guarded([&] {
+        DDL_REQUIRE(nranks >= 1 && nranks <= 64 && count >= 1 && srcs && dsts && elements && (!want || sumsq_out),
+                    DDL_STATUS_INVALID_ARGUMENT, "bad thread fused allreduce");
+        DDL_REQUIRE(dtype == DDL_BFLOAT16, DDL_STATUS_UNSUPPORTED_DTYPE,
+                    "the e4m3 wire carries bfloat16 among the 16-bit tensor dtypes, not " << dtype_name(dtype));
+        check_wire_ranks(kDtypeE4m3, nranks);
+        check_float_ops(ops, count, "MIN / MAX take no wire");
+        check_factors(prescale, postscale, count);
+        FusedCall c{nranks, count, srcs, dsts, elements, 0, kDtypeE4m3, dtype, hip_stream, subplans};
+        c.ops = ops;
+        c.prescale = prescale, c.postscale = postscale;
+        c.want = want, c.sumsq_out = sumsq_out;
+        c.cut_segs = cut_segs, c.cut_elems = cut_elems, c.max_cuts = max_cuts, c.ncuts = ncuts;
+        thread_fused(c);
+    });
+}
+
 int ddl_testing_thread_fused_allreduce_e4m3_fb(int nranks, int count, const void *const *srcs, void *const *dsts,
                                                void *const *residuals, const size_t *elements, const int *ops,
                                                const float *prescale, const float *postscale, void *hip_stream,

@@ -139,8 +139,11 @@ inline int decode_keyed_op(int op, int dtype, bool host, int *base, bool *feedba
     if (q8fb) *feedback = true;
     if (!w && !q8) return 0;
     DDL_REQUIRE(!host, DDL_STATUS_INVALID_ARGUMENT, "wire compression is for device requests only");
-    DDL_REQUIRE(dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
-                "wire compression is defined for float32 only, not " << dtype_name(dtype));
+    // the e4m3 wire alone also carries native bfloat16 tensors (ddl_amd.h "The e4m3 wire"); its error feedback does not
+    DDL_REQUIRE(dtype == DDL_FLOAT || (q8 && dtype == DDL_BFLOAT16), DDL_STATUS_UNSUPPORTED_DTYPE,
+                "wire compression is defined for float32 (WIRE_E4M3: or bfloat16) only, not " << dtype_name(dtype));
+    DDL_REQUIRE(dtype == DDL_FLOAT || !q8fb, DDL_STATUS_UNSUPPORTED_DTYPE,
+                "WIRE_E4M3_FEEDBACK is defined for float32 only, not " << dtype_name(dtype));
     if (q8) return kDtypeE4m3;
     return w == DDL_ALLREDUCE_WIRE_FP16 ? DDL_HALF : DDL_BFLOAT16;
 }

@@ -125,8 +125,10 @@ void validate(const Request &r, int size) {
     switch (r.type) {
         case kReqAllreduce:
             check_allreduce_op(r.op, r.dtype);
-            DDL_REQUIRE(r.wire == 0 || (r.dtype == DDL_FLOAT && !r.host &&
-                                        (r.wire == DDL_HALF || r.wire == DDL_BFLOAT16 || r.wire == kDtypeE4m3)),
+            // (bfloat16 tensors: the e4m3 wire only, without its error feedback)
+            DDL_REQUIRE(r.wire == 0 ||
+                            (!r.host && ((r.dtype == DDL_FLOAT && (r.wire == DDL_HALF || r.wire == DDL_BFLOAT16 || r.wire == kDtypeE4m3)) ||
+                                         (r.dtype == DDL_BFLOAT16 && r.wire == kDtypeE4m3 && !r.feedback))),
                         DDL_STATUS_INVALID_ARGUMENT, "wire dtype " << r.wire << " on a " << dtype_name(r.dtype) << " request");
             check_wire_ranks(r.wire, size);
             DDL_REQUIRE(r.wire != kDtypeE4m3 || !op_is_minmax(r.op), DDL_STATUS_INVALID_ARGUMENT,
@@ -489,10 +491,9 @@ void plan_slices(const Plan &p, const std::vector<Request> &reqs, const std::vec
     for (size_t q = p.req_begin; q <= p.req_end; ++q) {
         const Request &r = reqs[group[q]];
         const size_t b = q == p.req_begin ? p.elem_begin : 0, e = q == p.req_end ? p.elem_end : plan_units(r);
-        if (r.wire == kDtypeE4m3) {  // granules b..e of an fp32 tensor: the tail is the request's, not the granule's
-            const size_t e0 = b * kE4m3Elems, e1 = std::min(e * kE4m3Elems, r.n);
-            fn(static_cast<const char *>(r.in) + e0 * sizeof(float), static_cast<char *>(r.out) + e0 * sizeof(float),
-               (e1 - e0) * sizeof(float));
+        if (r.wire == kDtypeE4m3) {  // granules b..e of an fp32 or bf16 tensor: the tail is the request's, not the granule's
+            const size_t e0 = b * kE4m3Elems, e1 = std::min(e * kE4m3Elems, r.n), ts = dtype_size(r.dtype);
+            fn(static_cast<const char *>(r.in) + e0 * ts, static_cast<char *>(r.out) + e0 * ts, (e1 - e0) * ts);
             continue;
         }
         fn(static_cast<const char *>(r.in) + b * es, static_cast<char *>(r.out) + b * es, (e - b) * es);
@@ -610,14 +611,17 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
     // AVG, 1 MIN, 2 MAX) is communicated too — it is what the plan's allreduce computes — so MIN and
     // MAX requests form groups of their own after the SUM / AVG group of the same dtype and memory;
     // a round without them forms exactly the groups it formed before. The e4m3 wire's internal dtype id is
-    // above every ddl_dtype, so its group comes after all of these.
+    // above every ddl_dtype, so its group comes after all of these. A compressed request whose tensors are not
+    // fp32 (bf16 over the e4m3 wire) adds its source dtype to the key (0 for fp32: those groups and their order are
+    // what they were): a launch has one tensor dtype, and the group sorts behind the fp32-source one of its wire.
     auto kind_rank = [](int op) { return op == DDL_ALLREDUCE_OP_MIN ? 1 : op == DDL_ALLREDUCE_OP_MAX ? 2 : 0; };
-    std::map<std::tuple<int, int, int, int>, std::vector<size_t>> groups;
+    std::map<std::tuple<int, int, int, int, int>, std::vector<size_t>> groups;
     for (size_t i = 0; i < reqs.size(); ++i) {
         if (reqs[i].n == 0) dones.push_back(Done{kNoPlan, i, DDL_STATUS_OK});  // nothing to reduce
         else
             groups[std::make_tuple(reqs[i].wire ? reqs[i].wire : reqs[i].dtype, reqs[i].wire ? 1 : 0,
-                                   reqs[i].host ? 1 : 0, kind_rank(reqs[i].op))]
+                                   reqs[i].host ? 1 : 0, kind_rank(reqs[i].op),
+                                   reqs[i].wire && reqs[i].dtype != DDL_FLOAT ? reqs[i].dtype : 0)]
                 .push_back(i);
     }
     std::vector<hipEvent_t> waited;
@@ -626,12 +630,13 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
         const bool comp = std::get<1>(g.first) != 0;
         const bool host = std::get<2>(g.first) != 0;
         const int kind = reduce_kind(reqs[g.second[0]].op);  // of the whole group: SUM, MIN or MAX
-        const int sdt = comp ? DDL_FLOAT : dt;  // what the tensors hold
+        const int src = std::get<4>(g.first);
+        const int sdt = !comp ? dt : src ? src : DDL_FLOAT;  // what the tensors hold
         // plans, the fusion threshold and the message size count wire bytes (es); the tensors'
         // slices their own (ses)
-        // (the e4m3 wire: es one granule, ses the 252 fp32 elements it carries, the plans in granules)
+        // (the e4m3 wire: es one granule, ses the 252 tensor elements it carries, the plans in granules)
         const bool q8 = dt == kDtypeE4m3;
-        const size_t es = dtype_size(dt), ses = q8 ? kE4m3Elems * sizeof(float) : dtype_size(sdt);
+        const size_t es = dtype_size(dt), ses = q8 ? kE4m3Elems * dtype_size(sdt) : dtype_size(sdt);
         std::vector<size_t> elems, esz;
         for (size_t i : g.second) {
             elems.push_back(plan_units(reqs[i]));
@@ -695,7 +700,7 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
                 // the scale factors: (g (x) a) (x) b in one in-place launch behind the copy, each factor
                 // skipped when it is 1 (two launches when both are present: two separately rounded products)
                 size_t q = p.req_begin;
-                plan_slices(p, reqs, g.second, q8 ? sizeof(float) : ses, [&](const char *s, char *d, size_t n) {
+                plan_slices(p, reqs, g.second, dtype_size(sdt), [&](const char *s, char *d, size_t n) {
                     const Request &r = reqs[g.second[q]];
                     if (s != d && n) DDL_HIP(hipMemcpyAsync(d, s, n, hipMemcpyDeviceToDevice, stream_));
                     if (n && r.prescale != 1.0f) scale_in_place_(d, n, sdt, DDL_ALLREDUCE_OP_SUM, 1, r.prescale);

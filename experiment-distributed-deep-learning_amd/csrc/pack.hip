@@ -12,7 +12,7 @@
 // tile, the tile's segment from a one-byte-per-tile index built on the device (k_tile_index).
 // One kernel, k_seg, walks the tiles for every operation; what an operation does to a 16-byte
 // unit and to a single element is its Op struct (CopyOp, DivOp, CvtPackOp, CvtUnpackOp, ScaleGatherOp,
-// ScaleGather16Op, Q8PackOp, Q8UnpackOp).
+// ScaleGather16Op, Q8PackOp, Q8UnpackOp, Q8Pack16Op, Q8Unpack16Op).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -781,6 +781,120 @@ template <bool SCALE = false> struct Q8UnpackOp {
     __device__ void elem(uint64_t) const {}
 };
 
+// ---- the e4m3 wire over native 16-bit tensors (DDL_ALLREDUCE_WIRE_E4M3 on DDL_BFLOAT16 requests) ----------------
+// Q8Pack16Op / Q8Unpack16Op<DT, SCALE>: the wire side is Q8PackOp's to the byte — whole granules, 1 KiB wire tiles of 4
+// granules, one 16-lane row per granule, SegElems, the factor table, NT accesses — and a wire tile now carries 1008
+// 16-bit elements: 2016 tensor bytes. The tensor side has a mapping of its own: a granule's 252 elements are 504
+// bytes = 63 8-byte units of 4 elements, and granule g starts 504 g bytes into the tensor, so every granule of an
+// 8-byte aligned tensor starts 8-byte aligned (an odd one is not 16-byte aligned, whatever the tensor is). Lane r takes
+// the 8-byte units r, 16 + r, 32 + r, 48 + r (unit 63 does not exist: lane 15 takes three) and the wire dwords of the
+// same numbers, so x[4 h .. 4 h + 3] are the values behind the lane's dword h, lane 15's fourth dword is the scale and
+// quantize_row / dequantize are e4m3.h's, untouched. Each of the four tensor instructions of a row covers 128 contiguous
+// bytes, each wire one 64; there is no parity case. (The other mapping tried — 16-byte tensor vectors r and 16 + r a
+// lane, wire dwords 2 r, 2 r + 1, 32 + 2 r, 33 + 2 r as two 8-byte accesses, rows on an 8-byte-aligned granule base
+// falling back to 8-byte halves — gave the same bits and took 1.09 (pack) and 1.13 (unpack) of this one's time:
+// profiles/wire_e4m3_bf16/probe_mappings.json.) A tensor aligned below 8 bytes and the units over the request's
+// tail go element by element; elements past n count as +0.0 and are never read or written. 2 + 256/252 bytes moved
+// per element against the plain bf16 copy's 4.
+// Pack: c = widen(g) (exact), with SCALE c = widen(g) (x) a through mul_rn, NOT narrowed back (unlike ScaleGather16Op:
+// c goes straight into the granule rule). Unpack: y = code x s, Chain<kDivF32>: AVG's quotient, the postscale, then
+// ONE narrowing (Wide16::narrow: nearest even, NaN stays NaN, an overflow of the narrowing alone gives +-inf).
+using u32x2 = unsigned int __attribute__((ext_vector_type(2)));
+template <class T> union Half4 {
+    u32x2 v;
+    T e[4];
+};
+
+template <int DT, bool SCALE = false> struct Q8Pack16Op {
+    using W = Wide16<DT>;
+    using T = typename W::T;
+    static constexpr uint32_t kUnit = 1;
+    char *fl;
+    const T *tp;
+    uint64_t n;
+    bool v;  // the tensor is 8-byte aligned: its granules' units are
+    Factor<SCALE> fac;
+    template <class... A>
+    __device__ Q8Pack16Op(char *flat, const SegDesc &sd, int seg, A... a)
+        : fl(flat + sd.off), tp(reinterpret_cast<const T *>(sd.ptr)), n(arg_of<const SegElems *>(a...)[seg].n),
+          v((sd.ptr & 7u) == 0), fac(sd, seg, a...) {}
+    __device__ bool vector() const { return true; }  // whole granules: the edges are the tensor side's, below
+    __device__ void vec(uint64_t b) const {
+        const int r = (int)(b >> 4) & 15;
+        const uint64_t g0 = (b >> 8) * kE4m3Elems;  // the granule's first element
+        float x[16];
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const int ui = 16 * h + r;  // the granule's 8-byte unit
+            const uint64_t e = g0 + (uint64_t)ui * 4;
+            Half4<T> q;
+            q.v = u32x2{0, 0};
+            if (ui < 63) {
+                if (v && e + 4 <= n) {
+                    q.v = __builtin_nontemporal_load(reinterpret_cast<const u32x2 *>(tp + e));
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (e + k < n) q.e[k] = __builtin_nontemporal_load(tp + e + k);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) x[4 * h + k] = W::widen(q.e[k]);
+        }
+        fac(x);
+        const u32x4 w = e4m3::quantize_row(x, r);
+        uint32_t *dst = reinterpret_cast<uint32_t *>(fl + (b & ~uint64_t(255))) + r;
+#pragma unroll
+        for (int h = 0; h < 4; ++h) __builtin_nontemporal_store(w[h], dst + 16 * h);
+    }
+    __device__ void elem(uint64_t) const {}
+};
+
+template <int DT, bool SCALE = false> struct Q8Unpack16Op {
+    using W = Wide16<DT>;
+    using T = typename W::T;
+    static constexpr uint32_t kUnit = 1;
+    const char *fl;
+    T *tp;
+    uint64_t n;
+    Chain<kDivF32, SCALE> val;  // on the fp32 values, ahead of the one narrowing
+    bool v;
+    template <class... A>
+    __device__ Q8Unpack16Op(const char *flat, const SegDesc &sd, int seg, float dv, A... a)
+        : fl(flat + sd.off), tp(reinterpret_cast<T *>(sd.ptr)), n(arg_of<const SegElems *>(a...)[seg].n),
+          val(sd, seg, dv, a...), v((sd.ptr & 7u) == 0) {}
+    __device__ bool vector() const { return true; }
+    __device__ void vec(uint64_t b) const {
+        const int r = (int)(b >> 4) & 15;
+        const uint64_t g0 = (b >> 8) * kE4m3Elems;
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(fl + (b & ~uint64_t(255)));
+        u32x4 raw;
+#pragma unroll
+        for (int h = 0; h < 4; ++h) raw[h] = __builtin_nontemporal_load(src + 16 * h + r);
+        const float s = __uint_as_float(__builtin_nontemporal_load(src + 63));
+        float y[16];
+        e4m3::dequantize(raw, s, y);
+        val(y);
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const int ui = 16 * h + r;
+            const uint64_t e = g0 + (uint64_t)ui * 4;
+            if (ui >= 63) continue;
+            Half4<T> q;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) q.e[k] = W::narrow(y[4 * h + k]);
+            if (v && e + 4 <= n) {
+                __builtin_nontemporal_store(q.v, reinterpret_cast<u32x2 *>(tp + e));
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (e + k < n) __builtin_nontemporal_store(q.e[k], tp + e + k);
+            }
+        }
+    }
+    __device__ void elem(uint64_t) const {}
+};
+
 // ScaleGatherOp: the uncompressed prescale, tensor -> flat. Whole fp32 elements (kUnit 4): CopyOp moves
 // bytes, so it has no twin to fold into.
 struct ScaleGatherOp {
@@ -1080,9 +1194,9 @@ void require_16bit_segments(const CopySeg *segs, int count, int dtype) {
         DDL_REQUIRE(segs[i].bytes % 2 == 0 && reinterpret_cast<uintptr_t>(segs[i].ptr) % 2 == 0, DDL_STATUS_INVALID_ARGUMENT,
                     "segment " << i << " is not whole, aligned " << dtype_name(dtype) << " elements");
 }
-// the tensors of a scaled or counted launch: float32 (also under a wire), or bfloat16 without one
+// the tensors of a scaled or counted launch: float32 (also under a wire), or bfloat16 without one or under the e4m3 wire
 void require_scalable_segments(const CopySeg *segs, int count, int dtype, int wire, const char *what) {
-    const bool h16 = dtype == DDL_BFLOAT16 && !wire;
+    const bool h16 = dtype == DDL_BFLOAT16 && (!wire || wire == kDtypeE4m3);
     DDL_REQUIRE(dtype == DDL_FLOAT || h16, DDL_STATUS_UNSUPPORTED_DTYPE,
                 what << " defined for float32 tensors, not " << dtype_name(dtype));
     if (h16) require_16bit_segments(segs, count, dtype);
@@ -1155,6 +1269,7 @@ void SegmentCopier::run(const CopyLaunch &how, const CopySeg *segs, int count) {
     const bool plain = segs == plain_.data();  // copy()'s own segments: every option at its default
     const bool h16 = !wire && dtype == DDL_BFLOAT16;  // native 16-bit tensors whose factors and statistic have kernels
     const bool q8 = wire == kDtypeE4m3;  // the e4m3 wire: granules in the flat buffer, the element counts in a table
+    const bool q16 = q8 && dtype == DDL_BFLOAT16;  // over native bfloat16 tensors: Q8Pack16Op / Q8Unpack16Op
     for (int i = 0; i < n; ++i) {
         const CopySeg &sg = segs[i];
         wanted |= sg.want;
@@ -1179,8 +1294,8 @@ void SegmentCopier::run(const CopyLaunch &how, const CopySeg *segs, int count) {
     // divided; a converting pack has no ops)
     div = div && divisor > 1 && (wire ? dir == 1 : dir != kSumsqInPlace);
     if (wire) {
-        DDL_REQUIRE(dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
-                    "wire compression is defined for float32 sources, not " << dtype_name(dtype));
+        DDL_REQUIRE(dtype == DDL_FLOAT || q16, DDL_STATUS_UNSUPPORTED_DTYPE,
+                    "wire compression is defined for float32 sources (the e4m3 wire: or bfloat16), not " << dtype_name(dtype));
         DDL_REQUIRE(wire == DDL_HALF || wire == DDL_BFLOAT16 || q8, DDL_STATUS_UNSUPPORTED_DTYPE,
                     "wire dtype " << wire << " is neither float16 nor bfloat16");
         DDL_REQUIRE(dir == 0 || dir == 1 || (dir == kSumsqInPlace && !q8), DDL_STATUS_INVALID_ARGUMENT,
@@ -1189,7 +1304,9 @@ void SegmentCopier::run(const CopyLaunch &how, const CopySeg *segs, int count) {
             DDL_REQUIRE(segs[i].bytes == e4m3_granules(segs[i].elems) * kE4m3Granule && !segs[i].stream.on,
                         DDL_STATUS_INVALID_ARGUMENT, "segment " << i << " is not the granules of its elements");
         DDL_REQUIRE(divisor >= 1, DDL_STATUS_INVALID_ARGUMENT, "divisor " << divisor);
-        require_f32_segments(segs, n, 2);
+        DDL_REQUIRE(!q16 || !fbk, DDL_STATUS_INVALID_ARGUMENT, "error feedback of the e4m3 wire takes float32 tensors");
+        if (q16) require_16bit_segments(segs, n, dtype);
+        else require_f32_segments(segs, n, 2);
         for (int i = 0; i < n && fbk; ++i)
             DDL_REQUIRE(!segs[i].bytes || reinterpret_cast<uintptr_t>(segs[i].residual) % 4 == 0, DDL_STATUS_INVALID_ARGUMENT,
                         "residual " << i << " is not aligned float32 elements");
@@ -1370,7 +1487,9 @@ void SegmentCopier::run(const CopyLaunch &how, const CopySeg *segs, int count) {
                 else sumsq(std::integral_constant<int, -1>{});
             } else if (q8) {
                 const SegElems *cnt = reinterpret_cast<const SegElems *>(static_cast<char *>(sl.dev) + rtab);
-                if (dir != 0) seg((Q8UnpackOp<SCALE> *)nullptr, (float)divisor, cnt);
+                if (q16 && dir != 0) seg((Q8Unpack16Op<kDivBF16, SCALE> *)nullptr, (float)divisor, cnt);
+                else if (q16) seg((Q8Pack16Op<kDivBF16, SCALE> *)nullptr, cnt);
+                else if (dir != 0) seg((Q8UnpackOp<SCALE> *)nullptr, (float)divisor, cnt);
                 else if (fbk) seg((Q8PackOp<SCALE, true> *)nullptr, cnt, res);
                 else seg((Q8PackOp<SCALE> *)nullptr, cnt);
             } else if (wire) {
@@ -1419,7 +1538,7 @@ void SegmentCopier::run(const CopyLaunch &how, const CopySeg *segs, int count) {
         const size_t widen = wire && !q8 ? dtype_size(dtype) / dtype_size(wire) : 1;  // the tensor side in its own bytes
         for (int i = 0; i < count; ++i)
             if (segs[i].bytes) {
-                const size_t tb = q8 ? segs[i].elems * sizeof(float) : segs[i].bytes * widen;
+                const size_t tb = q8 ? segs[i].elems * dtype_size(dtype) : segs[i].bytes * widen;
                 acc.push_back(gather ? dep::rd(segs[i].ptr, tb) : dep::wr(segs[i].ptr, tb));
             }
         for (int i = 0; i < count && fbk; ++i)
@@ -1435,9 +1554,10 @@ void SegmentCopier::run(const CopyLaunch &how, const CopySeg *segs, int count) {
         dep::op(stream, label, std::move(acc));
     }
     if (q8stat) {  // the canonical uncompressed sums over what the unpack stored: one extra read of the outputs
+        // (bfloat16 tensors: of the stored bfloat16 values in the 2-byte layout's order, k_seg_sumsq16 in place)
         std::vector<CopySeg> f32(segs, segs + count);
-        for (CopySeg &sg : f32) sg.bytes = sg.elems * sizeof(float), sg.scale = 1.0f, sg.op = DDL_ALLREDUCE_OP_SUM;
-        run(CopyLaunch{kSumsqInPlace, nullptr, stream, DDL_FLOAT, 0, 1, how.sumsq}, f32.data(), count);
+        for (CopySeg &sg : f32) sg.bytes = sg.elems * dtype_size(dtype), sg.scale = 1.0f, sg.op = DDL_ALLREDUCE_OP_SUM;
+        run(CopyLaunch{kSumsqInPlace, nullptr, stream, dtype, 0, 1, how.sumsq}, f32.data(), count);
     }
 }
 

@@ -48,6 +48,16 @@ and runs these requests on its fold-once schedules. The per-granule scale remove
 predivide factor or loss scale is needed for the wire's sake; both still compose), what remains is precision:
 3 mantissa bits, an error below amax / 14 of each granule per quantization. It keeps no per-name state, so
 fresh names are fine (allreduce_gradient takes it); communicators of at most 16 ranks; SUM and AVG only.
+`Compression.fp8` compresses fp32 tensors only: a bf16 tensor under it is submitted uncompressed, as under every
+other kind, so nobody's numerics change with the engine's version.
+
+8 bits for bf16 gradients too: `Compression.fp8_all` is the same wire and the same flag, and also compresses dense
+bf16 device tensors — the one format that halves a bf16 model's bytes per hop (252 values are 504 tensor bytes and
+256 wire bytes). The pack widens (exact), applies the prescale in fp32 and quantizes that product directly; the unpack
+decodes, takes AVG's quotient and the postscale in fp32 and rounds to bf16 once, at the end (nearest even). `sumsq` is
+of the stored bf16 values. It keeps no per-name state either (allreduce_gradient takes it). Opt-in, because a bf16
+gradient that used to travel exactly as bf16 now travels through 3 mantissa bits. There is no `fp8_all_feedback`: the
+engine refuses error feedback for bf16 sources.
 
 8 bits with error feedback: `Compression.fp8_feedback` (include/ddl_amd.h, DDL_ALLREDUCE_WIRE_E4M3_FEEDBACK). On 3
 mantissa bits the bias feedback cures is more than 16 times the 16-bit wires': within a granule whose amax does not
@@ -64,14 +74,17 @@ reset: as for the 16-bit kinds — `reset_error_feedback()` after loading a chec
 scale (unless prescale = 1 / loss scale keeps the residual in the true gradient's units). A name that moves between
 `fp8_feedback` and a 16-bit `_feedback` kind restarts from zero by itself.
 """
+import torch
+
 from ddl.torch import cpp_backend as cb
 
 
 class _Wire:
-    __slots__ = ('name', 'flag')
+    __slots__ = ('name', 'flag', 'dtypes')
 
-    def __init__(self, name: str, flag: int):
-        self.name, self.flag = name, flag
+    def __init__(self, name: str, flag: int, dtypes=(torch.float32,)):
+        # dtypes: the tensor dtypes the kind compresses; any other tensor of a call is submitted uncompressed
+        self.name, self.flag, self.dtypes = name, flag, tuple(dtypes)
 
     @property
     def feedback(self) -> bool:
@@ -97,7 +110,8 @@ class Compression:
     16 ranks). `fp8_feedback`: the same wire with an error-feedback residual per request name for the pack's
     quantization (module docstring: one fp32 copy of every gradient, a 13-byte-per-element pack instead of 5, the
     sum's requantization not compensated, `reset_error_feedback()` as for the 16-bit kinds; not for
-    allreduce_gradient)."""
+    allreduce_gradient). `fp8_all`: `fp8` that also compresses dense bf16 device tensors (module docstring: one bf16
+    rounding, at the end of the unpack; no per-name state; allreduce_gradient takes it)."""
     none = _Wire('none', 0)
     fp16 = _Wire('fp16', cb.WIRE_FP16)
     bf16 = _Wire('bf16', cb.WIRE_BF16)
@@ -106,6 +120,7 @@ class Compression:
     bf16_stochastic = _Wire('bf16_stochastic', cb.WIRE_BF16 | cb.WIRE_STOCHASTIC)
     fp8 = _Wire('fp8', cb.WIRE_E4M3)
     fp8_feedback = _Wire('fp8_feedback', cb.WIRE_E4M3 | cb.WIRE_E4M3_FEEDBACK)
+    fp8_all = _Wire('fp8_all', cb.WIRE_E4M3, (torch.float32, torch.bfloat16))
 
 
 def wire_flag(compression) -> int:
@@ -114,8 +129,14 @@ def wire_flag(compression) -> int:
         return 0
     if not isinstance(compression, _Wire):
         raise TypeError('compression must be Compression.none, .fp16, .bf16, .fp16_feedback, .bf16_feedback, '
-                        f'.bf16_stochastic, .fp8 or .fp8_feedback, not {compression!r}')
+                        f'.bf16_stochastic, .fp8, .fp8_feedback or .fp8_all, not {compression!r}')
     return compression.flag
+
+
+def wire_dtypes(compression) -> tuple:
+    """The tensor dtypes a `compression=` argument compresses (None = Compression.none: the flag is 0 anyway)."""
+    wire_flag(compression)
+    return Compression.none.dtypes if compression is None else compression.dtypes
 
 
 def reset_error_feedback() -> None:

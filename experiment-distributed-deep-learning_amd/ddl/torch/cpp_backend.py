@@ -246,6 +246,13 @@ class CPPBackend:
         sig('ddl_testing_thread_fused_allreduce_e4m3', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp),
             ctypes.POINTER(sz), ctypes.POINTER(ci), fp, fp, vp, ctypes.POINTER(sz), ub, dp, ctypes.POINTER(sz),
             ctypes.POINTER(sz), ci, ctypes.POINTER(ci))
+        # (testing library: the e4m3 wire over native 16-bit tensors — the same entries with the tensors' dtype)
+        sig('ddl_pack_e4m3_16', ci, vp, ctypes.POINTER(vp), ctypes.POINTER(sz), ci, ci, fp, vp)
+        sig('ddl_unpack_e4m3_16', ci, ctypes.POINTER(vp), vp, ctypes.POINTER(sz), ctypes.POINTER(ci), ci, ci, ci, fp, vp, ub,
+            dp)
+        sig('ddl_testing_thread_fused_allreduce_e4m3_16', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp),
+            ctypes.POINTER(sz), ctypes.POINTER(ci), ci, fp, fp, vp, ctypes.POINTER(sz), ub, dp, ctypes.POINTER(sz),
+            ctypes.POINTER(sz), ci, ctypes.POINTER(ci))
         # (testing library: error feedback of the e4m3 wire with caller-owned residuals)
         sig('ddl_pack_e4m3_fb', ci, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(sz), ci, fp, vp)
         sig('ddl_testing_thread_fused_allreduce_e4m3_fb', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp),

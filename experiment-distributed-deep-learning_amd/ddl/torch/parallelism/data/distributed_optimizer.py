@@ -58,7 +58,10 @@ No residual, nothing to reset, the plain 6-byte pack; the stable per-parameter n
 codes and a power-of-two scale per 256 bytes), quantized once per rank and once for the sum, on both paths.
 It keeps no state, composes with `fused_mean`, the norm tracking, `gradient_predivide_factor`, `loss_scale`
 and `DynamicLossScaler` (the per-block scale makes neither factor necessary for the wire's sake), and takes
-communicators of at most 16 ranks.
+communicators of at most 16 ranks. bf16 gradients travel uncompressed under it.
+
+`compression=Compression.fp8_all`: `Compression.fp8` for dense bf16 device gradients too (ddl.torch.compression:
+half a bf16 allreduce's bytes per hop; one bf16 rounding, at the end of the unpack). Same composition, no state.
 
 `compression=Compression.fp8_feedback`: the same wire with error feedback of the pack's quantization — every
 rank keeps what its own quantization removed from each gradient under the gradient's stable name and adds it

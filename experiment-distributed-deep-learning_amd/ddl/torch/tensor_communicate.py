@@ -26,7 +26,7 @@ import torch
 
 from ddl.torch import cpp_backend as cb
 from ddl.torch.communicator import Communicator
-from ddl.torch.compression import Compression, wire_flag
+from ddl.torch.compression import Compression, wire_dtypes, wire_flag
 from ddl.torch.cpp_backend import CPPBackend, check
 from ddl.torch.util import (current_stream_handle, ddl_dtype, memory_kind, require_device_tensor,
                            stream_handle_for)
@@ -136,7 +136,7 @@ def allreduce_gradient(tensor: torch.Tensor, communicator: Communicator = None,
             values = values / communicator.size
         indices = allgather(tensor._indices().t().contiguous(), communicator).t()
         return torch.sparse_coo_tensor(indices, values, tensor.shape)
-    if _compressible(tensor, communicator, wire_flag(compression)):
+    if _compressible(tensor, communicator, compression):
         # the wire format belongs to the keyed requests: one request under a per-communicator
         # running name (every rank reduces its gradients in the same order)
         src = tensor.contiguous()
@@ -442,10 +442,11 @@ def _watch_host(tensors):
 _gradient_ids = collections.defaultdict(lambda: itertools.count())  # allreduce_gradient's compressed requests
 
 
-def _compressible(tensor: torch.Tensor, communicator: Communicator, flag: int, mem: int = None) -> bool:
-    """Whether `compression` applies to this request: a dense fp32 device tensor at size > 1. Every
-    other tensor of a call with `compression` is submitted uncompressed — not an error."""
-    if not flag or tensor.is_sparse or tensor.dtype != torch.float32:
+def _compressible(tensor: torch.Tensor, communicator: Communicator, compression, mem: int = None) -> bool:
+    """Whether `compression` applies to this request: a dense device tensor of one of the kind's dtypes (fp32;
+    Compression.fp8_all: or bf16) at size > 1. Every other tensor of a call with `compression` is submitted
+    uncompressed — not an error."""
+    if not wire_flag(compression) or tensor.is_sparse or tensor.dtype not in wire_dtypes(compression):
         return False
     if (memory_kind(tensor) if mem is None else mem) != cb.MEMORY_DEVICE:
         return False
@@ -556,7 +557,7 @@ def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator 
         _watch_host((tensor, out))
     # argument errors first: a group whose slot is never submitted would stay pending
     key, dt, stream = name.encode(), ddl_dtype(tensor), stream_handle_for(tensor)
-    if _compressible(tensor, communicator, wire_flag(compression), mem):
+    if _compressible(tensor, communicator, compression, mem):
         op = int(op) | wire_flag(compression)
     if sumsq or scaled:
         import ctypes
@@ -647,10 +648,11 @@ def allreduce_async_batch(tensors, names, communicator: Communicator = None, out
         if w:
             handles[i]._sumsq_ref = (values, i)
     done, slots = _native_done(), group.slots()
-    # one submission per (memory kind, wire flag): the engine takes one op per batch, so the fp32
-    # device tensors that travel compressed go apart from the rest
+    # one submission per (memory kind, wire flag): the engine takes one op per batch, so the device tensors
+    # that travel compressed (fp32; under Compression.fp8_all bf16 too, in the same submission — the handler's
+    # group key keeps the two source dtypes apart) go apart from the rest
     flag = wire_flag(compression)
-    wires = [flag if flag and _compressible(t, communicator, flag, m_) else 0 for t, m_ in zip(tensors, mems)]
+    wires = [flag if flag and _compressible(t, communicator, compression, m_) else 0 for t, m_ in zip(tensors, mems)]
     part = list(zip(mems, wires))
     kinds = sorted(set(part))
     for kind in kinds:

@@ -428,6 +428,21 @@ void py_error(const char *log_str);
  * ddl_allreduce_host, or a communicator of more than 16 ranks (a fold of more than 16 inputs goes through
  * partials, which would requantize) return DDL_STATUS_INVALID_ARGUMENT; another dtype
  * DDL_STATUS_UNSUPPORTED_DTYPE. P = 1: with "one_rank_shortcut" 1 nothing is quantized.
+ * bfloat16 tensors: the same flag on a keyed DDL_BFLOAT16 device request, under the same conditions (SUM or AVG,
+ * with or without SUMSQ and SCALE, no other wire bit, at most 16 ranks, keyed entry points only). The wire format
+ * and the fold are unchanged: 252 values per granule, now 504 tensor bytes per 256 wire bytes. Pack: c = widen(g),
+ * which is exact; with a prescale a != 1, c = widen(g) (x) a, one fp32 product that is never part of an fma. c is
+ * NOT narrowed back to bfloat16 (unlike the native prescale of the uncompressed bfloat16 request): it goes straight
+ * into the granule rule above. Unpack: y = code * s, then AVG's quotient by (float)P, then the postscale, all in
+ * fp32, and the store is narrow(y) with the nearest-even rounding of v_cvt_pk_bf16_f32: ONE bfloat16 rounding, at
+ * the end, never one between quotient and factor. NaN stays NaN; a value that overflows only in the narrowing
+ * becomes +-inf. The sum of squares is of the stored bfloat16 values in the 2-byte layout's order (the order of a
+ * native bfloat16 request) over each piece of `out`, taken by one read-only pass behind the unpack. Such requests
+ * form a fusion group of their own behind the fp32-source e4m3 group; a round without one forms exactly the groups
+ * it formed before. Still refused, before anything is registered: DDL_HALF and integer tensors
+ * (DDL_STATUS_UNSUPPORTED_DTYPE), DDL_ALLREDUCE_WIRE_E4M3_FEEDBACK on a bfloat16 request
+ * (DDL_STATUS_UNSUPPORTED_DTYPE), the 16-bit wire flags on a bfloat16 request, DDL_MEMORY_HOST, MIN / MAX and the
+ * unkeyed entry points. tests/_e4m3_bf16_helpers.py restates this paragraph in NumPy.
  *
  * Error feedback of the e4m3 wire: DDL_ALLREDUCE_WIRE_E4M3_FEEDBACK, OR-ed with DDL_ALLREDUCE_WIRE_E4M3 (and
  * optionally DDL_ALLREDUCE_SUMSQ / DDL_ALLREDUCE_SCALE) on the keyed entry points. The wire keeps 3 mantissa bits:

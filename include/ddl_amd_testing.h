@@ -340,6 +340,22 @@ int ddl_testing_thread_fused_allreduce_e4m3(int nranks, int count, const void *c
                                             const float *postscale, void *hip_stream, size_t *subplans,
                                             const unsigned char *want, double *sumsq_out, size_t *cut_segs,
                                             size_t *cut_elems, int max_cuts, int *ncuts);
+/* The e4m3 wire over native 16-bit tensors (ddl_amd.h "The e4m3 wire", bfloat16 tensors; csrc/pack.hip
+ * k_seg<Q8Pack16Op> / k_seg<Q8Unpack16Op>): ddl_pack_e4m3, ddl_unpack_e4m3 and
+ * ddl_testing_thread_fused_allreduce_e4m3 with the tensors' `dtype`. The tensors hold elements[i] values of it
+ * (DDL_BFLOAT16, 2-byte aligned; the unit path needs 8 bytes; DDL_FLOAT runs the fp32 kernels; anything else:
+ * DDL_STATUS_UNSUPPORTED_DTYPE); the flat buffer, the scales, ops, cuts and the fold are those of the fp32 entries.
+ * The unpack narrows once, behind the quotient and the postscale; want / sumsq_out: the sum of the squares of the
+ * stored 16-bit values in the 2-byte layout's order (tests/_sumsq_helpers.py mirror(..., compressed=True)). */
+int ddl_pack_e4m3_16(void *dst, const void *const *srcs, const size_t *elements, int count, int dtype, const float *scale,
+                     void *hip_stream);
+int ddl_unpack_e4m3_16(void *const *dsts, const void *src, const size_t *elements, const int *ops, int count, int dtype,
+                       int divisor, const float *scale, void *hip_stream, const unsigned char *want, double *sumsq_out);
+int ddl_testing_thread_fused_allreduce_e4m3_16(int nranks, int count, const void *const *srcs, void *const *dsts,
+                                               const size_t *elements, const int *ops, int dtype, const float *prescale,
+                                               const float *postscale, void *hip_stream, size_t *subplans,
+                                               const unsigned char *want, double *sumsq_out, size_t *cut_segs,
+                                               size_t *cut_elems, int max_cuts, int *ncuts);
 /* Error feedback of the e4m3 wire (DDL_ALLREDUCE_WIRE_E4M3_FEEDBACK; ddl_amd.h "Error feedback of the e4m3 wire";
  * csrc/pack.hip k_seg<Q8PackOp<SCALE, true>>) with caller-owned residuals. _pack_e4m3_fb: ddl_pack_e4m3 where
  * residuals[i] holds elements[i] fp32 values (4-byte aligned; read, then overwritten with what the pack's
