@@ -348,6 +348,8 @@ namespace {
 static void take_sumsq(int *op, void **user, double **sumsq, float *pre, float *post) {
     *sumsq = nullptr;
     *pre = *post = 1.0f;
+    // (the op proper is below the flags' bits) ADASUM refuses the bit itself, wanted or not
+    if ((*op & 0xff) == DDL_ALLREDUCE_OP_ADASUM) check_adasum(DDL_FLOAT, false, false, (*op & DDL_ALLREDUCE_SUMSQ) != 0);
     if (*op & DDL_ALLREDUCE_SCALE) {
         DDL_REQUIRE(*user, DDL_STATUS_INVALID_ARGUMENT, "DDL_ALLREDUCE_SCALE needs a ddl_scale_arg as the user pointer");
         const ddl_scale_arg arg = *static_cast<const ddl_scale_arg *>(*user);
@@ -401,6 +403,7 @@ int ddl_allreduce_submit_mem(ddl_communicator_id id, const char *key, const void
         take_sumsq(&op, &user, &r.sumsq, &r.prescale, &r.postscale);
         r.wire = decode_keyed_op(op, dtype, r.host, &r.op, &r.feedback, &r.stochastic);  // refusals before anything is posted
         check_wire_ranks(r.wire, c->size());
+        check_adasum_ranks(r.op, c->size());
         check_sumsq(r.sumsq, dtype, r.op, r.host);
         check_scale(r.prescale, r.postscale, dtype, r.op, r.host);
         r.done = done;
@@ -500,6 +503,7 @@ int ddl_allreduce_submit_batch_mem(ddl_communicator_id id, int count, const char
             take_sumsq(&opi, &rs[i].user, &rs[i].sumsq, &rs[i].prescale, &rs[i].postscale);  // (sumsq entries may be NULL)
             rs[i].wire = decode_keyed_op(opi, dtypes[i], rs[i].host, &rs[i].op, &rs[i].feedback, &rs[i].stochastic);
             check_wire_ranks(rs[i].wire, c->size());
+            check_adasum_ranks(rs[i].op, c->size());
             check_sumsq(rs[i].sumsq, dtypes[i], rs[i].op, rs[i].host);
             check_scale(rs[i].prescale, rs[i].postscale, dtypes[i], rs[i].op, rs[i].host);
             rs[i].done = done;

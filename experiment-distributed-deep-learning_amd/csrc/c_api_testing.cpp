@@ -1071,6 +1071,20 @@ int ddl_testing_thread_fused_allreduce_scale(int nranks, int count, const void *
     });
 }
 
+int ddl_testing_thread_adasum(int nranks, int count, const void *const *srcs, void *const *dsts, const size_t *elements,
+                              const float *prescale, const float *postscale, void *hip_stream) {
+    return guarded([&] {
+        DDL_REQUIRE(nranks >= 1 && count >= 1 && srcs && dsts && elements, DDL_STATUS_INVALID_ARGUMENT, "bad thread adasum");
+        check_adasum_ranks(DDL_ALLREDUCE_OP_ADASUM, nranks);
+        check_factors(prescale, postscale, nranks * count);
+        std::vector<AdasumSeg> segs;
+        for (int k = 0; k < nranks * count; ++k)
+            segs.push_back(AdasumSeg{srcs[k], dsts[k], elements[k % count], prescale ? prescale[k] : 1.0f,
+                                     postscale ? postscale[k] : 1.0f});
+        thread_world(nranks).adasum(segs.data(), count, (size_t)config().fusion_threshold_bytes.load(), as_stream(hip_stream));
+    });
+}
+
 int ddl_testing_thread_fused_allreduce_native(int nranks, int count, const void *const *srcs, void *const *dsts,
                                               const size_t *elements, const int *ops, int dtype, const float *prescale,
                                               const float *postscale, void *hip_stream, size_t *subplans,

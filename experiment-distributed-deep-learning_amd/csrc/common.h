@@ -101,6 +101,20 @@ inline void check_allreduce_op(int op, int dtype) {
                 DDL_STATUS_UNSUPPORTED_DTYPE, "AVG is not defined for " << dtype_name(dtype));
 }
 
+// DDL_ALLREDUCE_OP_ADASUM (adasum.h): keyed float32 device requests without a wire flag or a sum of squares,
+// on at most 16 ranks (check_adasum_ranks). The refusals of the C-ABI and of the handler, before anything is
+// registered; the unkeyed entry points refuse the op as unknown (check_allreduce_op).
+inline void check_adasum(int dtype, bool host, bool wire, bool sumsq) {
+    DDL_REQUIRE(dtype == DDL_FLOAT, DDL_STATUS_INVALID_ARGUMENT, "ADASUM is defined for float32 requests, not " << dtype_name(dtype));
+    DDL_REQUIRE(!host, DDL_STATUS_INVALID_ARGUMENT, "ADASUM takes device memory");
+    DDL_REQUIRE(!wire, DDL_STATUS_INVALID_ARGUMENT, "ADASUM takes no wire, feedback or stochastic flag");
+    DDL_REQUIRE(!sumsq, DDL_STATUS_INVALID_ARGUMENT, "ADASUM takes no DDL_ALLREDUCE_SUMSQ");
+}
+inline void check_adasum_ranks(int op, int size) {
+    DDL_REQUIRE(op != DDL_ALLREDUCE_OP_ADASUM || size <= 16, DDL_STATUS_INVALID_ARGUMENT,
+                "DDL_ALLREDUCE_OP_ADASUM takes a communicator of at most 16 ranks, not " << size);
+}
+
 // The `op` of a keyed allreduce request: SUM / AVG / MIN / MAX in the low bits, with SUM / AVG
 // optionally one ddl_allreduce_wire format flag, optionally DDL_ALLREDUCE_WIRE_FEEDBACK with it, or
 // DDL_ALLREDUCE_WIRE_STOCHASTIC with WIRE_BF16; or DDL_ALLREDUCE_WIRE_E4M3 alone (kDtypeE4m3), optionally with
@@ -117,6 +131,10 @@ inline int decode_keyed_op(int op, int dtype, bool host, int *base, bool *feedba
     *stochastic = (op & DDL_ALLREDUCE_WIRE_STOCHASTIC) != 0;
     const int w = op & kWire;
     DDL_REQUIRE(w != kWire, DDL_STATUS_INVALID_ARGUMENT, "both wire flags in allreduce op " << op);
+    if (*base == DDL_ALLREDUCE_OP_ADASUM) {
+        check_adasum(dtype, host, w || q8 || q8fb || *feedback || *stochastic, false);
+        return 0;
+    }
     DDL_REQUIRE(*base == DDL_ALLREDUCE_OP_SUM || *base == DDL_ALLREDUCE_OP_AVG || op_is_minmax(*base),
                 DDL_STATUS_INVALID_ARGUMENT,
                 "unknown allreduce op " << op << " (SUM = 0, AVG = 1, | WIRE_FP16 = 0x100 or WIRE_BF16 = 0x200, "

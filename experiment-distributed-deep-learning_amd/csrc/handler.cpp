@@ -124,7 +124,12 @@ void validate(const Request &r, int size) {
                 "unsupported dtype " << r.dtype);
     switch (r.type) {
         case kReqAllreduce:
-            check_allreduce_op(r.op, r.dtype);
+            if (r.op == DDL_ALLREDUCE_OP_ADASUM) {  // a keyed op only: check_allreduce_op refuses it
+                check_adasum(r.dtype, r.host, r.wire != 0 || r.feedback || r.stochastic, r.sumsq != nullptr);
+                check_adasum_ranks(r.op, size);
+            } else {
+                check_allreduce_op(r.op, r.dtype);
+            }
             // (bfloat16 tensors: the e4m3 wire only, without its error feedback)
             DDL_REQUIRE(r.wire == 0 ||
                             (!r.host && ((r.dtype == DDL_FLOAT && (r.wire == DDL_HALF || r.wire == DDL_BFLOAT16 || r.wire == kDtypeE4m3)) ||
@@ -614,7 +619,11 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
     // above every ddl_dtype, so its group comes after all of these. A compressed request whose tensors are not
     // fp32 (bf16 over the e4m3 wire) adds its source dtype to the key (0 for fp32: those groups and their order are
     // what they were): a launch has one tensor dtype, and the group sorts behind the fp32-source one of its wire.
-    auto kind_rank = [](int op) { return op == DDL_ALLREDUCE_OP_MIN ? 1 : op == DDL_ALLREDUCE_OP_MAX ? 2 : 0; };
+    // Adasum (adasum.h) is a fourth kind, after MAX: its plans hold whole requests and run gather -> Gram ->
+    // coefficients -> apply instead of an allreduce.
+    auto kind_rank = [](int op) {
+        return op == DDL_ALLREDUCE_OP_MIN ? 1 : op == DDL_ALLREDUCE_OP_MAX ? 2 : op == DDL_ALLREDUCE_OP_ADASUM ? 3 : 0;
+    };
     std::map<std::tuple<int, int, int, int, int>, std::vector<size_t>> groups;
     for (size_t i = 0; i < reqs.size(); ++i) {
         if (reqs[i].n == 0) dones.push_back(Done{kNoPlan, i, DDL_STATUS_OK});  // nothing to reduce
@@ -649,9 +658,10 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
         // (Request::stochastic) — found or made once per round, so all plans and pieces of a request share
         // them; none (and no sequence number spent) where the one-rank shortcut skips the data plane
         const bool fused = !host && !(data_->size() == 1 && config().one_rank_shortcut.load()), wire_opts = comp && fused;
+        const bool adasum = std::get<3>(g.first) == 3;  // (its plans take AdasumSegs, not these)
         std::vector<PlanSeg> whole;
-        whole.reserve(fused ? g.second.size() : 0);
-        for (size_t q = 0; fused && q < g.second.size(); ++q) {
+        whole.reserve(fused && !adasum ? g.second.size() : 0);
+        for (size_t q = 0; fused && !adasum && q < g.second.size(); ++q) {
             const Request &r = reqs[g.second[q]];
             whole.push_back(PlanSeg{r.in, r.out, plan_units(r) * es, r.op, r.prescale, r.postscale});
             whole.back().want = r.sumsq != nullptr;
@@ -659,9 +669,30 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
             if (wire_opts && r.feedback) whole.back().residual = residual_(r);
             if (wire_opts && r.stochastic) whole.back().stream = WireStream{stochastic_stream_(r), 0, 1};
         }
-        for (const Plan &p : make_plans(elems, esz, (size_t)config().fusion_threshold_bytes.load())) {
+        const size_t threshold = (size_t)config().fusion_threshold_bytes.load();
+        std::vector<Plan> plans;
+        if (adasum)  // whole requests only: the Gram matrix is of the whole tensor
+            for (const auto &w : adasum_plans(elems, threshold)) plans.push_back(Plan{w.first, 0, w.second - 1, elems[w.second - 1]});
+        else plans = make_plans(elems, esz, threshold);
+        for (const Plan &p : plans) {
             for (size_t q = p.req_begin; q <= p.req_end; ++q) wait_inputs_(reqs[g.second[q]], waited);
-            if (host) {
+            if (adasum && fused) {
+                // pack into this rank's slot (the prescale rides on it), one allgatherv of the slot — the call
+                // allgather_reqs_ makes — then Gram, coefficients and apply on stream_, the apply writing
+                // straight into every request's output
+                std::vector<AdasumSeg> segs;
+                for (size_t q = p.req_begin; q <= p.req_end; ++q) {
+                    const Request &r = reqs[g.second[q]];
+                    segs.push_back(AdasumSeg{r.in, r.out, r.n, r.prescale, r.postscale});
+                }
+                const int P = data_->size();
+                adasum_.run(segs.data(), (int)segs.size(), P, data_->rank(), stream_, fp_.copier,
+                            [&](const void *send, void *recv, size_t per) {
+                                std::vector<size_t> cnt((size_t)P, per), dsp((size_t)P);
+                                for (int q = 0; q < P; ++q) dsp[(size_t)q] = (size_t)q * per;
+                                data_->allgatherv(send, recv, cnt.data(), dsp.data(), DDL_FLOAT, stream_);
+                            });
+            } else if (host) {
                 // memcpy in -> MPI_Allreduce -> memcpy out (MPIRingTokenCommunication.cc:548-733),
                 // the allreduce on the device through pinned chunks
                 std::vector<HostSeg> segs;

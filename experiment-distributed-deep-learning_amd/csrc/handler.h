@@ -31,6 +31,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "adasum.h"
 #include "engine.h"
 #include "fusion.h"
 #include "host_stage.h"
@@ -54,7 +55,7 @@ struct Request {
     void *out = nullptr;
     size_t n = 0;  // elements of `in`
     int dtype = 0;
-    int op = 0;                       // allreduce: SUM / AVG / MIN / MAX (the wire flag decoded into `wire`)
+    int op = 0;                       // allreduce: SUM / AVG / MIN / MAX / ADASUM (the wire flag decoded into `wire`)
     int wire = 0;                     // allreduce: wire dtype of a compressed fp32 request (0: its own dtype)
     bool feedback = false;            // allreduce: DDL_ALLREDUCE_WIRE_FEEDBACK, or with the e4m3 `wire` _E4M3_FEEDBACK (rank-local)
     bool stochastic = false;          // allreduce: DDL_ALLREDUCE_WIRE_STOCHASTIC (only with the bf16 `wire`; rank-local)
@@ -183,6 +184,8 @@ private:
     // multi-request plans: pack -> allreduce -> unpack, pipelined in sub-plans above
     // fusion_pipeline_bytes (fusion.h); its buffer 0 also packs broadcast / allgather plans
     FusionPipe fp_;
+    // DDL_ALLREDUCE_OP_ADASUM plans: gather -> Gram -> coefficients -> apply (adasum.h); packs with fp_'s copier
+    AdasumPipe adasum_;
     // Error feedback (DDL_ALLREDUCE_WIRE_FEEDBACK, DDL_ALLREDUCE_WIRE_E4M3_FEEDBACK): what the wire's rounding removed from this rank's
     // contribution to a key, added back at the key's next request. One fp32 array per key that ever
     // asked for feedback, owned here and freed with the handler (a replaced one is retired, never

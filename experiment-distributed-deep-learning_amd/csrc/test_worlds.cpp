@@ -282,6 +282,23 @@ void ThreadWorld::allreduce_batch(const void *const *in, void *const *out, const
     });
 }
 
+void ThreadWorld::adasum(const AdasumSeg *segs, int count, size_t threshold, hipStream_t user) {
+    while (pipes_.size() < (size_t)P_) pipes_.emplace_back(new FusionPipe);
+    while (adasums_.size() < (size_t)P_) adasums_.emplace_back(new AdasumPipe);
+    std::vector<size_t> elems;
+    for (int i = 0; i < count; ++i) elems.push_back(segs[i].n);
+    const auto plans = adasum_plans(elems, threshold);
+    run_(user, [&](int r, hipStream_t s) {
+        for (const auto &p : plans)
+            adasums_[r]->run(segs + (size_t)r * count + p.first, (int)(p.second - p.first), P_, r, s, pipes_[r]->copier,
+                             [&](const void *send, void *recv, size_t per) {
+                                 std::vector<size_t> cnt((size_t)P_, per), dsp((size_t)P_);
+                                 for (int q = 0; q < P_; ++q) dsp[(size_t)q] = (size_t)q * per;
+                                 ex_[r]->allgatherv(send, recv, cnt.data(), dsp.data(), DDL_FLOAT, s);
+                             });
+    });
+}
+
 size_t ThreadWorld::fused_allreduce(const PlanSeg *segs, int count, int dtype, int src_dtype, size_t cap,
                                     hipStream_t user, const RingConfig &cfg, double *sumsq_out,
                                     std::vector<std::pair<size_t, size_t>> *cuts) {

@@ -14,6 +14,7 @@
 #include <mutex>
 #include <vector>
 
+#include "adasum.h"
 #include "engine.h"
 #include "executor.h"
 
@@ -181,6 +182,10 @@ public:
     size_t fused_allreduce(const PlanSeg *segs, int count, int dtype, int src_dtype, size_t cap, hipStream_t user,
                            const RingConfig &cfg, double *sumsq_out = nullptr,
                            std::vector<std::pair<size_t, size_t>> *cuts = nullptr);
+    // The keyed path's Adasum group on every rank (what the handler runs: adasum_plans' whole-request plans
+    // under `threshold` bytes, AdasumPipe::run per plan), each plan's allgatherv through the rank's
+    // RingExecutor. segs[r * count + i]: rank r's tensor i; the element counts are rank 0's on every rank.
+    void adasum(const AdasumSeg *segs, int count, size_t threshold, hipStream_t user);
 
 private:
     void run_(hipStream_t user, const std::function<void(int, hipStream_t)> &body);
@@ -188,6 +193,7 @@ private:
     std::shared_ptr<ThreadFabric> fab_;
     std::vector<std::unique_ptr<RingExecutor>> ex_;
     std::vector<std::unique_ptr<FusionPipe>> pipes_;  // one per rank (fused_allreduce)
+    std::vector<std::unique_ptr<AdasumPipe>> adasums_;  // one per rank (adasum; packs with pipes_[r]'s copier)
     std::vector<hipStream_t> streams_;
     std::vector<hipEvent_t> done_;
     hipEvent_t fork_ = nullptr;

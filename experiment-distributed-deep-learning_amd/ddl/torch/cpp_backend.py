@@ -41,6 +41,7 @@ STATUS_NAMES = {0: 'OK', 1: 'COMM_ERROR', 2: 'ERROR_UNKNOWN', 3: 'INVALID_ARGUME
 STATUS_CONFIG_MISMATCH = 8
 OP_SUM, OP_AVG = 0, 1  # enum ddl_allreduce_op
 OP_MIN, OP_MAX = 3, 4  # element-wise IEEE 754-2019 minimum / maximum (integers: their order); 2 is not an op
+OP_ADASUM = 6  # the scale-invariant Adasum combination (keyed fp32 device requests; include/ddl_amd.h); 5 is not an op
 WIRE_FP16, WIRE_BF16 = 0x100, 0x200  # enum ddl_allreduce_wire: OR-ed into a keyed fp32 device request's op
 WIRE_FEEDBACK = 0x1000  # error feedback: only together with exactly one of the two wire flags
 WIRE_STOCHASTIC = 0x8000  # stochastic rounding: only together with WIRE_BF16, never with WIRE_FEEDBACK
@@ -170,6 +171,7 @@ class CPPBackend:
         sig('ddl_testing_thread_fused_allreduce_scale', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp),
             ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(ci), ci, fp, fp, vp, ctypes.POINTER(sz), ub, dp,
             ctypes.POINTER(sz), ctypes.POINTER(sz), ci, ctypes.POINTER(ci))
+        sig('ddl_testing_thread_adasum', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(sz), fp, fp, vp)
         # (testing library: the same for native bfloat16 tensors)
         sig('ddl_pack_scale_dtype', ci, vp, ctypes.POINTER(vp), ctypes.POINTER(sz), ci, ci, fp, vp)
         sig('ddl_unpack_scale_dtype', ci, ctypes.POINTER(vp), vp, ctypes.POINTER(sz), ctypes.POINTER(ci), ci, ci, ci, fp,

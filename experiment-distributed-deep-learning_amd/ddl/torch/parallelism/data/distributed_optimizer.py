@@ -122,6 +122,7 @@ class DataParallelismDistributedOptimizer:
     communicator: Communicator = None
     pin_host_gradients: bool = True
     fused_mean: bool = False
+    adasum: bool = False
     compression = Compression.none
     track_grad_norm: bool = False
     max_grad_norm: float = None
@@ -141,7 +142,18 @@ class DataParallelismDistributedOptimizer:
         return self.communicator or Communicator.world()
 
     def _op(self) -> int:
+        if self.adasum:
+            return cb.OP_ADASUM
         return cb.OP_AVG if self.fused_mean else cb.OP_SUM
+
+    def _check_adasum(self, g) -> None:
+        """`adasum`: a gradient the engine's Adasum op cannot carry is an error, never a silent mean."""
+        if self._tracking():
+            raise ValueError('adasum does not compose with track_grad_norm / max_grad_norm / skip_nonfinite')
+        if g.is_sparse or not g.is_cuda or g.dtype != torch.float32 or not g.is_contiguous():
+            raise ValueError('adasum needs dense, contiguous float32 device gradients, not a '
+                             f'{"sparse " if g.is_sparse else ""}{g.dtype} {g.device.type} one'
+                             f'{"" if g.is_sparse or g.is_contiguous() else " (strided)"}')
 
     def _tracking(self) -> bool:
         return bool(self.track_grad_norm or self.max_grad_norm is not None or self.skip_nonfinite)
@@ -206,6 +218,8 @@ class DataParallelismDistributedOptimizer:
         g = p.grad
         if not self._syncing or g is None or g.is_sparse or not g.is_contiguous() or self._comm().size <= 1:
             return  # no_sync, or left to step() (sparse / strided gradients)
+        if self.adasum:
+            self._check_adasum(g)
         if p in self._grad_handles:
             raise RuntimeError(f'{key}: gradient accumulated again while its allreduce is pending; run the '
                                'earlier backward passes inside no_sync()')
@@ -242,6 +256,11 @@ class DataParallelismDistributedOptimizer:
         comm = self._comm()
         track = self._tracking()
         inv = self._unscale()
+        if self.adasum:  # before anything is submitted, at every size
+            for group in self.param_groups:
+                for p in group['params']:
+                    if p.grad is not None and p not in (self._grad_handles or {}):
+                        self._check_adasum(p.grad)
         if comm.size <= 1:
             if inv != 1.0:  # nothing is communicated: the unscale is torch's
                 for group in self.param_groups:
@@ -254,7 +273,7 @@ class DataParallelismDistributedOptimizer:
             return
         # gradients already submitted by the backward hooks (overlap_backward)
         hooked = self._drain_hooked()
-        fused = self.fused_mean  # the engine has divided already
+        fused = self.fused_mean or self.adasum  # the engine has divided already (Adasum: nothing is divided)
         # the squared norm's contributions, all of the sums (fused_mean off) or all of the means
         contributions = []
         for p, h in hooked.items():
@@ -395,6 +414,7 @@ def data_parallelism_distributed_optimizer_wrapper(
         overlap_backward: bool = False,
         bucket_bytes: int = 32 << 20,
         fused_mean: bool = False,
+        adasum: bool = False,
         compression=Compression.none,
         track_grad_norm: bool = False,
         max_grad_norm: float = None,
@@ -426,7 +446,15 @@ def data_parallelism_distributed_optimizer_wrapper(
     `max_grad_norm`: clip the averaged gradients to that global L2 norm before the step;
     `skip_nonfinite`: skip the wrapped step() when a gradient holds an inf or NaN. The last two imply
     the first. `gradient_predivide_factor` (finite, > 0; the same on every rank): the engine-handled
-    gradients are divided by it before the sum and multiplied by it after (module docstring)."""
+    gradients are divided by it before the sum and multiplied by it after (module docstring).
+    `adasum`: the gradients are combined by the engine's Adasum op (`cb.OP_ADASUM`, include/ddl_amd.h
+    "Adasum": what is orthogonal in the ranks' gradients is summed, what is parallel averaged) and nothing
+    is divided by the size. Every gradient must be a dense, contiguous fp32 device tensor (bf16, CPU, sparse
+    or strided: ValueError at the first step); together with `fused_mean`, a `compression`,
+    `track_grad_norm`, `max_grad_norm` or `skip_nonfinite` it is a ValueError (so a DynamicLossScaler, which
+    needs `skip_nonfinite`, is refused at its first step; a fixed `optimizer.loss_scale` works through the
+    postscale). The engine gathers every rank's gradients: P times the gradient bytes in device memory, and
+    (P - 1) n bytes received per rank where the mean moves about 2 n; at most 16 ranks."""
     opt_cls = optimizer.__class__
     assert issubclass(opt_cls, torch.optim.Optimizer)
     cls = type(opt_cls.__name__, (DataParallelismDistributedOptimizer, opt_cls), {})
@@ -435,6 +463,11 @@ def data_parallelism_distributed_optimizer_wrapper(
     res.communicator = communicator
     res.pin_host_gradients = pin_host_gradients
     res.fused_mean = bool(fused_mean)
+    res.adasum = bool(adasum)
+    if res.adasum and (fused_mean or wire_flag(compression) or track_grad_norm or max_grad_norm is not None
+                       or skip_nonfinite):
+        raise ValueError('adasum does not compose with fused_mean, compression, track_grad_norm, max_grad_norm '
+                         'or skip_nonfinite')
     wire_flag(compression)  # a TypeError here, not at the first step
     res.compression = Compression.none if compression is None else compression
     res.track_grad_norm = bool(track_grad_norm)

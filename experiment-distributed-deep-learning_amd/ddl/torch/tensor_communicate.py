@@ -103,8 +103,11 @@ def allreduce_batch_(tensors, communicator: Communicator = None, op: int = cb.OP
 
 def allreduce_gradient(tensor: torch.Tensor, communicator: Communicator = None,
                        return_mean: bool = True, fused_mean: bool = False,
-                       compression=Compression.none) -> torch.Tensor:
+                       compression=Compression.none, op: int = None) -> torch.Tensor:
     """Dense gradient: allreduce, then divide by the size (tensor_communicate.py:21-25). With
+    `op=cb.OP_ADASUM` (a dense fp32 device gradient, no compression; anything else: ValueError) the gradient
+    is combined by the engine's Adasum op through the keyed path and nothing is divided: Adasum already
+    averages what is parallel (include/ddl_amd.h "Adasum"). With
     `fused_mean` the engine takes the mean itself (`op=cb.OP_AVG`: the IEEE quotient, in the kernel
     that writes the result) and no `div_` runs here; on a device tensor the last bit may then
     differ from torch's `div_`, which multiplies by the reciprocal, when the size is no power of two.
@@ -122,6 +125,12 @@ def allreduce_gradient(tensor: torch.Tensor, communicator: Communicator = None,
     divides the values; duplicate indices stay uncoalesced, as IndexedSlices keeps them.
     """
     communicator = _comm(communicator)
+    if op is not None and int(op) == cb.OP_ADASUM:
+        _check_adasum((tensor,), compression, False, 'allreduce_gradient')
+        name = f'allreduce_gradient/adasum/{next(_gradient_ids[communicator.id]):08d}'
+        return allreduce_async(tensor, name, communicator, op=cb.OP_ADASUM).wait()
+    if op is not None:
+        raise ValueError(f'allreduce_gradient takes op=cb.OP_ADASUM or none, not {op!r}')
     if wire_flag(compression) & (cb.WIRE_FEEDBACK | cb.WIRE_E4M3_FEEDBACK):
         raise ValueError(f'allreduce_gradient does not take {compression!r}: its compressed requests get a fresh '
                          'name per call, which would leak one error-feedback residual per call; use allreduce_async '
@@ -472,6 +481,23 @@ def _check_sumsq(tensors, op: int, what: str) -> None:
             raise ValueError(f'{what}: sumsq is defined for float32 and bfloat16 tensors, not {t.dtype}')
 
 
+def _check_adasum(tensors, compression, sumsq, what: str) -> None:
+    """`op=cb.OP_ADASUM` is the engine's DDL_ALLREDUCE_OP_ADASUM: dense, contiguous fp32 device tensors, no
+    compression and no sumsq (include/ddl_amd.h "Adasum"). Raised before any library call."""
+    if wire_flag(compression):
+        raise ValueError(f'{what}: OP_ADASUM takes no compression, got {compression!r}')
+    if sumsq:
+        raise ValueError(f'{what}: OP_ADASUM takes no sumsq')
+    for t in tensors:
+        if t.is_sparse or not t.is_cuda:
+            raise ValueError(f'{what}: OP_ADASUM needs a dense device tensor, not a {t.device.type} '
+                             f'{"sparse " if t.is_sparse else ""}one')
+        if t.dtype != torch.float32:
+            raise ValueError(f'{what}: OP_ADASUM is defined for float32 tensors, not {t.dtype}')
+        if not t.is_contiguous():
+            raise ValueError(f'{what}: OP_ADASUM needs a contiguous tensor')
+
+
 def _scale_factor(value, what: str) -> float:
     """A prescale / postscale as the engine takes it: an fp32 value, finite and > 0 (ValueError otherwise)."""
     import math
@@ -514,6 +540,11 @@ def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator 
     """Register a keyed allreduce (`op`: cb.OP_SUM, cb.OP_AVG for the mean, cb.OP_MIN / cb.OP_MAX for
     the element-wise minimum / maximum — like a compression, the same on every rank for a name, and
     never together with one: ValueError); returns a Handle.
+    `op=cb.OP_ADASUM` (a dense, contiguous fp32 device tensor; no compression and no sumsq — anything else:
+    ValueError before anything is submitted): the scale-invariant Adasum combination of include/ddl_amd.h
+    "Adasum", which sums what is orthogonal in the ranks' tensors and averages what is parallel; nothing is
+    divided by the size. It composes with `prescale` / `postscale`. The engine gathers every rank's tensor:
+    P times the tensor in device memory, (P - 1) n bytes received per rank; at most 16 ranks.
     `compression` (Compression.fp16 / .bf16): a dense fp32 device tensor at size > 1 is sent and
     summed as 16-bit values and comes back as fp32 (ddl.torch.compression; every rank must pass the
     same compression for a name); any other tensor is submitted as without it. With
@@ -544,6 +575,8 @@ def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator 
     DEVICE_CPU (AllreduceOp.cc:68) — are fused through pinned staging to the GPU and back.
     """
     _check_op_compression(op, compression)
+    if int(op) == cb.OP_ADASUM:
+        _check_adasum((tensor,) if output is None else (tensor, output), compression, sumsq, 'allreduce_async')
     if sumsq:
         _check_sumsq((tensor,) if output is None else (tensor, output), op, 'allreduce_async')
     pre, post = _scale_factor(prescale, 'allreduce_async'), _scale_factor(postscale, 'allreduce_async')
@@ -591,7 +624,8 @@ def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator 
 def allreduce_async_batch(tensors, names, communicator: Communicator = None, outputs=None, op: int = cb.OP_SUM,
                           compression=Compression.none, sumsq=False, prescale=1.0, postscale=1.0):
     """Register several keyed allreduces at once (one engine wake-up, one input-ready event), all
-    with `op` (cb.OP_SUM, cb.OP_AVG for the mean, cb.OP_MIN / cb.OP_MAX); returns one Handle per tensor. Same key rules as `allreduce_async`; device and host tensors
+    with `op` (cb.OP_SUM, cb.OP_AVG for the mean, cb.OP_MIN / cb.OP_MAX, or cb.OP_ADASUM under the rules of
+    `allreduce_async`: dense, contiguous fp32 device tensors, no compression, no sumsq); returns one Handle per tensor. Same key rules as `allreduce_async`; device and host tensors
     may be mixed (one submission per memory kind). `compression` (Compression.fp16 / .bf16) applies
     to the dense fp32 device tensors at size > 1 (ddl.torch.compression); the others are submitted
     uncompressed, so a mixed batch goes as one compressed and one plain submission. The handles
@@ -611,6 +645,9 @@ def allreduce_async_batch(tensors, names, communicator: Communicator = None, out
     wanted = [bool(sumsq)] * len(tensors) if isinstance(sumsq, (bool, int)) else [bool(w) for w in sumsq]
     if len(wanted) != len(tensors):
         raise ValueError('sumsq: one flag per tensor')
+    if int(op) == cb.OP_ADASUM:
+        _check_adasum(tensors + ([] if outputs is None else list(outputs)), compression, any(wanted),
+                      'allreduce_async_batch')
     if any(wanted):
         outs_ = tensors if outputs is None else list(outputs)
         _check_sumsq([x for t, o, w in zip(tensors, outs_, wanted) if w for x in (t, o)], op, 'allreduce_async_batch')

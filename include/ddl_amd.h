@@ -81,6 +81,10 @@ enum ddl_memory { DDL_MEMORY_DEVICE = 0, DDL_MEMORY_HOST = 1 };
  * Horovod's numbers; 2 is not an op) are the element-wise minimum / maximum over the ranks. */
 enum ddl_allreduce_op { DDL_ALLREDUCE_OP_SUM = 0, DDL_ALLREDUCE_OP_AVG = 1, DDL_ALLREDUCE_OP_MIN = 3,
                         DDL_ALLREDUCE_OP_MAX = 4 };
+/* Adasum (MI355X extension, Horovod's op=Adasum; "Adasum" in the data-plane section): one more value of `op`, for the
+ * keyed entry points and DDL_FLOAT device requests only — every other entry point refuses it as it refuses 2 and 5,
+ * which are not ops. An enum of its own: ddl_allreduce_op above holds what every allreduce entry point takes. */
+enum ddl_allreduce_op_keyed { DDL_ALLREDUCE_OP_ADASUM = 6 };
 /* Wire format of a keyed device allreduce of DDL_FLOAT tensors (MI355X extension, Horovod's
  * Compression.fp16): at most one flag, OR-ed into `op`. The gradients travel and are summed as
  * 16-bit values and come back as fp32 (see the data-plane section). */
@@ -514,7 +518,33 @@ void py_error(const char *log_str);
  * the SUM / AVG group of the same dtype and memory, MIN before MAX). Ranks that disagree about a
  * key's kind post different collectives.
  * Refusals, before anything is registered: MIN / MAX with a wire flag or DDL_ALLREDUCE_WIRE_FEEDBACK
- * returns DDL_STATUS_INVALID_ARGUMENT; op values 2 and above 4 stay DDL_STATUS_INVALID_ARGUMENT.
+ * returns DDL_STATUS_INVALID_ARGUMENT; op values 2, 5 and above 6 stay DDL_STATUS_INVALID_ARGUMENT.
+ *
+ * Adasum: DDL_ALLREDUCE_OP_ADASUM = 6 (MI355X extension, Horovod's op=Adasum), the scale-invariant combination
+ * for large-batch data parallelism: it sums the components of the ranks' tensors that are orthogonal and
+ * averages the components that are parallel. For two tensors a, b of one shape, with the dot products and
+ * norms taken over the WHOLE tensor in fp64:
+ *     adasum(a, b) = (1 - a.b / (2 a.a)) a + (1 - a.b / (2 b.b)) b
+ * A coefficient whose own norm^2 is exactly 0 is 1 (adasum(0, b) = b, adasum(0, 0) = 0); there is no
+ * threshold, so the result is scale-invariant and survives a loss scale. Over P ranks a list starts as
+ * x_0 ... x_{P-1} in rank order; each level replaces the adjacent pairs (0, 1), (2, 3), ... by their adasum and
+ * carries an odd last entry up unchanged, until one entry is left (P = 2^k: Horovod's tree; every
+ * 1 <= P <= 16 is defined). Nothing is divided by P. The result is a weighted sum of the P inputs, the fp64
+ * weights computed from the tensor's P x P Gram matrix, accumulated in fp64 and rounded once to fp32; every
+ * rank stores the same bits, run after run (no float atomics, no order that depends on a launch shape).
+ * A NaN or inf anywhere in any rank's tensor makes THAT TENSOR non-finite on every rank; the other tensors
+ * of the round are untouched.
+ * Accepted on ddl_allreduce_submit[_mem] and ddl_allreduce_submit_batch[_mem] for DDL_FLOAT device tensors,
+ * alone or with DDL_ALLREDUCE_SCALE (the prescale on the way in, the postscale multiplied into the weights).
+ * Like MIN / MAX the kind is communicated: Adasum requests form fusion groups of their own, after MAX. A
+ * tensor is never cut: a plan holds whole requests, a request above "fusion_threshold_bytes" is a plan of
+ * its own, and nothing is pipelined in "fusion_pipeline_bytes" pieces. Cost: each plan is ONE allgatherv of
+ * the packed requests into a gather buffer of P x the plan's bytes, so a rank receives (P - 1) n bytes where
+ * a SUM moves about 2 n, followed by two passes over the P copies (csrc/adasum.hip).
+ * Refusals, before anything is registered (the communicator works afterwards), all
+ * DDL_STATUS_INVALID_ARGUMENT: a dtype other than DDL_FLOAT, DDL_MEMORY_HOST, any wire, feedback or
+ * stochastic flag, DDL_ALLREDUCE_SUMSQ, a communicator of more than 16 ranks, and every unkeyed entry point
+ * (ddl_allreduce, _batch, _host, the local ring). P = 1: the input with the scale factors applied, as SUM.
  *
  * Sum of squares (DDL_ALLREDUCE_SUMSQ in `op`, `user` a ddl_sumsq_arg): an optional per-request output of a
  * keyed DDL_FLOAT device request with op SUM or AVG (a wire flag and the feedback bit allowed):

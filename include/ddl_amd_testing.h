@@ -312,6 +312,13 @@ int ddl_testing_thread_fused_allreduce_native(int nranks, int count, const void 
                                               const float *postscale, void *hip_stream, size_t *subplans,
                                               const unsigned char *want, double *sumsq_out, size_t *cut_segs,
                                               size_t *cut_elems, int max_cuts, int *ncuts);
+/* A DDL_ALLREDUCE_OP_ADASUM request group (ddl_amd.h "Adasum"; csrc/adasum.hip) over nranks virtual ranks on
+ * threads, as the keyed handler runs it: whole-request plans under "fusion_threshold_bytes", each packed,
+ * gathered by one allgatherv of the rank's executor, then Gram, coefficients and apply. `count` fp32 tensors of
+ * elements[i] values; srcs / dsts [r * count + i]; prescale / postscale [r * count + i] (NULL = none). At most
+ * 16 virtual ranks. */
+int ddl_testing_thread_adasum(int nranks, int count, const void *const *srcs, void *const *dsts, const size_t *elements,
+                              const float *prescale, const float *postscale, void *hip_stream);
 /* The kernels of the e4m3 wire (DDL_ALLREDUCE_WIRE_E4M3; ddl_amd.h "The e4m3 wire"; csrc/pack.hip k_seg<Q8PackOp> /
  * k_seg<Q8UnpackOp>, csrc/reduce_kernels.hip k_foldq). The tensors hold elements[i] fp32 values (4-byte aligned);
  * segment i of the flat buffer is its ceil(elements[i] / 252) granules of 256 bytes at the running sum of the
