@@ -115,6 +115,31 @@ inline void check_adasum_ranks(int op, int size) {
                 "DDL_ALLREDUCE_OP_ADASUM takes a communicator of at most 16 ranks, not " << size);
 }
 
+// DDL_ALLREDUCE_WIRE_TOPK (topk.h): keyed float32 device requests with op SUM or AVG and no other wire,
+// feedback or stochastic bit, of fewer than 2^31 elements; no DDL_ALLREDUCE_SUMSQ. take_topk: whether `*op`
+// (as the caller passed it) carries the flag, which it takes out; the refusals of the C-ABI before anything is
+// registered. The unkeyed entry points refuse the flag as an unknown op.
+inline void check_topk_elements(size_t n) {
+    DDL_REQUIRE(n < (size_t(1) << 31), DDL_STATUS_INVALID_ARGUMENT,
+                "DDL_ALLREDUCE_WIRE_TOPK takes tensors of fewer than 2^31 elements, not " << n);
+}
+inline void check_topk_ppm(long long ppm) {
+    DDL_REQUIRE(ppm >= 1 && ppm <= 1000000, DDL_STATUS_INVALID_ARGUMENT, "wire_topk_ppm must be in [1, 1000000], not " << ppm);
+}
+inline bool take_topk(int *op, int dtype, bool host, size_t n) {
+    if (!(*op & DDL_ALLREDUCE_WIRE_TOPK)) return false;
+    DDL_REQUIRE(!(*op & DDL_ALLREDUCE_SUMSQ), DDL_STATUS_INVALID_ARGUMENT, "WIRE_TOPK takes no DDL_ALLREDUCE_SUMSQ");
+    const int base = *op & ~(DDL_ALLREDUCE_WIRE_TOPK | DDL_ALLREDUCE_SCALE);
+    DDL_REQUIRE(base == DDL_ALLREDUCE_OP_SUM || base == DDL_ALLREDUCE_OP_AVG, DDL_STATUS_INVALID_ARGUMENT,
+                "WIRE_TOPK takes SUM or AVG and no other wire, feedback or stochastic flag (allreduce op " << *op << ")");
+    DDL_REQUIRE(!host, DDL_STATUS_INVALID_ARGUMENT, "wire compression is for device requests only");
+    DDL_REQUIRE(dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
+                "WIRE_TOPK is defined for float32 only, not " << dtype_name(dtype));
+    check_topk_elements(n);
+    *op &= ~DDL_ALLREDUCE_WIRE_TOPK;
+    return true;
+}
+
 // The `op` of a keyed allreduce request: SUM / AVG / MIN / MAX in the low bits, with SUM / AVG
 // optionally one ddl_allreduce_wire format flag, optionally DDL_ALLREDUCE_WIRE_FEEDBACK with it, or
 // DDL_ALLREDUCE_WIRE_STOCHASTIC with WIRE_BF16; or DDL_ALLREDUCE_WIRE_E4M3 alone (kDtypeE4m3), optionally with

@@ -108,6 +108,10 @@ struct Config {
     // of this process starts from (ddl_amd.h; read as its 64 bits when a request's S is computed). Per
     // process, not in shared_hash: the random bits are rank-local and change nothing that is communicated.
     std::atomic<long long> wire_stochastic_seed{0};
+    // the top-k wire (DDL_ALLREDUCE_WIRE_TOPK): the density in parts per million, 1 .. 10^6 (default 1 %): a
+    // tensor of n elements sends k = min(n, max(1, ceil(n ppm / 10^6))) entries. Shared (in shared_hash): the
+    // ranks' slot sizes, and so the allgatherv they post, depend on it.
+    std::atomic<long long> wire_topk_ppm{10000};
     // keyed rounds: 1 — a completion thread waits for a round's data plane and fires its done()
     // calls while the engine thread negotiates and enqueues the next round; 0 — the engine
     // thread waits for each round before negotiating the next (as the reference's recv thread
@@ -153,7 +157,7 @@ struct Config {
     // Hash of the tunables every rank of a communicator must share (they shape the collectives'
     // programs, the fusion plans and the host chunks): algo, slice_bytes, rings, max_slices,
     // fusion_threshold_bytes, tune, fusion_pipeline_bytes, reference_order, host_chunk_bytes,
-    // rccl_min_ctas, rccl_max_ctas.
+    // rccl_min_ctas, rccl_max_ctas, wire_topk_ppm.
     // Never 0 or kCfgMismatch. Local tunables (log_level, cycle_time_us, host_copy_threads,
     // host_zero_copy, pipeline_rounds, one_rank_shortcut, wire_feedback_epoch, wire_stochastic_seed) are not
     // in it.

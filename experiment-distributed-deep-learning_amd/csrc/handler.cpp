@@ -136,6 +136,12 @@ void validate(const Request &r, int size) {
                                          (r.dtype == DDL_BFLOAT16 && r.wire == kDtypeE4m3 && !r.feedback))),
                         DDL_STATUS_INVALID_ARGUMENT, "wire dtype " << r.wire << " on a " << dtype_name(r.dtype) << " request");
             check_wire_ranks(r.wire, size);
+            if (r.topk) {  // what take_topk lets through
+                DDL_REQUIRE(r.dtype == DDL_FLOAT && !r.host && r.wire == 0 && !r.feedback && !r.stochastic && !r.sumsq &&
+                                (r.op == DDL_ALLREDUCE_OP_SUM || r.op == DDL_ALLREDUCE_OP_AVG),
+                            DDL_STATUS_INVALID_ARGUMENT, "the top-k wire takes a float32 device SUM or AVG request and no other flag");
+                check_topk_elements(r.n);
+            }
             DDL_REQUIRE(r.wire != kDtypeE4m3 || !op_is_minmax(r.op), DDL_STATUS_INVALID_ARGUMENT,
                         "the e4m3 wire takes SUM or AVG");
             DDL_REQUIRE(!r.feedback || r.wire != 0, DDL_STATUS_INVALID_ARGUMENT, "error feedback without a wire dtype");
@@ -517,10 +523,10 @@ std::vector<int> plan_ops(const Plan &p, const std::vector<Request> &reqs, const
 // Engine thread only. hipMalloc does not wait for the device (profiles/r06/s17); the zeroing is
 // posted on stream_, so it runs after every earlier pack of this key and before the next one. A
 // residual of another element count is retired, not freed: its last pack may still be running. A key that
-// comes back under the other family of wire (e4m3 after a 16-bit wire, or the reverse) restarts from zero.
+// comes back under another family of wire (the 16-bit wires, e4m3, top-k) restarts from zero.
 void *RequestHandler::residual_(const Request &r) {
     const long long epoch = config().wire_feedback_epoch.load();
-    const int family = r.wire == kDtypeE4m3 ? kFamilyE4m3 : kFamily16;
+    const int family = r.topk ? kFamilyTopk : r.wire == kDtypeE4m3 ? kFamilyE4m3 : kFamily16;
     Residual &res = residuals_[r.key];
     if (res.ptr && res.n == r.n && res.epoch == epoch && res.family == family) return res.ptr;
     res.family = family;
@@ -620,16 +626,19 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
     // fp32 (bf16 over the e4m3 wire) adds its source dtype to the key (0 for fp32: those groups and their order are
     // what they were): a launch has one tensor dtype, and the group sorts behind the fp32-source one of its wire.
     // Adasum (adasum.h) is a fourth kind, after MAX: its plans hold whole requests and run gather -> Gram ->
-    // coefficients -> apply instead of an allreduce.
-    auto kind_rank = [](int op) {
-        return op == DDL_ALLREDUCE_OP_MIN ? 1 : op == DDL_ALLREDUCE_OP_MAX ? 2 : op == DDL_ALLREDUCE_OP_ADASUM ? 3 : 0;
+    // coefficients -> apply instead of an allreduce. The top-k wire (topk.h) is a fifth, after Adasum: whole
+    // requests too, select -> emit -> gather -> combine (SUM and AVG share it: the quotient is rank-local).
+    // Where the one-rank shortcut skips the data plane nothing is selected: those requests are plain SUM / AVG ones.
+    const bool shortcut = data_->size() == 1 && config().one_rank_shortcut.load();
+    auto kind_rank = [shortcut](const Request &r) {
+        return r.topk && !shortcut ? 4 : r.op == DDL_ALLREDUCE_OP_MIN ? 1 : r.op == DDL_ALLREDUCE_OP_MAX ? 2 : r.op == DDL_ALLREDUCE_OP_ADASUM ? 3 : 0;
     };
     std::map<std::tuple<int, int, int, int, int>, std::vector<size_t>> groups;
     for (size_t i = 0; i < reqs.size(); ++i) {
         if (reqs[i].n == 0) dones.push_back(Done{kNoPlan, i, DDL_STATUS_OK});  // nothing to reduce
         else
             groups[std::make_tuple(reqs[i].wire ? reqs[i].wire : reqs[i].dtype, reqs[i].wire ? 1 : 0,
-                                   reqs[i].host ? 1 : 0, kind_rank(reqs[i].op),
+                                   reqs[i].host ? 1 : 0, kind_rank(reqs[i]),
                                    reqs[i].wire && reqs[i].dtype != DDL_FLOAT ? reqs[i].dtype : 0)]
                 .push_back(i);
     }
@@ -659,9 +668,10 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
         // them; none (and no sequence number spent) where the one-rank shortcut skips the data plane
         const bool fused = !host && !(data_->size() == 1 && config().one_rank_shortcut.load()), wire_opts = comp && fused;
         const bool adasum = std::get<3>(g.first) == 3;  // (its plans take AdasumSegs, not these)
+        const bool topk = std::get<3>(g.first) == 4;    // (TopkSegs; always fused)
         std::vector<PlanSeg> whole;
-        whole.reserve(fused && !adasum ? g.second.size() : 0);
-        for (size_t q = 0; fused && !adasum && q < g.second.size(); ++q) {
+        whole.reserve(fused && !adasum && !topk ? g.second.size() : 0);
+        for (size_t q = 0; fused && !adasum && !topk && q < g.second.size(); ++q) {
             const Request &r = reqs[g.second[q]];
             whole.push_back(PlanSeg{r.in, r.out, plan_units(r) * es, r.op, r.prescale, r.postscale});
             whole.back().want = r.sumsq != nullptr;
@@ -671,7 +681,7 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
         }
         const size_t threshold = (size_t)config().fusion_threshold_bytes.load();
         std::vector<Plan> plans;
-        if (adasum)  // whole requests only: the Gram matrix is of the whole tensor
+        if (adasum || topk)  // whole requests only: the Gram matrix, the selection, is of the whole tensor
             for (const auto &w : adasum_plans(elems, threshold)) plans.push_back(Plan{w.first, 0, w.second - 1, elems[w.second - 1]});
         else plans = make_plans(elems, esz, threshold);
         for (const Plan &p : plans) {
@@ -692,6 +702,21 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
                                 for (int q = 0; q < P; ++q) dsp[(size_t)q] = (size_t)q * per;
                                 data_->allgatherv(send, recv, cnt.data(), dsp.data(), DDL_FLOAT, stream_);
                             });
+            } else if (topk) {
+                // a + residual selected and emitted into this rank's slot (the residual keeps the rest), one
+                // allgatherv of the slot, then the combine writes straight into every request's output
+                std::vector<TopkSeg> segs;
+                for (size_t q = p.req_begin; q <= p.req_end; ++q) {
+                    const Request &r = reqs[g.second[q]];
+                    segs.push_back(TopkSeg{r.in, r.out, residual_(r), r.n, r.prescale, r.postscale, r.op});
+                }
+                const int P = data_->size();
+                topk_.run(segs.data(), (int)segs.size(), P, data_->rank(), config().wire_topk_ppm.load(), stream_,
+                          [&](const void *send, void *recv, size_t per) {
+                              std::vector<size_t> cnt((size_t)P, per), dsp((size_t)P);
+                              for (int q = 0; q < P; ++q) dsp[(size_t)q] = (size_t)q * per;
+                              data_->allgatherv(send, recv, cnt.data(), dsp.data(), DDL_FLOAT, stream_);
+                          });
             } else if (host) {
                 // memcpy in -> MPI_Allreduce -> memcpy out (MPIRingTokenCommunication.cc:548-733),
                 // the allreduce on the device through pinned chunks

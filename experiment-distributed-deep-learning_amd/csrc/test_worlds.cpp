@@ -299,6 +299,22 @@ void ThreadWorld::adasum(const AdasumSeg *segs, int count, size_t threshold, hip
     });
 }
 
+void ThreadWorld::topk(const TopkSeg *segs, int count, size_t threshold, long long ppm, hipStream_t user) {
+    while (topks_.size() < (size_t)P_) topks_.emplace_back(new TopkPipe);
+    std::vector<size_t> elems;
+    for (int i = 0; i < count; ++i) elems.push_back(segs[i].n);
+    const auto plans = adasum_plans(elems, threshold);
+    run_(user, [&](int r, hipStream_t s) {
+        for (const auto &p : plans)
+            topks_[r]->run(segs + (size_t)r * count + p.first, (int)(p.second - p.first), P_, r, ppm, s,
+                           [&](const void *send, void *recv, size_t per) {
+                               std::vector<size_t> cnt((size_t)P_, per), dsp((size_t)P_);
+                               for (int q = 0; q < P_; ++q) dsp[(size_t)q] = (size_t)q * per;
+                               ex_[r]->allgatherv(send, recv, cnt.data(), dsp.data(), DDL_FLOAT, s);
+                           });
+    });
+}
+
 size_t ThreadWorld::fused_allreduce(const PlanSeg *segs, int count, int dtype, int src_dtype, size_t cap,
                                     hipStream_t user, const RingConfig &cfg, double *sumsq_out,
                                     std::vector<std::pair<size_t, size_t>> *cuts) {

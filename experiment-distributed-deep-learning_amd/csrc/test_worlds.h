@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "adasum.h"
+#include "topk.h"
 #include "engine.h"
 #include "executor.h"
 
@@ -186,6 +187,9 @@ public:
     // under `threshold` bytes, AdasumPipe::run per plan), each plan's allgatherv through the rank's
     // RingExecutor. segs[r * count + i]: rank r's tensor i; the element counts are rank 0's on every rank.
     void adasum(const AdasumSeg *segs, int count, size_t threshold, hipStream_t user);
+    // The keyed path's top-k group on every rank (adasum_plans' whole-request plans, TopkPipe::run per plan at
+    // density `ppm`), laid out as adasum's; the residuals are the caller's.
+    void topk(const TopkSeg *segs, int count, size_t threshold, long long ppm, hipStream_t user);
 
 private:
     void run_(hipStream_t user, const std::function<void(int, hipStream_t)> &body);
@@ -194,6 +198,7 @@ private:
     std::vector<std::unique_ptr<RingExecutor>> ex_;
     std::vector<std::unique_ptr<FusionPipe>> pipes_;  // one per rank (fused_allreduce)
     std::vector<std::unique_ptr<AdasumPipe>> adasums_;  // one per rank (adasum; packs with pipes_[r]'s copier)
+    std::vector<std::unique_ptr<TopkPipe>> topks_;      // one per rank (topk)
     std::vector<hipStream_t> streams_;
     std::vector<hipEvent_t> done_;
     hipEvent_t fork_ = nullptr;

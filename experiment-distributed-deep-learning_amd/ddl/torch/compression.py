@@ -73,6 +73,19 @@ against the plain pack's 0.66 on the C5 gradient set, 2.42 times, and 1.05 times
 reset: as for the 16-bit kinds — `reset_error_feedback()` after loading a checkpoint or a large change of the loss
 scale (unless prescale = 1 / loss scale keeps the residual in the true gradient's units). A name that moves between
 `fp8_feedback` and a 16-bit `_feedback` kind restarts from zero by itself.
+
+Sparsification: `Compression.topk` (include/ddl_amd.h, DDL_ALLREDUCE_WIRE_TOPK; Deep Gradient Compression, EF-SGD,
+GRACE's topk) for when the link is the bottleneck and a quarter of the bytes is not enough. Every rank adds what it
+has not sent yet under a name to that name's tensor, sends the entries of largest magnitude as (index, value) pairs —
+1 % of them by default (`set_topk_density`), 8 bytes each, so about 50 times fewer bytes than fp32 — and keeps the
+rest for later. The result is the dense fp32 sum (or mean) of what was sent, +0.0 where nobody sent anything, the
+same bits on every rank. The selection is exact and deterministic (ties go to the lower index); values travel as
+fp32, so range and precision are not the issue here, delay is: a small entry waits until it has accumulated its
+way into the top. The cost: one fp32 copy of each gradient in device memory, kept per request NAME (stable names
+only: allreduce_gradient refuses it), P slots of 8 bytes per sent entry in a gather buffer, and about four reads
+and one write of the residual per element in the selection (csrc/topk.hip). No `sumsq` (ValueError; so none of the
+wrapper's norm tracking), SUM and AVG only, fp32 only — any other tensor of a call is submitted uncompressed.
+`reset_error_feedback()` restarts these residuals too.
 """
 import torch
 
@@ -88,7 +101,7 @@ class _Wire:
 
     @property
     def feedback(self) -> bool:
-        return bool(self.flag & (cb.WIRE_FEEDBACK | cb.WIRE_E4M3_FEEDBACK))
+        return bool(self.flag & (cb.WIRE_FEEDBACK | cb.WIRE_E4M3_FEEDBACK | cb.WIRE_TOPK))  # a residual per name
 
     @property
     def stochastic(self) -> bool:
@@ -121,6 +134,7 @@ class Compression:
     fp8 = _Wire('fp8', cb.WIRE_E4M3)
     fp8_feedback = _Wire('fp8_feedback', cb.WIRE_E4M3 | cb.WIRE_E4M3_FEEDBACK)
     fp8_all = _Wire('fp8_all', cb.WIRE_E4M3, (torch.float32, torch.bfloat16))
+    topk = _Wire('topk', cb.WIRE_TOPK)
 
 
 def wire_flag(compression) -> int:
@@ -129,7 +143,7 @@ def wire_flag(compression) -> int:
         return 0
     if not isinstance(compression, _Wire):
         raise TypeError('compression must be Compression.none, .fp16, .bf16, .fp16_feedback, .bf16_feedback, '
-                        f'.bf16_stochastic, .fp8, .fp8_feedback or .fp8_all, not {compression!r}')
+                        f'.bf16_stochastic, .fp8, .fp8_feedback, .fp8_all or .topk, not {compression!r}')
     return compression.flag
 
 
@@ -147,6 +161,17 @@ def reset_error_feedback() -> None:
     lib = cb.CPPBackend.c_api()
     cb.check(lib.ddl_set_config(b'wire_feedback_epoch', int(lib.ddl_get_config(b'wire_feedback_epoch')) + 1),
              'ddl_set_config(wire_feedback_epoch)')
+
+
+def set_topk_density(fraction: float) -> None:
+    """Set the share of each tensor's entries `Compression.topk` sends (the engine's SHARED `wire_topk_ppm`,
+    parts per million, default 0.01 = 10 000 ppm; 1e-6 <= fraction <= 1, else ValueError). Shared: it sizes what
+    the ranks exchange, so set it alike on every rank between the same two collectives — a mismatch fails the
+    round with CONFIG_MISMATCH, never a hang."""
+    ppm = round(float(fraction) * 1e6)
+    if not 1 <= ppm <= 1000000:
+        raise ValueError(f'set_topk_density: a fraction in [1e-6, 1], not {fraction!r}')
+    cb.check(cb.CPPBackend.c_api().ddl_set_config(b'wire_topk_ppm', ppm), 'ddl_set_config(wire_topk_ppm)')
 
 
 def set_stochastic_seed(seed: int) -> None:

@@ -47,6 +47,7 @@ WIRE_FEEDBACK = 0x1000  # error feedback: only together with exactly one of the 
 WIRE_STOCHASTIC = 0x8000  # stochastic rounding: only together with WIRE_BF16, never with WIRE_FEEDBACK
 WIRE_E4M3 = 0x20000  # enum ddl_allreduce_wire8: block-scaled e4m3fn granules; no other wire bit with it
 WIRE_E4M3_FEEDBACK = 0x40000  # enum ddl_allreduce_wire8_feedback: error feedback of the e4m3 pack; only with WIRE_E4M3
+WIRE_TOPK = 0x80000  # enum ddl_allreduce_wire_sparse: top-k (index, value) pairs with error feedback; no other wire bit, no SUMSQ
 SUMSQ = 0x2000  # enum ddl_allreduce_stat: `user` points to a SumsqArg (struct ddl_sumsq_arg)
 SCALE = 0x4000  # enum ddl_allreduce_scale: `user` points to a ScaleArg (struct ddl_scale_arg)
 MEMORY_DEVICE, MEMORY_HOST = 0, 1  # enum ddl_memory
@@ -172,6 +173,8 @@ class CPPBackend:
             ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(ci), ci, fp, fp, vp, ctypes.POINTER(sz), ub, dp,
             ctypes.POINTER(sz), ctypes.POINTER(sz), ci, ctypes.POINTER(ci))
         sig('ddl_testing_thread_adasum', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(sz), fp, fp, vp)
+        sig('ddl_testing_thread_topk', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
+            ctypes.POINTER(sz), fp, fp, ci, vp)
         # (testing library: the same for native bfloat16 tensors)
         sig('ddl_pack_scale_dtype', ci, vp, ctypes.POINTER(vp), ctypes.POINTER(sz), ci, ci, fp, vp)
         sig('ddl_unpack_scale_dtype', ci, ctypes.POINTER(vp), vp, ctypes.POINTER(sz), ctypes.POINTER(ci), ci, ci, ci, fp,

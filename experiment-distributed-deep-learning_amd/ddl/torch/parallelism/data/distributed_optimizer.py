@@ -70,6 +70,12 @@ bytes per element instead of 5; the requantization of the sum is not compensated
 with everything `Compression.fp8` composes with, the residuals being in prescaled units, and
 `ddl.torch.compression.reset_error_feedback()` restarts it as it restarts the 16-bit kinds.
 
+`compression=Compression.topk`: every rank sends the largest-magnitude 1 % (`set_topk_density`) of each dense fp32
+device gradient plus what it has not sent yet, and keeps the rest under the gradient's stable name
+(ddl.torch.compression: about 50 times fewer bytes than fp32, one fp32 copy of every gradient in device memory).
+On both paths, with `fused_mean`, `gradient_predivide_factor` and a fixed `loss_scale`; with `track_grad_norm`,
+`max_grad_norm` or `skip_nonfinite` it is a ValueError (the engine takes no sum of squares over this wire).
+
 `track_grad_norm=True` (implied by `max_grad_norm` and `skip_nonfinite`): after
 `allreduce_gradients()`, `optimizer.grad_norm` is the global L2 norm of the averaged gradients (a
 float) and `optimizer.found_nonfinite` is `not math.isfinite(grad_norm)`. Every dense fp32 or bf16 device
@@ -468,7 +474,10 @@ def data_parallelism_distributed_optimizer_wrapper(
                        or skip_nonfinite):
         raise ValueError('adasum does not compose with fused_mean, compression, track_grad_norm, max_grad_norm '
                          'or skip_nonfinite')
-    wire_flag(compression)  # a TypeError here, not at the first step
+    if wire_flag(compression) & cb.WIRE_TOPK and (track_grad_norm or max_grad_norm is not None or skip_nonfinite):
+        # (wire_flag: a TypeError here, not at the first step) the norm would be of the sparse sums
+        raise ValueError('Compression.topk does not compose with track_grad_norm, max_grad_norm or skip_nonfinite: '
+                         'the engine takes no sum of squares over the top-k wire')
     res.compression = Compression.none if compression is None else compression
     res.track_grad_norm = bool(track_grad_norm)
     res.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)

@@ -36,10 +36,13 @@ def _comm(communicator):
     return Communicator.world() if communicator is None else communicator
 
 
-def _check_op_compression(op, compression) -> None:
-    """MIN / MAX never travel over a 16-bit wire: refused here, before any library call."""
+def _check_op_compression(op, compression, sumsq=False) -> None:
+    """MIN / MAX never travel over a 16-bit wire, and Compression.topk takes no sumsq (the engine refuses
+    DDL_ALLREDUCE_SUMSQ with DDL_ALLREDUCE_WIRE_TOPK): refused here, before any library call."""
     if int(op) in (cb.OP_MIN, cb.OP_MAX) and wire_flag(compression):
         raise ValueError(f'op {int(op)} (MIN / MAX) takes no compression, got {compression!r}')
+    if sumsq and wire_flag(compression) & cb.WIRE_TOPK:
+        raise ValueError(f'{compression!r} takes no sumsq')
 
 
 def _allreduce_device(src: torch.Tensor, dst: torch.Tensor, communicator: Communicator,
@@ -131,7 +134,7 @@ def allreduce_gradient(tensor: torch.Tensor, communicator: Communicator = None,
         return allreduce_async(tensor, name, communicator, op=cb.OP_ADASUM).wait()
     if op is not None:
         raise ValueError(f'allreduce_gradient takes op=cb.OP_ADASUM or none, not {op!r}')
-    if wire_flag(compression) & (cb.WIRE_FEEDBACK | cb.WIRE_E4M3_FEEDBACK):
+    if wire_flag(compression) & (cb.WIRE_FEEDBACK | cb.WIRE_E4M3_FEEDBACK | cb.WIRE_TOPK):  # (Compression.topk keeps one too)
         raise ValueError(f'allreduce_gradient does not take {compression!r}: its compressed requests get a fresh '
                          'name per call, which would leak one error-feedback residual per call; use allreduce_async '
                          'with a stable name')
@@ -574,7 +577,7 @@ def allreduce_async(tensor: torch.Tensor, name: str, communicator: Communicator 
     Device tensors stay in HBM; host (CPU) tensors — the reference's only kind, its op is
     DEVICE_CPU (AllreduceOp.cc:68) — are fused through pinned staging to the GPU and back.
     """
-    _check_op_compression(op, compression)
+    _check_op_compression(op, compression, sumsq)
     if int(op) == cb.OP_ADASUM:
         _check_adasum((tensor,) if output is None else (tensor, output), compression, sumsq, 'allreduce_async')
     if sumsq:
@@ -645,6 +648,7 @@ def allreduce_async_batch(tensors, names, communicator: Communicator = None, out
     wanted = [bool(sumsq)] * len(tensors) if isinstance(sumsq, (bool, int)) else [bool(w) for w in sumsq]
     if len(wanted) != len(tensors):
         raise ValueError('sumsq: one flag per tensor')
+    _check_op_compression(op, compression, any(wanted))
     if int(op) == cb.OP_ADASUM:
         _check_adasum(tensors + ([] if outputs is None else list(outputs)), compression, any(wanted),
                       'allreduce_async_batch')

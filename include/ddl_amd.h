@@ -103,6 +103,12 @@ enum ddl_allreduce_wire8 { DDL_ALLREDUCE_WIRE_E4M3 = 0x20000 };
  * the same `op`, valid only OR-ed with DDL_ALLREDUCE_WIRE_E4M3. A bit of its own, not DDL_ALLREDUCE_WIRE_FEEDBACK
  * (which stays refused with WIRE_E4M3): another rule — per granule, no overflow case, another byte cost. */
 enum ddl_allreduce_wire8_feedback { DDL_ALLREDUCE_WIRE_E4M3_FEEDBACK = 0x40000 };
+/* The top-k sparsified wire with error feedback (MI355X extension; Deep Gradient Compression, GRACE's topk; "The
+ * top-k wire" in the data-plane section): every rank sends the entries of largest magnitude of (gradient + what it
+ * has not sent yet) as (index, value) pairs and keeps the rest. OR-ed into the `op` (SUM or AVG) of the keyed entry
+ * points for DDL_FLOAT device requests, optionally with DDL_ALLREDUCE_SCALE; never with any other wire, feedback
+ * or stochastic flag, and never with DDL_ALLREDUCE_SUMSQ. */
+enum ddl_allreduce_wire_sparse { DDL_ALLREDUCE_WIRE_TOPK = 0x80000 };
 /* Sum of squares of a keyed device allreduce of DDL_FLOAT or DDL_BFLOAT16 tensors (MI355X extension; the data-plane
  * section): OR-ed into the `op` of ddl_allreduce_submit / _submit_batch (and _submit_mem /
  * _submit_batch_mem with DDL_MEMORY_DEVICE), SUM or AVG, with or without a wire flag. With the bit
@@ -222,7 +228,8 @@ int ddl_is_initialized(void);
  * after loading a checkpoint or after a change of the loss scale by a large factor),
  * "wire_stochastic_seed" (0, default; per process: the seed of the random bits of
  * DDL_ALLREDUCE_WIRE_STOCHASTIC, the data-plane section; its 64 bits are read when a request is packed;
- * rank-local like "wire_feedback_epoch", not a shared tunable), "pipeline_rounds" (1,
+ * rank-local like "wire_feedback_epoch", not a shared tunable), "wire_topk_ppm" (10000, default; shared: the
+ * density of DDL_ALLREDUCE_WIRE_TOPK in parts per million, 1 .. 1000000), "pipeline_rounds" (1,
  * default: a completion thread fires a keyed round's done() calls as its plans land while the
  * engine thread negotiates the next round; 0: each round is waited for first), "reference_order" (1,
  * default: every allreduce sum equals the reference's MPI_Allreduce — MPICH 3.3.2 — bit for
@@ -233,7 +240,7 @@ int ddl_is_initialized(void);
  * slice size) per bucket-size class (floor(log2 bytes)) the first time it sees that class: a
  * collective timing of a fixed candidate list on scratch buffers, max over ranks, argmin.
  * The shared tunables (algo, slice_bytes, rings, max_slices, fusion_threshold_bytes, tune,
- * fusion_pipeline_bytes, reference_order, host_chunk_bytes, rccl_min_ctas, rccl_max_ctas) must
+ * fusion_pipeline_bytes, reference_order, host_chunk_bytes, rccl_min_ctas, rccl_max_ctas, wire_topk_ppm) must
  * be equal on every rank of a
  * communicator. Direct collectives: the ranks exchange a hash of them at a communicator's first
  * collective and at the next collective after this rank's values changed; a mismatch found there
@@ -499,6 +506,37 @@ void py_error(const char *log_str);
  * DDL_STATUS_INVALID_ARGUMENT; a dtype other than DDL_FLOAT DDL_STATUS_UNSUPPORTED_DTYPE.
  * P = 1: with "one_rank_shortcut" 1 nothing is touched and no residual is made; with 0 the data plane runs and
  * the rule applies.
+ *
+ * The top-k wire: DDL_ALLREDUCE_WIRE_TOPK = 0x80000, OR-ed into op SUM or AVG (optionally with
+ * DDL_ALLREDUCE_SCALE) on the keyed entry points, DDL_FLOAT device tensors. The density is the SHARED config
+ * "wire_topk_ppm" (1 .. 1000000 parts per million, default 10000 = 1 %; it sizes what the ranks exchange, so a
+ * mismatch fails the round with DDL_STATUS_CONFIG_MISMATCH): a request of n elements sends
+ *     k = min(n, max(1, ceil(n ppm / 10^6)))
+ * entries of 8 bytes, at 1 % about 50 times fewer bytes than fp32. r is the rank's residual for the key (fp32, n
+ * elements, zero the first time). All arithmetic is fp32, round to nearest even, never contracted. On each rank:
+ *     a      = fl32(g (x) prescale) (+) r                (g itself without a prescale)
+ *     key(a) = bits(a) & 0x7fffffff                      the magnitude as an integer: a NaN sorts above inf
+ *     S      = the k elements of largest key; ties at the threshold key are taken in ascending index
+ *     sent   = (i, a_i) for i in S, in ascending i
+ *     r'     = +0.0 on S, a elsewhere
+ * and on every rank out[i] = post(sum of a^q[i] over the ranks q = 0 .. P - 1 that selected i, in rank order, in
+ * fp32, starting from +0.0): AVG's correctly rounded quotient by (float)P, then the postscale, as the unpack
+ * composes them. An element nobody selected is +0.0. Every rank stores the same bits, run after run: the
+ * selection is an exact radix select whose only atomics are integer counts, the combine has none
+ * (csrc/topk.hip). tests/_topk_helpers.py restates the rule in NumPy, bit for bit.
+ * Requests with the flag form fusion groups of their own, after Adasum's. A tensor is never cut: a plan holds
+ * whole requests, a request above "fusion_threshold_bytes" is a plan of its own, nothing is pipelined. Each plan
+ * is ONE allgatherv of the rank's slot — per tensor the tiles' first positions (one uint32 per 2048 elements),
+ * k uint32 indices and k fp32 values — so a rank receives (P - 1) x 8 k bytes, and the gather buffer holds P slots.
+ * The residual has the lifetime and the restarts of the other wires' (kept by the communicator, restarted from
+ * zero on another element count, on another "wire_feedback_epoch" and when the key comes back from another
+ * family of wire): EVERY DISTINCT KEY THAT EVER CARRIED THE FLAG HOLDS 4 BYTES PER ELEMENT, never use it with
+ * fresh key names per step. It is in prescaled units.
+ * Refusals, before anything is registered (the communicator works afterwards): any other wire, feedback or
+ * stochastic flag, DDL_ALLREDUCE_SUMSQ, MIN, MAX or ADASUM, DDL_MEMORY_HOST, a tensor of 2^31 or more elements
+ * return DDL_STATUS_INVALID_ARGUMENT, a dtype other than DDL_FLOAT DDL_STATUS_UNSUPPORTED_DTYPE as for the other
+ * wires; the unkeyed entry points refuse the flag as an unknown op. P = 1: with "one_rank_shortcut" 1 nothing is
+ * selected and no residual is made (the scaled input comes back); with 0 the data plane runs and the rule applies.
  *
  * MIN / MAX: DDL_ALLREDUCE_OP_MIN = 3 and DDL_ALLREDUCE_OP_MAX = 4, on every dtype and every
  * allreduce entry point. Per element over the P inputs: DDL_INT32 / DDL_INT64 in signed order,
