@@ -406,6 +406,7 @@ int ddl_allreduce_submit_mem(ddl_communicator_id id, const char *key, const void
         r.dtype = dtype;
         r.host = memory == DDL_MEMORY_HOST;
         r.topk = take_topk(&op, dtype, r.host, elements);
+        r.sign = take_sign(&op, dtype, r.host, c->size());
         take_sumsq(&op, &user, &r.sumsq, &r.prescale, &r.postscale);
         r.wire = decode_keyed_op(op, dtype, r.host, &r.op, &r.feedback, &r.stochastic);  // refusals before anything is posted
         check_wire_ranks(r.wire, c->size());
@@ -507,6 +508,7 @@ int ddl_allreduce_submit_batch_mem(ddl_communicator_id id, int count, const char
             int opi = op;
             rs[i].user = users ? users[i] : nullptr;
             rs[i].topk = take_topk(&opi, dtypes[i], rs[i].host, elements[i]);
+            rs[i].sign = take_sign(&opi, dtypes[i], rs[i].host, c->size());
             take_sumsq(&opi, &rs[i].user, &rs[i].sumsq, &rs[i].prescale, &rs[i].postscale);  // (sumsq entries may be NULL)
             rs[i].wire = decode_keyed_op(opi, dtypes[i], rs[i].host, &rs[i].op, &rs[i].feedback, &rs[i].stochastic);
             check_wire_ranks(rs[i].wire, c->size());

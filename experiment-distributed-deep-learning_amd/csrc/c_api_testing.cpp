@@ -1101,6 +1101,23 @@ int ddl_testing_thread_topk(int nranks, int count, const void *const *srcs, void
     });
 }
 
+int ddl_testing_thread_sign(int nranks, int count, const void *const *srcs, void *const *dsts, void *const *residuals,
+                            const size_t *elements, const float *prescale, const float *postscale, int op,
+                            void *hip_stream) {
+    return guarded([&] {
+        DDL_REQUIRE(nranks >= 1 && count >= 1 && srcs && dsts && residuals && elements, DDL_STATUS_INVALID_ARGUMENT,
+                    "bad thread sign");
+        check_sign_ranks(nranks);
+        check_factors(prescale, postscale, nranks * count);
+        std::vector<SignSeg> segs;
+        for (int k = 0; k < nranks * count; ++k)
+            segs.push_back(SignSeg{srcs[k], dsts[k], residuals[k], elements[k % count], prescale ? prescale[k] : 1.0f,
+                                   postscale ? postscale[k] : 1.0f, op});
+        thread_world(nranks).sign(segs.data(), count, (size_t)config().fusion_threshold_bytes.load(),
+                                  as_stream(hip_stream));
+    });
+}
+
 int ddl_testing_thread_fused_allreduce_native(int nranks, int count, const void *const *srcs, void *const *dsts,
                                               const size_t *elements, const int *ops, int dtype, const float *prescale,
                                               const float *postscale, void *hip_stream, size_t *subplans,

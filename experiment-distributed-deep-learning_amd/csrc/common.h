@@ -140,6 +140,28 @@ inline bool take_topk(int *op, int dtype, bool host, size_t n) {
     return true;
 }
 
+// DDL_ALLREDUCE_WIRE_SIGN (sign.h): keyed float32 device requests with op SUM or AVG and no other wire, feedback
+// or stochastic bit, on at most 16 ranks (the wire is gathered: beyond that it moves more than the e4m3 wire); no
+// DDL_ALLREDUCE_SUMSQ. take_sign: as take_topk, with top-k's statuses.
+constexpr int kSignMaxRanks = 16;
+inline void check_sign_ranks(int size) {
+    DDL_REQUIRE(size <= kSignMaxRanks, DDL_STATUS_INVALID_ARGUMENT,
+                "DDL_ALLREDUCE_WIRE_SIGN takes a communicator of at most 16 ranks, not " << size);
+}
+inline bool take_sign(int *op, int dtype, bool host, int size) {
+    if (!(*op & DDL_ALLREDUCE_WIRE_SIGN)) return false;
+    DDL_REQUIRE(!(*op & DDL_ALLREDUCE_SUMSQ), DDL_STATUS_INVALID_ARGUMENT, "WIRE_SIGN takes no DDL_ALLREDUCE_SUMSQ");
+    const int base = *op & ~(DDL_ALLREDUCE_WIRE_SIGN | DDL_ALLREDUCE_SCALE);
+    DDL_REQUIRE(base == DDL_ALLREDUCE_OP_SUM || base == DDL_ALLREDUCE_OP_AVG, DDL_STATUS_INVALID_ARGUMENT,
+                "WIRE_SIGN takes SUM or AVG and no other wire, feedback or stochastic flag (allreduce op " << *op << ")");
+    DDL_REQUIRE(!host, DDL_STATUS_INVALID_ARGUMENT, "wire compression is for device requests only");
+    check_sign_ranks(size);
+    DDL_REQUIRE(dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
+                "WIRE_SIGN is defined for float32 only, not " << dtype_name(dtype));
+    *op &= ~DDL_ALLREDUCE_WIRE_SIGN;
+    return true;
+}
+
 // The `op` of a keyed allreduce request: SUM / AVG / MIN / MAX in the low bits, with SUM / AVG
 // optionally one ddl_allreduce_wire format flag, optionally DDL_ALLREDUCE_WIRE_FEEDBACK with it, or
 // DDL_ALLREDUCE_WIRE_STOCHASTIC with WIRE_BF16; or DDL_ALLREDUCE_WIRE_E4M3 alone (kDtypeE4m3), optionally with

@@ -142,6 +142,12 @@ void validate(const Request &r, int size) {
                             DDL_STATUS_INVALID_ARGUMENT, "the top-k wire takes a float32 device SUM or AVG request and no other flag");
                 check_topk_elements(r.n);
             }
+            if (r.sign) {  // what take_sign lets through
+                DDL_REQUIRE(r.dtype == DDL_FLOAT && !r.host && r.wire == 0 && !r.feedback && !r.stochastic && !r.sumsq &&
+                                !r.topk && (r.op == DDL_ALLREDUCE_OP_SUM || r.op == DDL_ALLREDUCE_OP_AVG),
+                            DDL_STATUS_INVALID_ARGUMENT, "the sign wire takes a float32 device SUM or AVG request and no other flag");
+                check_sign_ranks(size);
+            }
             DDL_REQUIRE(r.wire != kDtypeE4m3 || !op_is_minmax(r.op), DDL_STATUS_INVALID_ARGUMENT,
                         "the e4m3 wire takes SUM or AVG");
             DDL_REQUIRE(!r.feedback || r.wire != 0, DDL_STATUS_INVALID_ARGUMENT, "error feedback without a wire dtype");
@@ -523,10 +529,10 @@ std::vector<int> plan_ops(const Plan &p, const std::vector<Request> &reqs, const
 // Engine thread only. hipMalloc does not wait for the device (profiles/r06/s17); the zeroing is
 // posted on stream_, so it runs after every earlier pack of this key and before the next one. A
 // residual of another element count is retired, not freed: its last pack may still be running. A key that
-// comes back under another family of wire (the 16-bit wires, e4m3, top-k) restarts from zero.
+// comes back under another family of wire (the 16-bit wires, e4m3, top-k, sign) restarts from zero.
 void *RequestHandler::residual_(const Request &r) {
     const long long epoch = config().wire_feedback_epoch.load();
-    const int family = r.topk ? kFamilyTopk : r.wire == kDtypeE4m3 ? kFamilyE4m3 : kFamily16;
+    const int family = r.sign ? kFamilySign : r.topk ? kFamilyTopk : r.wire == kDtypeE4m3 ? kFamilyE4m3 : kFamily16;
     Residual &res = residuals_[r.key];
     if (res.ptr && res.n == r.n && res.epoch == epoch && res.family == family) return res.ptr;
     res.family = family;
@@ -628,10 +634,12 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
     // Adasum (adasum.h) is a fourth kind, after MAX: its plans hold whole requests and run gather -> Gram ->
     // coefficients -> apply instead of an allreduce. The top-k wire (topk.h) is a fifth, after Adasum: whole
     // requests too, select -> emit -> gather -> combine (SUM and AVG share it: the quotient is rank-local).
-    // Where the one-rank shortcut skips the data plane nothing is selected: those requests are plain SUM / AVG ones.
+    // The sign wire (sign.h) is a sixth, after top-k: whole requests, pack -> gather -> combine.
+    // Where the one-rank shortcut skips the data plane nothing is selected or packed: those requests are plain
+    // SUM / AVG ones.
     const bool shortcut = data_->size() == 1 && config().one_rank_shortcut.load();
     auto kind_rank = [shortcut](const Request &r) {
-        return r.topk && !shortcut ? 4 : r.op == DDL_ALLREDUCE_OP_MIN ? 1 : r.op == DDL_ALLREDUCE_OP_MAX ? 2 : r.op == DDL_ALLREDUCE_OP_ADASUM ? 3 : 0;
+        return r.sign && !shortcut ? 5 : r.topk && !shortcut ? 4 : r.op == DDL_ALLREDUCE_OP_MIN ? 1 : r.op == DDL_ALLREDUCE_OP_MAX ? 2 : r.op == DDL_ALLREDUCE_OP_ADASUM ? 3 : 0;
     };
     std::map<std::tuple<int, int, int, int, int>, std::vector<size_t>> groups;
     for (size_t i = 0; i < reqs.size(); ++i) {
@@ -669,9 +677,11 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
         const bool fused = !host && !(data_->size() == 1 && config().one_rank_shortcut.load()), wire_opts = comp && fused;
         const bool adasum = std::get<3>(g.first) == 3;  // (its plans take AdasumSegs, not these)
         const bool topk = std::get<3>(g.first) == 4;    // (TopkSegs; always fused)
+        const bool sign = std::get<3>(g.first) == 5;    // (SignSegs; always fused)
+        const bool entire = adasum || topk || sign;     // plans of whole requests, run by a pipe of their own
         std::vector<PlanSeg> whole;
-        whole.reserve(fused && !adasum && !topk ? g.second.size() : 0);
-        for (size_t q = 0; fused && !adasum && !topk && q < g.second.size(); ++q) {
+        whole.reserve(fused && !entire ? g.second.size() : 0);
+        for (size_t q = 0; fused && !entire && q < g.second.size(); ++q) {
             const Request &r = reqs[g.second[q]];
             whole.push_back(PlanSeg{r.in, r.out, plan_units(r) * es, r.op, r.prescale, r.postscale});
             whole.back().want = r.sumsq != nullptr;
@@ -681,7 +691,7 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
         }
         const size_t threshold = (size_t)config().fusion_threshold_bytes.load();
         std::vector<Plan> plans;
-        if (adasum || topk)  // whole requests only: the Gram matrix, the selection, is of the whole tensor
+        if (entire)  // whole requests only: the Gram matrix, the selection, is of the whole tensor (the sign wire: its blocks)
             for (const auto &w : adasum_plans(elems, threshold)) plans.push_back(Plan{w.first, 0, w.second - 1, elems[w.second - 1]});
         else plans = make_plans(elems, esz, threshold);
         for (const Plan &p : plans) {
@@ -712,6 +722,21 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
                 }
                 const int P = data_->size();
                 topk_.run(segs.data(), (int)segs.size(), P, data_->rank(), config().wire_topk_ppm.load(), stream_,
+                          [&](const void *send, void *recv, size_t per) {
+                              std::vector<size_t> cnt((size_t)P, per), dsp((size_t)P);
+                              for (int q = 0; q < P; ++q) dsp[(size_t)q] = (size_t)q * per;
+                              data_->allgatherv(send, recv, cnt.data(), dsp.data(), DDL_FLOAT, stream_);
+                          });
+            } else if (sign) {
+                // a + residual packed into this rank's slot as block scales and sign words (the residual keeps
+                // what that removed), one allgatherv of the slot, then the combine writes every request's output
+                std::vector<SignSeg> segs;
+                for (size_t q = p.req_begin; q <= p.req_end; ++q) {
+                    const Request &r = reqs[g.second[q]];
+                    segs.push_back(SignSeg{r.in, r.out, residual_(r), r.n, r.prescale, r.postscale, r.op});
+                }
+                const int P = data_->size();
+                sign_.run(segs.data(), (int)segs.size(), P, data_->rank(), stream_,
                           [&](const void *send, void *recv, size_t per) {
                               std::vector<size_t> cnt((size_t)P, per), dsp((size_t)P);
                               for (int q = 0; q < P; ++q) dsp[(size_t)q] = (size_t)q * per;

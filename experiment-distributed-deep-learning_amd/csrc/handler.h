@@ -33,6 +33,7 @@
 
 #include "adasum.h"
 #include "topk.h"
+#include "sign.h"
 #include "engine.h"
 #include "fusion.h"
 #include "host_stage.h"
@@ -61,6 +62,7 @@ struct Request {
     bool feedback = false;            // allreduce: DDL_ALLREDUCE_WIRE_FEEDBACK, or with the e4m3 `wire` _E4M3_FEEDBACK (rank-local)
     bool stochastic = false;          // allreduce: DDL_ALLREDUCE_WIRE_STOCHASTIC (only with the bf16 `wire`; rank-local)
     bool topk = false;                // allreduce: DDL_ALLREDUCE_WIRE_TOPK (fp32 device SUM / AVG; `wire` stays 0: what travels is no dtype)
+    bool sign = false;                // allreduce: DDL_ALLREDUCE_WIRE_SIGN (fp32 device SUM / AVG; `wire` stays 0, as for top-k)
     double *sumsq = nullptr;          // allreduce: where the sum of squares of `out` goes before done() (host; rank-local)
     // allreduce: DDL_ALLREDUCE_SCALE's factors (1 = absent; fp32 device SUM / AVG requests). Rank-local like
     // the op and `sumsq`: in no group key, plan cut, pipeline cut or negotiation.
@@ -190,6 +192,8 @@ private:
     AdasumPipe adasum_;
     // DDL_ALLREDUCE_WIRE_TOPK plans: select -> emit -> gather -> combine (topk.h)
     TopkPipe topk_;
+    // DDL_ALLREDUCE_WIRE_SIGN plans: pack -> gather -> combine (sign.h)
+    SignPipe sign_;
     // Error feedback (DDL_ALLREDUCE_WIRE_FEEDBACK, DDL_ALLREDUCE_WIRE_E4M3_FEEDBACK): what the wire's rounding removed from this rank's
     // contribution to a key, added back at the key's next request. One fp32 array per key that ever
     // asked for feedback, owned here and freed with the handler (a replaced one is retired, never
@@ -198,9 +202,9 @@ private:
         void *ptr = nullptr;
         size_t n = 0;         // elements
         long long epoch = 0;  // config wire_feedback_epoch when it was last (re)started
-        int family = 0;       // kFamily16 (fp16 and bf16 share it), kFamilyE4m3 or kFamilyTopk: the rule that last wrote it
+        int family = 0;       // kFamily16 (fp16 and bf16 share it), kFamilyE4m3, kFamilyTopk or kFamilySign: the rule that last wrote it
     };
-    static constexpr int kFamily16 = 1, kFamilyE4m3 = 2, kFamilyTopk = 3;
+    static constexpr int kFamily16 = 1, kFamilyE4m3 = 2, kFamilyTopk = 3, kFamilySign = 4;
     std::unordered_map<std::string, Residual> residuals_;
     // the residual of request r for a pack posted on stream_: made, or restarted from zero (another
     // element count, another epoch, the other family of wire), by work posted on stream_ ahead of that pack

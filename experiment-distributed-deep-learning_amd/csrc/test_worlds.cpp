@@ -315,6 +315,22 @@ void ThreadWorld::topk(const TopkSeg *segs, int count, size_t threshold, long lo
     });
 }
 
+void ThreadWorld::sign(const SignSeg *segs, int count, size_t threshold, hipStream_t user) {
+    while (signs_.size() < (size_t)P_) signs_.emplace_back(new SignPipe);
+    std::vector<size_t> elems;
+    for (int i = 0; i < count; ++i) elems.push_back(segs[i].n);
+    const auto plans = adasum_plans(elems, threshold);
+    run_(user, [&](int r, hipStream_t s) {
+        for (const auto &p : plans)
+            signs_[r]->run(segs + (size_t)r * count + p.first, (int)(p.second - p.first), P_, r, s,
+                           [&](const void *send, void *recv, size_t per) {
+                               std::vector<size_t> cnt((size_t)P_, per), dsp((size_t)P_);
+                               for (int q = 0; q < P_; ++q) dsp[(size_t)q] = (size_t)q * per;
+                               ex_[r]->allgatherv(send, recv, cnt.data(), dsp.data(), DDL_FLOAT, s);
+                           });
+    });
+}
+
 size_t ThreadWorld::fused_allreduce(const PlanSeg *segs, int count, int dtype, int src_dtype, size_t cap,
                                     hipStream_t user, const RingConfig &cfg, double *sumsq_out,
                                     std::vector<std::pair<size_t, size_t>> *cuts) {

@@ -16,6 +16,7 @@
 
 #include "adasum.h"
 #include "topk.h"
+#include "sign.h"
 #include "engine.h"
 #include "executor.h"
 
@@ -190,6 +191,9 @@ public:
     // The keyed path's top-k group on every rank (adasum_plans' whole-request plans, TopkPipe::run per plan at
     // density `ppm`), laid out as adasum's; the residuals are the caller's.
     void topk(const TopkSeg *segs, int count, size_t threshold, long long ppm, hipStream_t user);
+    // The keyed path's sign group on every rank (adasum_plans' whole-request plans, SignPipe::run per plan), laid
+    // out as topk's; the residuals are the caller's.
+    void sign(const SignSeg *segs, int count, size_t threshold, hipStream_t user);
 
 private:
     void run_(hipStream_t user, const std::function<void(int, hipStream_t)> &body);
@@ -199,6 +203,7 @@ private:
     std::vector<std::unique_ptr<FusionPipe>> pipes_;  // one per rank (fused_allreduce)
     std::vector<std::unique_ptr<AdasumPipe>> adasums_;  // one per rank (adasum; packs with pipes_[r]'s copier)
     std::vector<std::unique_ptr<TopkPipe>> topks_;      // one per rank (topk)
+    std::vector<std::unique_ptr<SignPipe>> signs_;      // one per rank (sign)
     std::vector<hipStream_t> streams_;
     std::vector<hipEvent_t> done_;
     hipEvent_t fork_ = nullptr;

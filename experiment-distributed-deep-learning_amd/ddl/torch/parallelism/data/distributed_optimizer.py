@@ -76,6 +76,11 @@ device gradient plus what it has not sent yet, and keeps the rest under the grad
 On both paths, with `fused_mean`, `gradient_predivide_factor` and a fixed `loss_scale`; with `track_grad_norm`,
 `max_grad_norm` or `skip_nonfinite` it is a ValueError (the engine takes no sum of squares over this wire).
 
+`compression=Compression.onebit`: every rank sends the sign of every element of each dense fp32 device gradient plus
+its residual, and one magnitude per 2048 elements, and keeps what that removed under the gradient's stable name
+(ddl.torch.compression: 33/256 bytes per element, gathered rather than reduced, at most 16 ranks). It composes and
+refuses as `Compression.topk` does.
+
 `track_grad_norm=True` (implied by `max_grad_norm` and `skip_nonfinite`): after
 `allreduce_gradients()`, `optimizer.grad_norm` is the global L2 norm of the averaged gradients (a
 float) and `optimizer.found_nonfinite` is `not math.isfinite(grad_norm)`. Every dense fp32 or bf16 device
@@ -478,6 +483,9 @@ def data_parallelism_distributed_optimizer_wrapper(
         # (wire_flag: a TypeError here, not at the first step) the norm would be of the sparse sums
         raise ValueError('Compression.topk does not compose with track_grad_norm, max_grad_norm or skip_nonfinite: '
                          'the engine takes no sum of squares over the top-k wire')
+    if wire_flag(compression) & cb.WIRE_SIGN and (track_grad_norm or max_grad_norm is not None or skip_nonfinite):
+        raise ValueError('Compression.onebit does not compose with track_grad_norm, max_grad_norm or skip_nonfinite: '
+                         'the engine takes no sum of squares over the sign wire')
     res.compression = Compression.none if compression is None else compression
     res.track_grad_norm = bool(track_grad_norm)
     res.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)

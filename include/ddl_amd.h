@@ -109,6 +109,12 @@ enum ddl_allreduce_wire8_feedback { DDL_ALLREDUCE_WIRE_E4M3_FEEDBACK = 0x40000 }
  * points for DDL_FLOAT device requests, optionally with DDL_ALLREDUCE_SCALE; never with any other wire, feedback
  * or stochastic flag, and never with DDL_ALLREDUCE_SUMSQ. */
 enum ddl_allreduce_wire_sparse { DDL_ALLREDUCE_WIRE_TOPK = 0x80000 };
+/* The 1-bit sign wire with error feedback (MI355X extension; 1-bit SGD, EF-signSGD, GRACE's efsignsgd / onebit;
+ * "The sign wire" in the data-plane section): every rank sends one sign bit per element and one fp32 magnitude per
+ * block of 2048 elements, and keeps what that removed. OR-ed into the `op` (SUM or AVG) of the keyed entry points
+ * for DDL_FLOAT device requests, optionally with DDL_ALLREDUCE_SCALE; never with any other wire, feedback or
+ * stochastic flag, and never with DDL_ALLREDUCE_SUMSQ. */
+enum ddl_allreduce_wire_sign { DDL_ALLREDUCE_WIRE_SIGN = 0x100000 };
 /* Sum of squares of a keyed device allreduce of DDL_FLOAT or DDL_BFLOAT16 tensors (MI355X extension; the data-plane
  * section): OR-ed into the `op` of ddl_allreduce_submit / _submit_batch (and _submit_mem /
  * _submit_batch_mem with DDL_MEMORY_DEVICE), SUM or AVG, with or without a wire flag. With the bit
@@ -537,6 +543,40 @@ void py_error(const char *log_str);
  * return DDL_STATUS_INVALID_ARGUMENT, a dtype other than DDL_FLOAT DDL_STATUS_UNSUPPORTED_DTYPE as for the other
  * wires; the unkeyed entry points refuse the flag as an unknown op. P = 1: with "one_rank_shortcut" 1 nothing is
  * selected and no residual is made (the scaled input comes back); with 0 the data plane runs and the rule applies.
+ *
+ * The sign wire: DDL_ALLREDUCE_WIRE_SIGN = 0x100000, OR-ed into op SUM or AVG (optionally with
+ * DDL_ALLREDUCE_SCALE) on the keyed entry points, DDL_FLOAT device tensors. A tensor is cut into blocks of 2048
+ * elements; the last block may be short and has c real elements. r is the rank's residual for the key (fp32, n
+ * elements, zero the first time). All arithmetic is fp32, round to nearest even, never contracted. On each rank,
+ * per block:
+ *     a_i  = fl32(g_i (x) prescale) (+) r_i            (g itself without a prescale), as the top-k wire forms it
+ *     t_w  = |a| summed left to right over the 32 elements that word w owns (k = 0 .. 31, below), starting from
+ *            +0.0; an element past n counts as +0.0
+ *     for d in 32, 16, 8, 4, 2, 1: t_w = t_w (+) t_{w xor d}     (64 words; every w ends with the same bits)
+ *     s    = t_0 (/) (float)c                          correctly rounded; if s is not finite, s = 0x7fc00000
+ *     bit k of 32-bit word w (w = 0 .. 63) of the block = the IEEE sign bit of element (k >> 2) * 256 + 4 w + (k & 3);
+ *            0 past n
+ *     r'_i = a_i (-) (sign bit set ? -s : s)           if s is finite; the block's r is LEFT AS IT WAS if it is not
+ * and on every rank each block of out is post(sum over q = 0 .. P - 1, in rank order, starting from +0.0, of
+ * +-s^q) where every rank's s is finite — AVG's correctly rounded quotient by (float)P, then the postscale, as the
+ * top-k combine composes them — and 0x7fc00000 in every element where any rank sent the NaN scale (an explicit
+ * check, not arithmetic). The mean of |a| is the L2-optimal magnitude of a sign code. The method is exactly
+ * compensated: what was sent plus the residuals sums to the true gradients. Unlike the top-k wire every element
+ * moves every step. The bit layout is internal to the engine (csrc/sign.hip: lane w of a wave owns word w) and the
+ * same on every rank. tests/_sign_helpers.py restates the rule in NumPy, bit for bit.
+ * Requests with the flag form fusion groups of their own, after the top-k wire's. A tensor is never cut: a plan
+ * holds whole requests, a request above "fusion_threshold_bytes" is a plan of its own, nothing is pipelined. Each
+ * plan is ONE allgatherv of the rank's slot — per tensor ceil(n / 2048) fp32 scales, then 64 ceil(n / 2048) words:
+ * 33/256 bytes per element. THE WIRE IS GATHERED, NOT REDUCED: a rank receives (P - 1) n 33/256 bytes where a ring
+ * SUM moves about 8 n and the e4m3 wire about 2 n — on 8 ranks about 8 times fewer bytes than fp32 and 2 times
+ * fewer than e4m3, at 16 ranks level with e4m3, hence the limit of 16 ranks. The residual has the lifetime and the
+ * restarts of the other wires' (a family of its own): EVERY DISTINCT KEY THAT EVER CARRIED THE FLAG HOLDS 4 BYTES
+ * PER ELEMENT. It is in prescaled units.
+ * Refusals, before anything is registered (the communicator works afterwards): any other wire, feedback or
+ * stochastic flag, DDL_ALLREDUCE_SUMSQ, MIN, MAX or ADASUM, DDL_MEMORY_HOST and a communicator of more than 16
+ * ranks return DDL_STATUS_INVALID_ARGUMENT, a dtype other than DDL_FLOAT DDL_STATUS_UNSUPPORTED_DTYPE; the unkeyed
+ * entry points refuse the flag as an unknown op. P = 1: with "one_rank_shortcut" 1 nothing is packed and no
+ * residual is made (the scaled input comes back); with 0 the data plane runs and the rule applies.
  *
  * MIN / MAX: DDL_ALLREDUCE_OP_MIN = 3 and DDL_ALLREDUCE_OP_MAX = 4, on every dtype and every
  * allreduce entry point. Per element over the P inputs: DDL_INT32 / DDL_INT64 in signed order,

@@ -328,6 +328,13 @@ int ddl_testing_thread_adasum(int nranks, int count, const void *const *srcs, vo
 int ddl_testing_thread_topk(int nranks, int count, const void *const *srcs, void *const *dsts, void *const *residuals,
                             const size_t *elements, const float *prescale, const float *postscale, int op,
                             void *hip_stream);
+/* A DDL_ALLREDUCE_WIRE_SIGN request group (ddl_amd.h "The sign wire"; csrc/sign.hip) over nranks virtual ranks on
+ * threads, as the keyed handler runs it: whole-request plans under "fusion_threshold_bytes", each plan packed into
+ * the rank's slot, gathered by one allgatherv of the rank's executor, then combined. Arguments as
+ * ddl_testing_thread_topk's. */
+int ddl_testing_thread_sign(int nranks, int count, const void *const *srcs, void *const *dsts, void *const *residuals,
+                            const size_t *elements, const float *prescale, const float *postscale, int op,
+                            void *hip_stream);
 /* The kernels of the e4m3 wire (DDL_ALLREDUCE_WIRE_E4M3; ddl_amd.h "The e4m3 wire"; csrc/pack.hip k_seg<Q8PackOp> /
  * k_seg<Q8UnpackOp>, csrc/reduce_kernels.hip k_foldq). The tensors hold elements[i] fp32 values (4-byte aligned);
  * segment i of the flat buffer is its ceil(elements[i] / 252) granules of 256 bytes at the running sum of the
