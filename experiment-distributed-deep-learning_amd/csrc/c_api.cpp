@@ -158,6 +158,9 @@ int ddl_set_config(const char *key, long long value) {
         else if (k == "wire_topk_ppm") {
             check_topk_ppm(value);
             c.wire_topk_ppm = value;
+        } else if (k == "wire_lowrank_rank") {
+            check_lowrank_rank(value);
+            c.wire_lowrank_rank = value;
         }
         else if (k == "pipeline_rounds") c.pipeline_rounds = value ? 1 : 0;
         else if (k == "reference_order") c.reference_order = value ? 1 : 0;
@@ -226,6 +229,7 @@ long long ddl_get_config(const char *key) {
     if (k == "wire_feedback_epoch") return c.wire_feedback_epoch;
     if (k == "wire_stochastic_seed") return c.wire_stochastic_seed;
     if (k == "wire_topk_ppm") return c.wire_topk_ppm;
+    if (k == "wire_lowrank_rank") return c.wire_lowrank_rank;
     if (k == "pipeline_rounds") return c.pipeline_rounds;
     if (k == "reference_order") return c.reference_order;
     if (k == "capture_mode") return c.capture_mode;
@@ -407,6 +411,7 @@ int ddl_allreduce_submit_mem(ddl_communicator_id id, const char *key, const void
         r.host = memory == DDL_MEMORY_HOST;
         r.topk = take_topk(&op, dtype, r.host, elements);
         r.sign = take_sign(&op, dtype, r.host, c->size());
+        r.lowrank = take_lowrank(&op, dtype, r.host, elements);
         take_sumsq(&op, &user, &r.sumsq, &r.prescale, &r.postscale);
         r.wire = decode_keyed_op(op, dtype, r.host, &r.op, &r.feedback, &r.stochastic);  // refusals before anything is posted
         check_wire_ranks(r.wire, c->size());
@@ -509,6 +514,7 @@ int ddl_allreduce_submit_batch_mem(ddl_communicator_id id, int count, const char
             rs[i].user = users ? users[i] : nullptr;
             rs[i].topk = take_topk(&opi, dtypes[i], rs[i].host, elements[i]);
             rs[i].sign = take_sign(&opi, dtypes[i], rs[i].host, c->size());
+            rs[i].lowrank = take_lowrank(&opi, dtypes[i], rs[i].host, elements[i]);
             take_sumsq(&opi, &rs[i].user, &rs[i].sumsq, &rs[i].prescale, &rs[i].postscale);  // (sumsq entries may be NULL)
             rs[i].wire = decode_keyed_op(opi, dtypes[i], rs[i].host, &rs[i].op, &rs[i].feedback, &rs[i].stochastic);
             check_wire_ranks(rs[i].wire, c->size());

@@ -1118,6 +1118,32 @@ int ddl_testing_thread_sign(int nranks, int count, const void *const *srcs, void
     });
 }
 
+int ddl_testing_lowrank_shape(size_t n, int r, size_t *R, size_t *C, size_t *state_floats) {
+    return guarded([&] {
+        DDL_REQUIRE(n >= 1 && R && C && state_floats, DDL_STATUS_INVALID_ARGUMENT, "bad lowrank shape");
+        check_lowrank_rank(r);
+        check_lowrank_elements(n);
+        const LowrankShape s = lowrank_shape(n, r);
+        *R = s.R, *C = s.C, *state_floats = s.state_floats;
+    });
+}
+
+int ddl_testing_thread_lowrank(int nranks, int count, const void *const *srcs, void *const *dsts, void *const *residuals,
+                               void *const *qstates, const size_t *elements, const float *prescale,
+                               const float *postscale, int op, void *hip_stream) {
+    return guarded([&] {
+        DDL_REQUIRE(nranks >= 1 && count >= 1 && srcs && dsts && residuals && qstates && elements,
+                    DDL_STATUS_INVALID_ARGUMENT, "bad thread lowrank");
+        check_factors(prescale, postscale, nranks * count);
+        std::vector<LowrankSeg> segs;
+        for (int k = 0; k < nranks * count; ++k)
+            segs.push_back(LowrankSeg{srcs[k], dsts[k], residuals[k], qstates[k], elements[k % count],
+                                      prescale ? prescale[k] : 1.0f, postscale ? postscale[k] : 1.0f, op});
+        thread_world(nranks).lowrank(segs.data(), count, (size_t)config().fusion_threshold_bytes.load(),
+                                     (int)config().wire_lowrank_rank.load(), as_stream(hip_stream));
+    });
+}
+
 int ddl_testing_thread_fused_allreduce_native(int nranks, int count, const void *const *srcs, void *const *dsts,
                                               const size_t *elements, const int *ops, int dtype, const float *prescale,
                                               const float *postscale, void *hip_stream, size_t *subplans,

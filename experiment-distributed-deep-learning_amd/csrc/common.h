@@ -162,6 +162,31 @@ inline bool take_sign(int *op, int dtype, bool host, int size) {
     return true;
 }
 
+// DDL_ALLREDUCE_WIRE_LOWRANK (lowrank.h): keyed float32 device requests with op SUM or AVG and no other wire,
+// feedback or stochastic bit, of fewer than 2^31 elements; no DDL_ALLREDUCE_SUMSQ. No rank cap: the wire is
+// reduced, nothing is gathered. take_lowrank: as take_topk, with top-k's statuses. The rank r is the shared
+// config key "wire_lowrank_rank".
+inline void check_lowrank_elements(size_t n) {
+    DDL_REQUIRE(n < (size_t(1) << 31), DDL_STATUS_INVALID_ARGUMENT,
+                "DDL_ALLREDUCE_WIRE_LOWRANK takes tensors of fewer than 2^31 elements, not " << n);
+}
+inline void check_lowrank_rank(long long r) {
+    DDL_REQUIRE(r >= 1 && r <= 16, DDL_STATUS_INVALID_ARGUMENT, "wire_lowrank_rank must be in [1, 16], not " << r);
+}
+inline bool take_lowrank(int *op, int dtype, bool host, size_t n) {
+    if (!(*op & DDL_ALLREDUCE_WIRE_LOWRANK)) return false;
+    DDL_REQUIRE(!(*op & DDL_ALLREDUCE_SUMSQ), DDL_STATUS_INVALID_ARGUMENT, "WIRE_LOWRANK takes no DDL_ALLREDUCE_SUMSQ");
+    const int base = *op & ~(DDL_ALLREDUCE_WIRE_LOWRANK | DDL_ALLREDUCE_SCALE);
+    DDL_REQUIRE(base == DDL_ALLREDUCE_OP_SUM || base == DDL_ALLREDUCE_OP_AVG, DDL_STATUS_INVALID_ARGUMENT,
+                "WIRE_LOWRANK takes SUM or AVG and no other wire, feedback or stochastic flag (allreduce op " << *op << ")");
+    DDL_REQUIRE(!host, DDL_STATUS_INVALID_ARGUMENT, "wire compression is for device requests only");
+    DDL_REQUIRE(dtype == DDL_FLOAT, DDL_STATUS_UNSUPPORTED_DTYPE,
+                "WIRE_LOWRANK is defined for float32 only, not " << dtype_name(dtype));
+    check_lowrank_elements(n);
+    *op &= ~DDL_ALLREDUCE_WIRE_LOWRANK;
+    return true;
+}
+
 // The `op` of a keyed allreduce request: SUM / AVG / MIN / MAX in the low bits, with SUM / AVG
 // optionally one ddl_allreduce_wire format flag, optionally DDL_ALLREDUCE_WIRE_FEEDBACK with it, or
 // DDL_ALLREDUCE_WIRE_STOCHASTIC with WIRE_BF16; or DDL_ALLREDUCE_WIRE_E4M3 alone (kDtypeE4m3), optionally with

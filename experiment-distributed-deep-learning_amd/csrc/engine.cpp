@@ -46,7 +46,7 @@ uint64_t Config::shared_hash() const {
     const long long v[] = {algo.load(), slice_bytes.load(), rings.load(), max_slices.load(),
                            fusion_threshold_bytes.load(), tune.load(), fusion_pipeline_bytes.load(),
                            reference_order.load(), host_chunk_bytes.load(), rccl_min_ctas.load(),
-                           rccl_max_ctas.load(), wire_topk_ppm.load()};
+                           rccl_max_ctas.load(), wire_topk_ppm.load(), wire_lowrank_rank.load()};
     uint64_t h = 1469598103934665603ull;  // FNV-1a over the values' bytes
     for (long long x : v)
         for (int b = 0; b < 8; ++b) {
@@ -219,7 +219,7 @@ void check_config_agreement(int rank, const std::vector<uint64_t> &hashes) {
     if (same) return;
     std::ostringstream os;
     os << "shared tunables differ between ranks (algo, slice_bytes, rings, max_slices, fusion_threshold_bytes, "
-          "tune, fusion_pipeline_bytes, reference_order, host_chunk_bytes, rccl_min_ctas, rccl_max_ctas, wire_topk_ppm "
+          "tune, fusion_pipeline_bytes, reference_order, host_chunk_bytes, rccl_min_ctas, rccl_max_ctas, wire_topk_ppm, wire_lowrank_rank "
           "must be set alike on every rank); "
           "config hash per rank:";
     for (size_t q = 0; q < hashes.size(); ++q)

@@ -112,6 +112,9 @@ struct Config {
     // tensor of n elements sends k = min(n, max(1, ceil(n ppm / 10^6))) entries. Shared (in shared_hash): the
     // ranks' slot sizes, and so the allgatherv they post, depend on it.
     std::atomic<long long> wire_topk_ppm{10000};
+    // the low-rank wire (DDL_ALLREDUCE_WIRE_LOWRANK): the rank r of the factorisation, 1 .. 16 (default 4). Shared
+    // (in shared_hash): it sizes the P and Q buffers the ranks allreduce.
+    std::atomic<long long> wire_lowrank_rank{4};
     // keyed rounds: 1 — a completion thread waits for a round's data plane and fires its done()
     // calls while the engine thread negotiates and enqueues the next round; 0 — the engine
     // thread waits for each round before negotiating the next (as the reference's recv thread
@@ -157,7 +160,7 @@ struct Config {
     // Hash of the tunables every rank of a communicator must share (they shape the collectives'
     // programs, the fusion plans and the host chunks): algo, slice_bytes, rings, max_slices,
     // fusion_threshold_bytes, tune, fusion_pipeline_bytes, reference_order, host_chunk_bytes,
-    // rccl_min_ctas, rccl_max_ctas, wire_topk_ppm.
+    // rccl_min_ctas, rccl_max_ctas, wire_topk_ppm, wire_lowrank_rank.
     // Never 0 or kCfgMismatch. Local tunables (log_level, cycle_time_us, host_copy_threads,
     // host_zero_copy, pipeline_rounds, one_rank_shortcut, wire_feedback_epoch, wire_stochastic_seed) are not
     // in it.

@@ -114,6 +114,8 @@ RequestHandler::~RequestHandler() {
     if (dims_) (void)hipFree(dims_);
     for (auto &kv : residuals_)  // the error-feedback residuals live as long as the handler
         if (kv.second.ptr) (void)hipFree(kv.second.ptr);
+    for (auto &kv : lowrank_states_)  // and the low-rank wire's Q
+        if (kv.second.ptr) (void)hipFree(kv.second.ptr);
     host_.reset();  // the host path's slots, streams and registrations (its work waits on stream_)
     if (stream_) (void)hipStreamDestroy(stream_);
 }
@@ -147,6 +149,12 @@ void validate(const Request &r, int size) {
                                 !r.topk && (r.op == DDL_ALLREDUCE_OP_SUM || r.op == DDL_ALLREDUCE_OP_AVG),
                             DDL_STATUS_INVALID_ARGUMENT, "the sign wire takes a float32 device SUM or AVG request and no other flag");
                 check_sign_ranks(size);
+            }
+            if (r.lowrank) {  // what take_lowrank lets through
+                DDL_REQUIRE(r.dtype == DDL_FLOAT && !r.host && r.wire == 0 && !r.feedback && !r.stochastic && !r.sumsq &&
+                                !r.topk && !r.sign && (r.op == DDL_ALLREDUCE_OP_SUM || r.op == DDL_ALLREDUCE_OP_AVG),
+                            DDL_STATUS_INVALID_ARGUMENT, "the low-rank wire takes a float32 device SUM or AVG request and no other flag");
+                check_lowrank_elements(r.n);
             }
             DDL_REQUIRE(r.wire != kDtypeE4m3 || !op_is_minmax(r.op), DDL_STATUS_INVALID_ARGUMENT,
                         "the e4m3 wire takes SUM or AVG");
@@ -529,10 +537,10 @@ std::vector<int> plan_ops(const Plan &p, const std::vector<Request> &reqs, const
 // Engine thread only. hipMalloc does not wait for the device (profiles/r06/s17); the zeroing is
 // posted on stream_, so it runs after every earlier pack of this key and before the next one. A
 // residual of another element count is retired, not freed: its last pack may still be running. A key that
-// comes back under another family of wire (the 16-bit wires, e4m3, top-k, sign) restarts from zero.
+// comes back under another family of wire (the 16-bit wires, e4m3, top-k, sign, low-rank) restarts from zero.
 void *RequestHandler::residual_(const Request &r) {
     const long long epoch = config().wire_feedback_epoch.load();
-    const int family = r.sign ? kFamilySign : r.topk ? kFamilyTopk : r.wire == kDtypeE4m3 ? kFamilyE4m3 : kFamily16;
+    const int family = r.lowrank ? kFamilyLowrank : r.sign ? kFamilySign : r.topk ? kFamilyTopk : r.wire == kDtypeE4m3 ? kFamilyE4m3 : kFamily16;
     Residual &res = residuals_[r.key];
     if (res.ptr && res.n == r.n && res.epoch == epoch && res.family == family) return res.ptr;
     res.family = family;
@@ -546,6 +554,28 @@ void *RequestHandler::residual_(const Request &r) {
     res.epoch = epoch;
     DDL_HIP(hipMemsetAsync(res.ptr, 0, r.n * sizeof(float), stream_));
     return res.ptr;
+}
+
+// The low-rank wire's Q of request r at rank `rk` (lowrank.h: C x rk floats, then rk alive flags), as residual_:
+// made, or restarted to all flags 0 — by a memset posted on stream_, an outgrown one retired — when the element
+// count or the rank changes or the key was last written by another family of wire. wire_feedback_epoch does NOT
+// restart it: Q is a subspace estimate, not gradient mass, and it must stay alike on every rank.
+void *RequestHandler::lowrank_state_(const Request &r, int rk) {
+    LowrankState &st = lowrank_states_[r.key];
+    const auto it = residuals_.find(r.key);
+    const bool same_family = it != residuals_.end() && it->second.family == kFamilyLowrank;
+    if (st.ptr && st.n == r.n && st.r == rk && same_family) return st.ptr;
+    const size_t bytes = lowrank_shape(r.n, rk).state_floats * sizeof(float);
+    if (st.n != r.n || st.r != rk) {
+        if (st.ptr) retire_device(st.ptr);
+        st.ptr = nullptr;
+        st.n = 0;
+        DDL_HIP(hipMalloc(&st.ptr, bytes));
+        st.n = r.n;
+        st.r = rk;
+    }
+    DDL_HIP(hipMemsetAsync(st.ptr, 0, bytes, stream_));
+    return st.ptr;
 }
 
 uint64_t RequestHandler::stochastic_stream_(const Request &r) {
@@ -635,11 +665,12 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
     // coefficients -> apply instead of an allreduce. The top-k wire (topk.h) is a fifth, after Adasum: whole
     // requests too, select -> emit -> gather -> combine (SUM and AVG share it: the quotient is rank-local).
     // The sign wire (sign.h) is a sixth, after top-k: whole requests, pack -> gather -> combine.
+    // The low-rank wire (lowrank.h) is a seventh, after sign: whole requests, two in-place SUM allreduces per plan.
     // Where the one-rank shortcut skips the data plane nothing is selected or packed: those requests are plain
     // SUM / AVG ones.
     const bool shortcut = data_->size() == 1 && config().one_rank_shortcut.load();
     auto kind_rank = [shortcut](const Request &r) {
-        return r.sign && !shortcut ? 5 : r.topk && !shortcut ? 4 : r.op == DDL_ALLREDUCE_OP_MIN ? 1 : r.op == DDL_ALLREDUCE_OP_MAX ? 2 : r.op == DDL_ALLREDUCE_OP_ADASUM ? 3 : 0;
+        return r.lowrank && !shortcut ? 6 : r.sign && !shortcut ? 5 : r.topk && !shortcut ? 4 : r.op == DDL_ALLREDUCE_OP_MIN ? 1 : r.op == DDL_ALLREDUCE_OP_MAX ? 2 : r.op == DDL_ALLREDUCE_OP_ADASUM ? 3 : 0;
     };
     std::map<std::tuple<int, int, int, int, int>, std::vector<size_t>> groups;
     for (size_t i = 0; i < reqs.size(); ++i) {
@@ -678,7 +709,8 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
         const bool adasum = std::get<3>(g.first) == 3;  // (its plans take AdasumSegs, not these)
         const bool topk = std::get<3>(g.first) == 4;    // (TopkSegs; always fused)
         const bool sign = std::get<3>(g.first) == 5;    // (SignSegs; always fused)
-        const bool entire = adasum || topk || sign;     // plans of whole requests, run by a pipe of their own
+        const bool lowrank = std::get<3>(g.first) == 6;  // (LowrankSegs; always fused)
+        const bool entire = adasum || topk || sign || lowrank;  // plans of whole requests, run by a pipe of their own
         std::vector<PlanSeg> whole;
         whole.reserve(fused && !entire ? g.second.size() : 0);
         for (size_t q = 0; fused && !entire && q < g.second.size(); ++q) {
@@ -742,6 +774,21 @@ void RequestHandler::allreduce_reqs_(std::vector<Request> &reqs, std::vector<Don
                               for (int q = 0; q < P; ++q) dsp[(size_t)q] = (size_t)q * per;
                               data_->allgatherv(send, recv, cnt.data(), dsp.data(), DDL_FLOAT, stream_);
                           });
+            } else if (lowrank) {
+                // a = input + residual projected on the name's Q, ONE in-place SUM allreduce of the plan's P
+                // buffer, orthonormalised, projected back, ONE of its Q buffer, then the reconstruct writes every
+                // request's output and residual; a tensor too small to compress rides whole in the first buffer
+                const int P = data_->size(), rk = (int)config().wire_lowrank_rank.load();
+                std::vector<LowrankSeg> segs;
+                for (size_t q = p.req_begin; q <= p.req_end; ++q) {
+                    const Request &r = reqs[g.second[q]];
+                    const bool small = lowrank_shape(r.n, rk).small;  // (no residual, no state)
+                    void *state = small ? nullptr : lowrank_state_(r, rk);  // (before residual_: it reads the family)
+                    segs.push_back(LowrankSeg{r.in, r.out, small ? nullptr : residual_(r), state, r.n, r.prescale, r.postscale, r.op});
+                }
+                lowrank_.run(segs.data(), (int)segs.size(), P, data_->rank(), rk, stream_, [&](void *buf, size_t elems) {
+                    data_->allreduce(buf, buf, elems, DDL_FLOAT, DDL_ALLREDUCE_OP_SUM, stream_);
+                });
             } else if (host) {
                 // memcpy in -> MPI_Allreduce -> memcpy out (MPIRingTokenCommunication.cc:548-733),
                 // the allreduce on the device through pinned chunks

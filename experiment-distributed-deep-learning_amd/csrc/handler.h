@@ -34,6 +34,7 @@
 #include "adasum.h"
 #include "topk.h"
 #include "sign.h"
+#include "lowrank.h"
 #include "engine.h"
 #include "fusion.h"
 #include "host_stage.h"
@@ -63,6 +64,7 @@ struct Request {
     bool stochastic = false;          // allreduce: DDL_ALLREDUCE_WIRE_STOCHASTIC (only with the bf16 `wire`; rank-local)
     bool topk = false;                // allreduce: DDL_ALLREDUCE_WIRE_TOPK (fp32 device SUM / AVG; `wire` stays 0: what travels is no dtype)
     bool sign = false;                // allreduce: DDL_ALLREDUCE_WIRE_SIGN (fp32 device SUM / AVG; `wire` stays 0, as for top-k)
+    bool lowrank = false;             // allreduce: DDL_ALLREDUCE_WIRE_LOWRANK (fp32 device SUM / AVG; `wire` stays 0, as for top-k)
     double *sumsq = nullptr;          // allreduce: where the sum of squares of `out` goes before done() (host; rank-local)
     // allreduce: DDL_ALLREDUCE_SCALE's factors (1 = absent; fp32 device SUM / AVG requests). Rank-local like
     // the op and `sumsq`: in no group key, plan cut, pipeline cut or negotiation.
@@ -194,6 +196,9 @@ private:
     TopkPipe topk_;
     // DDL_ALLREDUCE_WIRE_SIGN plans: pack -> gather -> combine (sign.h)
     SignPipe sign_;
+    // DDL_ALLREDUCE_WIRE_LOWRANK plans: project -> allreduce -> orthonormalise -> back-project -> allreduce ->
+    // reconstruct (lowrank.h)
+    LowrankPipe lowrank_;
     // Error feedback (DDL_ALLREDUCE_WIRE_FEEDBACK, DDL_ALLREDUCE_WIRE_E4M3_FEEDBACK): what the wire's rounding removed from this rank's
     // contribution to a key, added back at the key's next request. One fp32 array per key that ever
     // asked for feedback, owned here and freed with the handler (a replaced one is retired, never
@@ -202,13 +207,23 @@ private:
         void *ptr = nullptr;
         size_t n = 0;         // elements
         long long epoch = 0;  // config wire_feedback_epoch when it was last (re)started
-        int family = 0;       // kFamily16 (fp16 and bf16 share it), kFamilyE4m3, kFamilyTopk or kFamilySign: the rule that last wrote it
+        int family = 0;       // kFamily16 (fp16 and bf16 share it), kFamilyE4m3, kFamilyTopk, kFamilySign or kFamilyLowrank: the rule that last wrote it
     };
-    static constexpr int kFamily16 = 1, kFamilyE4m3 = 2, kFamilyTopk = 3, kFamilySign = 4;
+    static constexpr int kFamily16 = 1, kFamilyE4m3 = 2, kFamilyTopk = 3, kFamilySign = 4, kFamilyLowrank = 5;
     std::unordered_map<std::string, Residual> residuals_;
     // the residual of request r for a pack posted on stream_: made, or restarted from zero (another
     // element count, another epoch, the other family of wire), by work posted on stream_ ahead of that pack
     void *residual_(const Request &r);
+    // The low-rank wire's Q per key, beside its residual: C x r floats and r alive flags (lowrank.h), kept until
+    // the handler goes. wire_feedback_epoch restarts the residual only.
+    struct LowrankState {
+        void *ptr = nullptr;
+        size_t n = 0;  // elements of the request
+        int r = 0;     // the rank it was made for
+    };
+    std::unordered_map<std::string, LowrankState> lowrank_states_;
+    // the Q of request r at rank rk, made or restarted (another element count, rank or family of wire) on stream_
+    void *lowrank_state_(const Request &r, int rk);
     // Stochastic rounding (DDL_ALLREDUCE_WIRE_STOCHASTIC): a key's sequence number n — how many requests of
     // the key with the bit this handler has packed before — one of the four things a request's stream key S
     // is mixed from (ddl_amd.h). One entry per key that ever carried the bit, kept until the handler goes.

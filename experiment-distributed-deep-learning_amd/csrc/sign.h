@@ -15,6 +15,7 @@
 #include <functional>
 
 #include "common.h"
+#include "plan_scratch.h"
 
 namespace ddl {
 
@@ -46,14 +47,7 @@ public:
     void run(const SignSeg *segs, int count, int P, int rank, hipStream_t stream, const Gather &gather);
 
 private:
-    struct Table {  // the segment table's pinned staging and its device copy, rewritten once `ready` has passed
-        void *host = nullptr, *dev = nullptr;
-        size_t cap = 0;
-        hipEvent_t ready = nullptr;
-    };
-    static constexpr int kTables = 4;
-    Table tab_[kTables];
-    int next_ = 0;
+    PlanTables tables_;       // the segment tables (plan_scratch.h)
     void *gather_ = nullptr;  // P slots
     size_t gather_cap_ = 0;
 };

@@ -194,32 +194,14 @@ __global__ void __launch_bounds__(256) k_sign_combine(const uint32_t *__restrict
 }  // namespace
 
 SignPipe::~SignPipe() {
-    for (Table &t : tab_) {
-        if (t.ready) (void)hipEventSynchronize(t.ready);
-        if (t.ready) (void)hipEventDestroy(t.ready);
-        if (t.host) (void)hipHostFree(t.host);
-        if (t.dev) (void)hipFree(t.dev);
-    }
     if (gather_) (void)hipFree(gather_);
 }
 
 void SignPipe::run(const SignSeg *segs, int count, int P, int rank, hipStream_t stream, const Gather &gather) {
     DDL_REQUIRE(segs && count >= 1 && P >= 1 && rank >= 0 && rank < P, DDL_STATUS_INVALID_ARGUMENT, "bad sign plan");
     // the table, in pinned staging
-    Table &tb = tab_[next_];
-    next_ = (next_ + 1) % kTables;
-    if (!tb.ready) DDL_HIP(hipEventCreateWithFlags(&tb.ready, hipEventDisableTiming));
-    else DDL_HIP(hipEventSynchronize(tb.ready));  // its last upload has been consumed
     const size_t table = (size_t)count * sizeof(SgSeg);
-    if (table > tb.cap) {
-        retire_host(tb.host);
-        retire_device(tb.dev);
-        tb.host = tb.dev = nullptr;
-        tb.cap = table + table / 2;
-        DDL_HIP(hipHostMalloc(&tb.host, tb.cap, hipHostMallocDefault));
-        DDL_HIP(hipMalloc(&tb.dev, tb.cap));
-    }
-    SgSeg *t = static_cast<SgSeg *>(tb.host);
+    SgSeg *t = static_cast<SgSeg *>(tables_.stage(table));
     uint64_t blocks = 0;
     for (int i = 0; i < count; ++i) {
         const SignSeg &s = segs[i];
@@ -245,20 +227,11 @@ void SignPipe::run(const SignSeg *segs, int count, int P, int rank, hipStream_t 
         blocks += nb;
         DDL_REQUIRE(blocks < (1ull << 31), DDL_STATUS_INVALID_ARGUMENT, "sign plan too large");
     }
-    DDL_HIP(hipMemcpyAsync(tb.dev, tb.host, table, hipMemcpyHostToDevice, stream));
-    DDL_HIP(hipEventRecord(tb.ready, stream));
-    const SgSeg *dd = static_cast<const SgSeg *>(tb.dev);
+    const SgSeg *dd = static_cast<const SgSeg *>(tables_.upload(stream));
 
     const uint64_t words = blocks * kSignBlockWords;
     const size_t slot_bytes = (size_t)words * 4, need = (size_t)P * slot_bytes;
-    if (need > gather_cap_) {  // may still be read on the device: retired, not freed (common.h retire_device)
-        if (gather_) retire_device(gather_);
-        gather_ = nullptr;
-        gather_cap_ = 0;
-        DDL_HIP(hipMalloc(&gather_, need + need / 2));
-        gather_cap_ = need + need / 2;
-    }
-    char *g = static_cast<char *>(gather_);
+    char *g = static_cast<char *>(grow_retire(gather_, gather_cap_, need));
     uint32_t *own = reinterpret_cast<uint32_t *>(g + (size_t)rank * slot_bytes);
 
     const dim3 grid((unsigned)((blocks + 3) / 4)), wg(256);  // one wave per block

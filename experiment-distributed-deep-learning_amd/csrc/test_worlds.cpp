@@ -331,6 +331,19 @@ void ThreadWorld::sign(const SignSeg *segs, int count, size_t threshold, hipStre
     });
 }
 
+void ThreadWorld::lowrank(const LowrankSeg *segs, int count, size_t threshold, int rk, hipStream_t user) {
+    while (lowranks_.size() < (size_t)P_) lowranks_.emplace_back(new LowrankPipe);
+    std::vector<size_t> elems;
+    for (int i = 0; i < count; ++i) elems.push_back(segs[i].n);
+    const auto plans = adasum_plans(elems, threshold);
+    const RingConfig cfg = config().ring();
+    run_(user, [&](int r, hipStream_t s) {
+        for (const auto &p : plans)
+            lowranks_[r]->run(segs + (size_t)r * count + p.first, (int)(p.second - p.first), P_, r, rk, s,
+                              [&](void *buf, size_t n) { ex_[r]->allreduce(buf, buf, n, DDL_FLOAT, s, cfg, DDL_ALLREDUCE_OP_SUM); });
+    });
+}
+
 size_t ThreadWorld::fused_allreduce(const PlanSeg *segs, int count, int dtype, int src_dtype, size_t cap,
                                     hipStream_t user, const RingConfig &cfg, double *sumsq_out,
                                     std::vector<std::pair<size_t, size_t>> *cuts) {

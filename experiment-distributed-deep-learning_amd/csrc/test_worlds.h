@@ -17,6 +17,7 @@
 #include "adasum.h"
 #include "topk.h"
 #include "sign.h"
+#include "lowrank.h"
 #include "engine.h"
 #include "executor.h"
 
@@ -194,6 +195,10 @@ public:
     // The keyed path's sign group on every rank (adasum_plans' whole-request plans, SignPipe::run per plan), laid
     // out as topk's; the residuals are the caller's.
     void sign(const SignSeg *segs, int count, size_t threshold, hipStream_t user);
+    // The keyed path's low-rank group on every rank (adasum_plans' whole-request plans, LowrankPipe::run per plan at
+    // rank `rk`, each rank's executor's in-place SUM allreduce as the callback), laid out as sign's; the residuals
+    // and the Q states are the caller's.
+    void lowrank(const LowrankSeg *segs, int count, size_t threshold, int rk, hipStream_t user);
 
 private:
     void run_(hipStream_t user, const std::function<void(int, hipStream_t)> &body);
@@ -204,6 +209,7 @@ private:
     std::vector<std::unique_ptr<AdasumPipe>> adasums_;  // one per rank (adasum; packs with pipes_[r]'s copier)
     std::vector<std::unique_ptr<TopkPipe>> topks_;      // one per rank (topk)
     std::vector<std::unique_ptr<SignPipe>> signs_;      // one per rank (sign)
+    std::vector<std::unique_ptr<LowrankPipe>> lowranks_;  // one per rank (lowrank)
     std::vector<hipStream_t> streams_;
     std::vector<hipEvent_t> done_;
     hipEvent_t fork_ = nullptr;

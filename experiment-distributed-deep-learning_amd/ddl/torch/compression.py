@@ -101,6 +101,23 @@ measured. One fp32 copy of each gradient in device memory per request NAME (stab
 refuses it), one read of gradient and residual and one write of the residual per element (csrc/sign.hip). No
 `sumsq` (ValueError; so none of the wrapper's norm tracking), SUM and AVG only, fp32 only — any other tensor of a
 call is submitted uncompressed. `reset_error_feedback()` restarts these residuals too.
+
+Low rank: `Compression.powersgd` (include/ddl_amd.h, DDL_ALLREDUCE_WIRE_LOWRANK; PowerSGD, Vogels et al. 2019, what
+PyTorch's DDP ships as `powerSGD_hook`), the top rung. A tensor of n elements is viewed as a near-square matrix of
+R x C (C the least multiple of 64 with C^2 >= n); every rank adds its residual under a name, multiplies by the name's
+stored C x r matrix Q (r = 4 by default, `set_powersgd_rank`), the products are SUMMED over the ranks, orthonormalised,
+multiplied back and summed again, and the result is the rank-r matrix P Q^T; what that removed stays in the residual.
+It is REDUCED, not gathered: 8 r (R + C) bytes per tensor whatever the number of ranks (a 64 Mi-element tensor at
+r = 4: 0.5 MiB against 256 MiB, 512 times fewer), no rank cap, and unlike `topk` every element moves every step.
+One power iteration per step, warm-started from the last step's Q, so the subspace follows the gradients over
+steps. The honest costs: three passes over the gradient — about 28 bytes per element of device memory traffic
+against `bf16_feedback`'s 14 (csrc/lowrank.hip) —, a plan-sized fp32 scratch, TWO DEPENDENT allreduces of latency
+per plan, and per request NAME one fp32 copy of the gradient plus Q (stable names only: allreduce_gradient refuses
+it). A tensor too small to gain (2 r (R + C) > n) travels whole, uncompressed, in the same allreduce. A NaN or
+overflow anywhere in a tensor makes the whole result NaN on every rank and leaves the state alone. No `sumsq`
+(ValueError; so none of the wrapper's norm tracking), SUM and AVG only, fp32 only — any other tensor of a call is
+submitted uncompressed. `reset_error_feedback()` restarts the residuals but NOT Q: Q is a subspace estimate that
+must stay alike on every rank. No end-to-end time was measured.
 """
 import torch
 
@@ -116,7 +133,8 @@ class _Wire:
 
     @property
     def feedback(self) -> bool:
-        return bool(self.flag & (cb.WIRE_FEEDBACK | cb.WIRE_E4M3_FEEDBACK | cb.WIRE_TOPK | cb.WIRE_SIGN))  # a residual per name
+        return bool(self.flag & (cb.WIRE_FEEDBACK | cb.WIRE_E4M3_FEEDBACK | cb.WIRE_TOPK | cb.WIRE_SIGN |
+                                 cb.WIRE_LOWRANK))  # a residual per name
 
     @property
     def stochastic(self) -> bool:
@@ -151,6 +169,7 @@ class Compression:
     fp8_all = _Wire('fp8_all', cb.WIRE_E4M3, (torch.float32, torch.bfloat16))
     topk = _Wire('topk', cb.WIRE_TOPK)
     onebit = _Wire('onebit', cb.WIRE_SIGN)
+    powersgd = _Wire('powersgd', cb.WIRE_LOWRANK)
 
 
 def wire_flag(compression) -> int:
@@ -159,7 +178,7 @@ def wire_flag(compression) -> int:
         return 0
     if not isinstance(compression, _Wire):
         raise TypeError('compression must be Compression.none, .fp16, .bf16, .fp16_feedback, .bf16_feedback, '
-                        f'.bf16_stochastic, .fp8, .fp8_feedback, .fp8_all, .topk or .onebit, not {compression!r}')
+                        f'.bf16_stochastic, .fp8, .fp8_feedback, .fp8_all, .topk, .onebit or .powersgd, not {compression!r}')
     return compression.flag
 
 
@@ -170,7 +189,7 @@ def wire_dtypes(compression) -> tuple:
 
 
 def reset_error_feedback() -> None:
-    """Restart every error-feedback residual of this process — the 16-bit kinds', `fp8_feedback`'s, `topk`'s and `onebit`'s — from zero at its next use (raises the
+    """Restart every error-feedback residual of this process — the 16-bit kinds', `fp8_feedback`'s, `topk`'s, `onebit`'s and `powersgd`'s (not its Q) — from zero at its next use (raises the
     engine's per-process `wire_feedback_epoch` by one). Call it after loading a checkpoint, or after
     a change of the loss scale by a large factor: the residuals describe gradients that no longer
     exist. Rank-local: nothing is communicated, the ranks need not call it together."""
@@ -188,6 +207,15 @@ def set_topk_density(fraction: float) -> None:
     if not 1 <= ppm <= 1000000:
         raise ValueError(f'set_topk_density: a fraction in [1e-6, 1], not {fraction!r}')
     cb.check(cb.CPPBackend.c_api().ddl_set_config(b'wire_topk_ppm', ppm), 'ddl_set_config(wire_topk_ppm)')
+
+
+def set_powersgd_rank(r: int) -> None:
+    """Set the rank r of `Compression.powersgd`'s factorisation (the engine's SHARED `wire_lowrank_rank`, default 4;
+    an integer in [1, 16], else ValueError). Shared as `set_topk_density`'s key: set it alike on every rank between
+    the same two collectives. A name's Q restarts when r changes."""
+    if isinstance(r, bool) or not isinstance(r, int) or not 1 <= r <= 16:
+        raise ValueError(f'set_powersgd_rank: an integer in [1, 16], not {r!r}')
+    cb.check(cb.CPPBackend.c_api().ddl_set_config(b'wire_lowrank_rank', r), 'ddl_set_config(wire_lowrank_rank)')
 
 
 def set_stochastic_seed(seed: int) -> None:

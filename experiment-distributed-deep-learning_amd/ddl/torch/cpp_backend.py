@@ -49,6 +49,7 @@ WIRE_E4M3 = 0x20000  # enum ddl_allreduce_wire8: block-scaled e4m3fn granules; n
 WIRE_E4M3_FEEDBACK = 0x40000  # enum ddl_allreduce_wire8_feedback: error feedback of the e4m3 pack; only with WIRE_E4M3
 WIRE_TOPK = 0x80000  # enum ddl_allreduce_wire_sparse: top-k (index, value) pairs with error feedback; no other wire bit, no SUMSQ
 WIRE_SIGN = 0x100000  # enum ddl_allreduce_wire_sign: one sign bit per element, one fp32 magnitude per 2048, error feedback; no other wire bit, no SUMSQ
+WIRE_LOWRANK = 0x200000  # enum ddl_allreduce_wire_lowrank: PowerSGD rank-r factors with error feedback; no other wire bit, no SUMSQ
 SUMSQ = 0x2000  # enum ddl_allreduce_stat: `user` points to a SumsqArg (struct ddl_sumsq_arg)
 SCALE = 0x4000  # enum ddl_allreduce_scale: `user` points to a ScaleArg (struct ddl_scale_arg)
 MEMORY_DEVICE, MEMORY_HOST = 0, 1  # enum ddl_memory
@@ -178,6 +179,9 @@ class CPPBackend:
             ctypes.POINTER(sz), fp, fp, ci, vp)
         sig('ddl_testing_thread_sign', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
             ctypes.POINTER(sz), fp, fp, ci, vp)
+        sig('ddl_testing_thread_lowrank', ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
+            ctypes.POINTER(vp), ctypes.POINTER(sz), fp, fp, ci, vp)
+        sig('ddl_testing_lowrank_shape', ci, sz, ci, ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(sz))
         # (testing library: the same for native bfloat16 tensors)
         sig('ddl_pack_scale_dtype', ci, vp, ctypes.POINTER(vp), ctypes.POINTER(sz), ci, ci, fp, vp)
         sig('ddl_unpack_scale_dtype', ci, ctypes.POINTER(vp), vp, ctypes.POINTER(sz), ctypes.POINTER(ci), ci, ci, ci, fp,

@@ -81,6 +81,11 @@ its residual, and one magnitude per 2048 elements, and keeps what that removed u
 (ddl.torch.compression: 33/256 bytes per element, gathered rather than reduced, at most 16 ranks). It composes and
 refuses as `Compression.topk` does.
 
+`compression=Compression.powersgd`: PowerSGD — each dense fp32 device gradient plus its residual is sent as a rank-r
+factorisation (r = 4, `set_powersgd_rank`), summed over the ranks in two dependent allreduces, under the gradient's
+stable name (ddl.torch.compression: 8 r (R + C) bytes per tensor, reduced, no rank cap; three passes over the
+gradient). It composes and refuses as `Compression.topk` does.
+
 `track_grad_norm=True` (implied by `max_grad_norm` and `skip_nonfinite`): after
 `allreduce_gradients()`, `optimizer.grad_norm` is the global L2 norm of the averaged gradients (a
 float) and `optimizer.found_nonfinite` is `not math.isfinite(grad_norm)`. Every dense fp32 or bf16 device
@@ -486,6 +491,9 @@ def data_parallelism_distributed_optimizer_wrapper(
     if wire_flag(compression) & cb.WIRE_SIGN and (track_grad_norm or max_grad_norm is not None or skip_nonfinite):
         raise ValueError('Compression.onebit does not compose with track_grad_norm, max_grad_norm or skip_nonfinite: '
                          'the engine takes no sum of squares over the sign wire')
+    if wire_flag(compression) & cb.WIRE_LOWRANK and (track_grad_norm or max_grad_norm is not None or skip_nonfinite):
+        raise ValueError('Compression.powersgd does not compose with track_grad_norm, max_grad_norm or skip_nonfinite: '
+                         'the engine takes no sum of squares over the low-rank wire')
     res.compression = Compression.none if compression is None else compression
     res.track_grad_norm = bool(track_grad_norm)
     res.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)

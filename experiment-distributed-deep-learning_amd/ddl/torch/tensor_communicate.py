@@ -37,11 +37,12 @@ def _comm(communicator):
 
 
 def _check_op_compression(op, compression, sumsq=False) -> None:
-    """MIN / MAX never travel over a 16-bit wire, and Compression.topk and .onebit take no sumsq (the engine refuses
-    DDL_ALLREDUCE_SUMSQ with DDL_ALLREDUCE_WIRE_TOPK and _WIRE_SIGN): refused here, before any library call."""
+    """MIN / MAX never travel over a 16-bit wire, and Compression.topk, .onebit and .powersgd take no sumsq (the
+    engine refuses DDL_ALLREDUCE_SUMSQ with DDL_ALLREDUCE_WIRE_TOPK, _WIRE_SIGN and _WIRE_LOWRANK): refused here,
+    before any library call."""
     if int(op) in (cb.OP_MIN, cb.OP_MAX) and wire_flag(compression):
         raise ValueError(f'op {int(op)} (MIN / MAX) takes no compression, got {compression!r}')
-    if sumsq and wire_flag(compression) & (cb.WIRE_TOPK | cb.WIRE_SIGN):
+    if sumsq and wire_flag(compression) & (cb.WIRE_TOPK | cb.WIRE_SIGN | cb.WIRE_LOWRANK):
         raise ValueError(f'{compression!r} takes no sumsq')
 
 
@@ -134,7 +135,8 @@ def allreduce_gradient(tensor: torch.Tensor, communicator: Communicator = None,
         return allreduce_async(tensor, name, communicator, op=cb.OP_ADASUM).wait()
     if op is not None:
         raise ValueError(f'allreduce_gradient takes op=cb.OP_ADASUM or none, not {op!r}')
-    if wire_flag(compression) & (cb.WIRE_FEEDBACK | cb.WIRE_E4M3_FEEDBACK | cb.WIRE_TOPK | cb.WIRE_SIGN):  # (.topk and .onebit keep one too)
+    if wire_flag(compression) & (cb.WIRE_FEEDBACK | cb.WIRE_E4M3_FEEDBACK | cb.WIRE_TOPK | cb.WIRE_SIGN |
+                                 cb.WIRE_LOWRANK):  # (.topk, .onebit and .powersgd keep one too)
         raise ValueError(f'allreduce_gradient does not take {compression!r}: its compressed requests get a fresh '
                          'name per call, which would leak one error-feedback residual per call; use allreduce_async '
                          'with a stable name')

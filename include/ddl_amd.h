@@ -115,6 +115,12 @@ enum ddl_allreduce_wire_sparse { DDL_ALLREDUCE_WIRE_TOPK = 0x80000 };
  * for DDL_FLOAT device requests, optionally with DDL_ALLREDUCE_SCALE; never with any other wire, feedback or
  * stochastic flag, and never with DDL_ALLREDUCE_SUMSQ. */
 enum ddl_allreduce_wire_sign { DDL_ALLREDUCE_WIRE_SIGN = 0x100000 };
+/* The low-rank wire with error feedback (MI355X extension; PowerSGD, Vogels et al. 2019, PyTorch's powerSGD_hook;
+ * "The low-rank wire" in the data-plane section): every rank sends a rank-r factorisation of its tensor plus its
+ * residual, reduced over the ranks in two dependent allreduces, and keeps what that removed. OR-ed into the `op`
+ * (SUM or AVG) of the keyed entry points for DDL_FLOAT device requests, optionally with DDL_ALLREDUCE_SCALE; never
+ * with any other wire, feedback or stochastic flag, and never with DDL_ALLREDUCE_SUMSQ. */
+enum ddl_allreduce_wire_lowrank { DDL_ALLREDUCE_WIRE_LOWRANK = 0x200000 };
 /* Sum of squares of a keyed device allreduce of DDL_FLOAT or DDL_BFLOAT16 tensors (MI355X extension; the data-plane
  * section): OR-ed into the `op` of ddl_allreduce_submit / _submit_batch (and _submit_mem /
  * _submit_batch_mem with DDL_MEMORY_DEVICE), SUM or AVG, with or without a wire flag. With the bit
@@ -235,7 +241,8 @@ int ddl_is_initialized(void);
  * "wire_stochastic_seed" (0, default; per process: the seed of the random bits of
  * DDL_ALLREDUCE_WIRE_STOCHASTIC, the data-plane section; its 64 bits are read when a request is packed;
  * rank-local like "wire_feedback_epoch", not a shared tunable), "wire_topk_ppm" (10000, default; shared: the
- * density of DDL_ALLREDUCE_WIRE_TOPK in parts per million, 1 .. 1000000), "pipeline_rounds" (1,
+ * density of DDL_ALLREDUCE_WIRE_TOPK in parts per million, 1 .. 1000000), "wire_lowrank_rank" (4, default; shared:
+ * the rank r of DDL_ALLREDUCE_WIRE_LOWRANK, 1 .. 16), "pipeline_rounds" (1,
  * default: a completion thread fires a keyed round's done() calls as its plans land while the
  * engine thread negotiates the next round; 0: each round is waited for first), "reference_order" (1,
  * default: every allreduce sum equals the reference's MPI_Allreduce — MPICH 3.3.2 — bit for
@@ -246,7 +253,8 @@ int ddl_is_initialized(void);
  * slice size) per bucket-size class (floor(log2 bytes)) the first time it sees that class: a
  * collective timing of a fixed candidate list on scratch buffers, max over ranks, argmin.
  * The shared tunables (algo, slice_bytes, rings, max_slices, fusion_threshold_bytes, tune,
- * fusion_pipeline_bytes, reference_order, host_chunk_bytes, rccl_min_ctas, rccl_max_ctas, wire_topk_ppm) must
+ * fusion_pipeline_bytes, reference_order, host_chunk_bytes, rccl_min_ctas, rccl_max_ctas, wire_topk_ppm,
+ * wire_lowrank_rank) must
  * be equal on every rank of a
  * communicator. Direct collectives: the ranks exchange a hash of them at a communicator's first
  * collective and at the next collective after this rank's values changed; a mismatch found there
@@ -577,6 +585,53 @@ void py_error(const char *log_str);
  * ranks return DDL_STATUS_INVALID_ARGUMENT, a dtype other than DDL_FLOAT DDL_STATUS_UNSUPPORTED_DTYPE; the unkeyed
  * entry points refuse the flag as an unknown op. P = 1: with "one_rank_shortcut" 1 nothing is packed and no
  * residual is made (the scaled input comes back); with 0 the data plane runs and the rule applies.
+ *
+ * The low-rank wire: DDL_ALLREDUCE_WIRE_LOWRANK = 0x200000, OR-ed into op SUM or AVG (optionally with
+ * DDL_ALLREDUCE_SCALE) on the keyed entry points, DDL_FLOAT device tensors. r is the SHARED config key
+ * "wire_lowrank_rank" (1 .. 16, default 4; it sizes what the ranks exchange, so a mismatch between ranks is
+ * DDL_STATUS_CONFIG_MISMATCH, never a hang). A request of n elements is the row-major matrix M of R x C with
+ * C = 64 ceil(sqrt(n) / 64), computed in integers (the least multiple of 64 whose square is >= n), and
+ * R = ceil(n / C); M is zero beyond element n, and nothing at or past n is ever read or written. (The C-ABI
+ * carries no shape; the square view is what PyTorch's batched hook uses and it maximises the compression at a
+ * given rank.) A tensor with 2 r (R + C) > n is not worth compressing: its a = fl32(g (x) prescale) travels whole
+ * inside the first allreduce's buffer and out = post(sum), with AVG's quotient; it has no residual and no state.
+ * State per key, rank-local and kept until the communicator goes: the error e (fp32, n elements, zero the first
+ * time; the residual of the other wires with a family of its own) and Q (C x r fp32, row-major) with r alive flags.
+ * Q restarts to all flags 0 when n, r or the family of wire of the key changes. "wire_feedback_epoch" restarts e
+ * ONLY: Q is a subspace estimate, not gradient mass, and it must stay alike on every rank — the ranks need not
+ * raise the epoch together. One step, all arithmetic fp32 round to nearest even unless said otherwise:
+ *     1. a_i = fl32(g_i (x) prescale) (+) e_i          two roundings, never contracted (g itself without a prescale)
+ *     2. P_loc = A Q_used (R x r): column j of Q_used is the stored column where its alive flag is set, else
+ *        qinit(c, j) = (float)(int32)fmix32(16 c + j + 0x9e3779b9) x 2^-31 (fmix32: MurmurHash3's finaliser; 32-bit
+ *        wrap-around) — a function of the indices only, the same on every rank with nothing communicated. The sum
+ *        over c is fp32 in an order the engine fixes (K-splits of 512 columns, added in split order).
+ *     3. ONE in-place fp32 SUM allreduce of the plan's buffer: all P matrices, r columns each, then the small tensors.
+ *     4. P^ = the summed P orthonormalised by modified Gram-Schmidt in column order, dots and norms accumulated
+ *        in fp64: for i < j, p_j = fl32(fma(-(p_i . p_j), p_i, p_j)) in fp64 per element; then with s = p_j . p_j:
+ *        s exactly 0 makes column j zeros and its alive flag 0 (it reseeds itself next step — a zero gradient or
+ *        an exactly rank-deficient sum is harmless, with no scale-dependent epsilon); s not finite POISONS the
+ *        tensor; otherwise p_j = fl32(p_j / sqrt(s)) in fp64 and the flag is 1.
+ *     5. Q_loc = A^T P^ (C x r), fp32 in an order the engine fixes (K-splits of 512 rows).
+ *     6. ONE in-place fp32 SUM allreduce of all Q_loc.
+ *     7. Q- = Q^ (/) (float)P, correctly rounded; any non-finite entry poisons the tensor.
+ *     8. D-_ic = the fma chain over j = 0 .. r - 1, from +0.0, of P^_ij Q-_cj; e'_i = a_i (-) D-_i, +0.0 where that
+ *        is not finite; out = post(D-) for AVG, post(D- (x) (float)P) for SUM; the stored Q <- Q-, flags from 4.
+ *     9. A poisoned tensor stores 0x7fc00000 in every element of out on every rank and leaves e, Q and the flags
+ *        exactly as they were. The decision comes from allreduced data, so every rank decides alike.
+ * The sum over the ranks of e' plus P D- equals the sum of the a: exactly compensated. Every rank stores the same
+ * bits: the two allreduces are the engine's, and every kernel between them has a fixed summation order.
+ * Requests with the flag form fusion groups of their own, after the sign wire's. A tensor is never cut: a plan
+ * holds whole requests, a request above "fusion_threshold_bytes" is a plan of its own, nothing is pipelined. What
+ * travels is 8 r (R + C) bytes per tensor in TWO DEPENDENT allreduces per plan, against 4 n: it is REDUCED, not
+ * gathered, so it does not grow with the number of ranks and has no rank cap. The costs: three passes over the
+ * gradient, about 28 bytes per element of device memory traffic; a plan-sized scratch (4 n bytes for a);
+ * EVERY DISTINCT KEY THAT EVER CARRIED THE FLAG HOLDS 4 n + 4 r (C + 1) BYTES. e is in prescaled units.
+ * tests/_lowrank_helpers.py restates the rule in NumPy.
+ * Refusals, before anything is registered (the communicator works afterwards): any other wire, feedback or
+ * stochastic flag, DDL_ALLREDUCE_SUMSQ, MIN, MAX or ADASUM, DDL_MEMORY_HOST and 2^31 or more elements return
+ * DDL_STATUS_INVALID_ARGUMENT, a dtype other than DDL_FLOAT DDL_STATUS_UNSUPPORTED_DTYPE; the unkeyed entry points
+ * refuse the flag as an unknown op. P = 1: with "one_rank_shortcut" 1 nothing is projected and no state is made
+ * (the scaled input comes back); with 0 the data plane runs and the rule applies.
  *
  * MIN / MAX: DDL_ALLREDUCE_OP_MIN = 3 and DDL_ALLREDUCE_OP_MAX = 4, on every dtype and every
  * allreduce entry point. Per element over the P inputs: DDL_INT32 / DDL_INT64 in signed order,

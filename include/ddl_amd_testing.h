@@ -335,6 +335,18 @@ int ddl_testing_thread_topk(int nranks, int count, const void *const *srcs, void
 int ddl_testing_thread_sign(int nranks, int count, const void *const *srcs, void *const *dsts, void *const *residuals,
                             const size_t *elements, const float *prescale, const float *postscale, int op,
                             void *hip_stream);
+/* The matrix view of an n-element request of the low-rank wire at rank r (ddl_amd.h "The low-rank wire"): *R rows,
+ * *C columns, and *state_floats = C r + r 4-byte words of Q state (Q, then the r alive flags; all zero = restarted),
+ * 0 for a tensor that travels whole. */
+int ddl_testing_lowrank_shape(size_t n, int r, size_t *R, size_t *C, size_t *state_floats);
+/* A DDL_ALLREDUCE_WIRE_LOWRANK request group (csrc/lowrank.hip) over nranks virtual ranks on threads, as the keyed
+ * handler runs it: whole-request plans under "fusion_threshold_bytes" at rank "wire_lowrank_rank", the two SUM
+ * allreduces of each plan by the rank's executor. Arguments as ddl_testing_thread_sign's, plus qstates[rank * count
+ * + i]: the caller-owned Q state of state_floats words (a tensor that travels whole uses neither its residual nor
+ * its state: both may be null). */
+int ddl_testing_thread_lowrank(int nranks, int count, const void *const *srcs, void *const *dsts, void *const *residuals,
+                               void *const *qstates, const size_t *elements, const float *prescale,
+                               const float *postscale, int op, void *hip_stream);
 /* The kernels of the e4m3 wire (DDL_ALLREDUCE_WIRE_E4M3; ddl_amd.h "The e4m3 wire"; csrc/pack.hip k_seg<Q8PackOp> /
  * k_seg<Q8UnpackOp>, csrc/reduce_kernels.hip k_foldq). The tensors hold elements[i] fp32 values (4-byte aligned);
  * segment i of the flat buffer is its ceil(elements[i] / 252) granules of 256 bytes at the running sum of the
